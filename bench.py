@@ -3,13 +3,15 @@
 cache_len = 4096 after an 8k-token prompt (BASELINE.json metric; SURVEY §8(d) config C3/C2 family), plus the
 HBM roofline of the dominant hot-path kernel and a CPU baseline of the same hot path.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one full decode token: 32 x (norm, wqkv GEMV, RoPE, evict-select + insert, GQA attention over
 the pruned cache, history update, wo, FFN) + LM head + greedy sampling, replayed from a hipGraph.
 N > 1 = tensor parallel over KV heads (cold_compress_amd/tp.py: RCCL all-reduce over xGMI), same model and
-token stream -> "strong" scaling.  Prints ONE JSON line on rank 0.
+token stream -> "strong" scaling.  Prints ONE JSON line on rank 0.  --dump-outputs DIR: what the last timed step returned
+(next token, probability row), as DIR/next_token.npy (float64) and DIR/probs.npy (float32); the weights and the prompt are seeded,
+so the same arguments give the same inputs on every run.
 """
 import argparse
 import ctypes as C
@@ -48,6 +50,8 @@ def parse():
     ap.add_argument("--roofline_iters", type=int, default=20)
     ap.add_argument("--no_live_pmc", action="store_true", help="take roofline.traffic from profiles/ instead of two rocprofv3 --pmc child runs")
     ap.add_argument("--pmc_child", action="store_true", help=argparse.SUPPRESS)  # the workload rocprofv3 is wrapped around
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (next token, probabilities) to DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -697,10 +701,26 @@ def _stage_collectives_through_host():
     dist.all_reduce, dist.broadcast = all_reduce, broadcast
 
 
+def dump_outputs(out_dir, tok, probs):
+    """What the last timed decode step handed its caller: the greedy next token and the probability row over the vocabulary
+    (0.5 MB at the 8B vocabulary).  Copied before anything else runs: a replayed graph reuses its output buffers."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"next_token": tok.detach().reshape(-1).to("cpu", torch.float64).numpy(),
+              "probs": probs.detach().reshape(-1).to("cpu", torch.float32).numpy()}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    print(f"[bench] outputs of the last timed step written to {out_dir}: " +
+          ", ".join(f"{n} {a.dtype} {list(a.shape)}" for n, a in arrays.items()), file=sys.stderr)
+
+
 def _self_launch(args):
-    """`python bench.py --gpus N` without a launcher: re-exec under torch.distributed.run with N ranks (one per GPU,
-    RCCL over xGMI), exactly the command the driver would have used.  Never silently runs TP=1 for --gpus N."""
+    """`python bench.py --gpus N` without a launcher: run under torch.distributed.run with N ranks (one per GPU, RCCL over
+    xGMI) in a child process, exactly the command the driver would have used, and exit with its status.  Never silently runs
+    TP=1 for --gpus N."""
     import socket
+    import subprocess
 
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -711,7 +731,7 @@ def _self_launch(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     print(f"[bench] --gpus {args.gpus} without WORLD_SIZE: launching {args.gpus} ranks: {' '.join(cmd)}", file=sys.stderr)
-    os.execv(sys.executable, cmd)
+    sys.exit(subprocess.call(cmd))
 
 
 def main():
@@ -719,7 +739,7 @@ def main():
     if args.pmc_child:
         return pmc_child()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        _self_launch(args)  # does not return
+        _self_launch(args)  # exits
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -778,10 +798,12 @@ def main():
         # per layer the GPU side of a token (~3 ms) hides the ~200 Python launches, and graph replay measured 2.4 %
         # SLOWER than eager on one GPU; under tensor parallelism the per-rank work shrinks and the graph wins.  Default:
         # time both on a few untimed tokens and keep the faster (ranks agree through a MAX all-reduce).
+        probs = None
+
         def run_with(dec_fn, n):
-            nonlocal cur
+            nonlocal cur, probs
             for _ in range(n):
-                nt, _ = dec_fn(model, cur, pos)
+                nt, probs = dec_fn(model, cur, pos)
                 cur = nt.view(1, 1)
                 pos.add_(1)
 
@@ -834,6 +856,8 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, cur, probs)
         dev_state = device_state() if rank == 0 else {}
         if world > 1:
             t = torch.tensor([dt], device=dev, dtype=torch.float64)

@@ -7,7 +7,7 @@ under tests/golden/.  The GPU box never sees the reference.
 
     PYTHONDONTWRITEBYTECODE=1 python oracle/gen_golden.py [--out tests/golden]
     ... --seed_offset N [--jitter_shapes] --out SOME_OTHER_DIR     (r5) the same families from other seeds (and shapes): fresh vectors
-        for differential runs (tests/test_oracle_fresh_seeds.py; CC_GOLDEN_DIR=DIR pytest ...); offset 0 without jitter = the committed files
+        for differential runs (tools/fuzz_fresh_seeds.sh; CC_GOLDEN_DIR=DIR pytest ...); offset 0 without jitter = the committed files
 
 Fixtures:
   f1_e2e_<strategy>.npz   tiny-Llama end-to-end runs through generation_utils.generate
@@ -21,6 +21,8 @@ Fixtures:
   f5_compress.npz         prompt_compression.* priorities -> keep_idxs (+ boundary-tie flags)
   f7_attn_<dtype>.npz     attention_utils.scaled_dot_product_attention decode + small prefill
   f8_budgets.json         generation_utils budget arithmetic
+  f8_budgets_random.json  the same arithmetic on 1000 random inputs (value, or the exception's type name)
+  f8_setup_random.json    setup_caches on 80 random configurations: normalised keyword lists and per-layer cache / compressor classes
   f9_quant_*.npz          --cache_bits: quantize/dequantize known answers, quantised heavy-hitter / recent-global replays
                           (the K/V attention sees at every step + the final int8 / packed images), one end-to-end run
 Low-precision tensors are stored as their uint16 bit patterns with a "<name>__dtype" tag.
@@ -36,7 +38,7 @@ import torch
 
 REF = "/root/reference"
 
-SEED_OFFSET = 0  # --seed_offset: every seed below is shifted by it (0 = the committed fixtures; tests/test_oracle_fresh_seeds.py uses others)
+SEED_OFFSET = 0  # --seed_offset: every seed below is shifted by it (0 = the committed fixtures; tools/fuzz_fresh_seeds.sh uses others)
 
 
 JITTER = False  # --jitter_shapes: the cache replays (f2 / f3 / f4 / f9) also move their lengths, windows and step counts with the offset
@@ -621,6 +623,92 @@ def attn_topk_case(A):
 # ------------------------------------------------------------------------------------------------ F8
 
 
+def budgets_random(G, M):
+    """normalize_cache_length, apply_pyramid_pattern, apply_pattern and find_multiple on random inputs: [case, answer] pairs."""
+    import contextlib
+    import io
+    import random
+
+    rng = random.Random(20260928 + SEED_OFFSET)
+    cases = []
+    for _ in range(400):
+        mx = rng.choice([52, 77, 1000, 4096, 8192, 10240, 18432, 34816, rng.randint(16, 40000)])
+        v = rng.choice([round(rng.uniform(0.01, 1.0), rng.choice([1, 2, 3])), 1, rng.randint(2, 2 * mx), float(rng.randint(2, mx))])
+        cases.append(["normalize", [v, mx]])
+    for _ in range(300):
+        mx = rng.choice([4096, 10240, 18432, 34816])
+        n = rng.choice([2, 4, 8, 16, 32, 80, rng.randint(2, 64)])
+        cases.append(["pyramid", [rng.choice([64, 256, 300, 512, 1024, 2560, 3488, rng.randint(32, mx // 2)]), mx, n, rng.random() < 0.7]])
+    for _ in range(200):
+        pat = [rng.choice([128, 512, 1024, "a", 0.5]) for _ in range(rng.choice([1, 1, 2, 4]))]
+        n = rng.choice([4, 8, 16, 32, 6])
+        cases.append(["pattern", [pat, n, rng.choice(["tile", "repeat", "pyramid", "funnel"]), rng.choice([4096, 18432])]])
+    for _ in range(100):
+        cases.append(["find_multiple", [rng.randint(0, 5000), rng.choice([1, 8, 16, 256])]])
+    out = []
+    for fn, args in cases:
+        f = {"normalize": G.normalize_cache_length, "pyramid": lambda a, b, c, d: G.apply_pyramid_pattern(a, b, c, decreasing=d),
+             "pattern": lambda p, n, s, m: G.apply_pattern(p, n, s, m), "find_multiple": M.find_multiple}[fn]
+        try:
+            with contextlib.redirect_stdout(io.StringIO()):
+                want = f(*args)
+        except Exception as e:
+            want = type(e).__name__
+        out.append([[fn, args], want])
+    return json.loads(json.dumps(out))  # (tuples as lists, as the test reads them back)
+
+
+def setup_random(C, G, M):
+    """setup_caches (generation_utils.py:324-388, model.py:191-233) on random configurations: [[n_layer, max_seq, kwargs], answer]
+    pairs; the answer is the normalised keyword lists and per layer the cache class, its length, buffer shape, window, sinks and
+    the prompt compressor's class, or the exception's type name."""
+    import contextlib
+    import io
+    import random
+
+    rng = random.Random(777 + SEED_OFFSET)
+    pairs = [("recent_global", "recent_global"), ("heavy_hitter", "heavy_hitter"), ("l2", "l2"), ("full", "full"), ("random", "random"),
+             ("keep_it_odd", "keep_it_odd"), ("recent_global", "l2"), ("l2", "recent_global")]
+    cases = []
+    for _ in range(80):
+        n_layer = rng.choice([2, 4, 8])
+        max_seq = rng.choice([96, 200, 256, 1000])
+        k = rng.choice([1, 1, 2])
+        strat = [rng.choice(pairs) for _ in range(k)]
+        lengths = [rng.choice([0.25, 0.5, 0.1, 1.0, 16, 32, 64, 24, 40]) for _ in range(rng.choice([1, 1, 2]))]
+        pat = rng.choice(["tile", "repeat", "tile", "repeat", "pyramid", "funnel"])
+        kw = dict(cache_strategy=[a for a, _ in strat], prompt_compression_strategy=[b for _, b in strat], max_cache_length=lengths,
+                  cache_length_pattern=pat, cache_strategy_pattern=rng.choice(["tile", "repeat"]), global_tokens=rng.choice([1, 4, 4, 8, 30]),
+                  recent_window=rng.choice([10, 4, 0.1, 0.5, 1, 100]))
+        if "full" in kw["cache_strategy"]:
+            kw["max_cache_length"] = [1.0]
+        cases.append([n_layer, max_seq, kw])
+    out = []
+    for n_layer, max_seq, kw in cases:
+        cfg = dict(TINY)
+        cfg["n_layer"] = n_layer
+        cfg["block_size"] = max(256, max_seq)
+        model = M.Transformer(M.ModelArgs(**cfg)).to(torch.float32).eval()
+        parser = argparse.ArgumentParser()
+        C.add_cache_arguments(parser)
+        G.add_generation_arguments(parser)
+        ck = vars(parser.parse_args([]))
+        ck.update(kw)
+        try:
+            with contextlib.redirect_stdout(io.StringIO()):
+                r = G.setup_caches(model, FakeTok(), "cpu", max_seq, dict(ck))
+            layers = [[type(l.attention.kv_cache).__name__, int(l.attention.kv_cache.max_cache_length), list(l.attention.kv_cache.pos.shape),
+                       int(getattr(l.attention.kv_cache, "recent_window", -1)), int(getattr(l.attention.kv_cache, "global_tokens", -1)),
+                       type(l.attention.prompt_compressor).__name__] for l in model.layers]
+            want = {"max_cache_length": list(r["max_cache_length"]), "recent_window": list(r["recent_window"]),
+                    "cache_strategy": list(r["cache_strategy"]), "prompt_compression_strategy": list(r["prompt_compression_strategy"]),
+                    "layers": layers}
+        except Exception as e:
+            want = type(e).__name__
+        out.append([[n_layer, max_seq, kw], want])
+    return json.loads(json.dumps(out))
+
+
 def budgets(G, M, C=None):
     rows = {"normalize": [], "pattern": [], "pyramid": [], "find_multiple": []}
     if C is not None:  # registry surface: relevant_kwargs per strategy + argparse defaults (cache.py:13-118, 1444-1478)
@@ -881,6 +969,14 @@ def main():
         # attn_thresholding=True cannot be captured: the reference itself raises at cache.py:721
         # ("Index put requires the source and destination dtypes match, got Bool ... and Int") on torch 2.10.
         if a.only == "f2w":
+            return
+
+    if a.only in (None, "f8r"):
+        for name, rows in (("f8_budgets_random.json", budgets_random(G, M)), ("f8_setup_random.json", setup_random(C, G, M))):
+            with open(os.path.join(a.out, name), "w") as f:
+                json.dump(rows, f, separators=(",", ":"))
+            print("wrote", name)
+        if a.only == "f8r":
             return
 
     if a.only in (None, "f7k"):

@@ -5,7 +5,7 @@ import numpy as np
 import torch
 
 # CC_GOLDEN_DIR: the same fixture families made by the reference from OTHER seeds (oracle/gen_golden.py --seed_offset N --out DIR; only
-# tests/test_oracle_fresh_seeds.py sets it, in the build container where /root/reference exists)
+# tools/fuzz_fresh_seeds.sh sets it, where the reference is at hand)
 GOLDEN = os.environ.get("CC_GOLDEN_DIR") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 # CC_TEST_DEVICE=cpu (with CC_TEST_CPU_TWIN=1, tests/conftest.py): the fixture-driven `-m gpu` tests run the product's Python layer on CPU

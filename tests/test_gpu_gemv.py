@@ -61,8 +61,22 @@ CASES = [
 @pytest.mark.parametrize("name,N,K,opt", CASES)
 def test_gemv_fused_matches_fp32_reference(oracle, dt, name, N, K, opt):
     if dt == torch.float32 and K * 4 > 64 * 1024:
-        pytest.skip("input vector beyond the LDS staging buffer for fp32 (the harness falls back to the library GEMV)")
+        _gemv_refused(dt, N, K)
+        return
     _gemv_case(oracle, dt, name, N, K, opt, N * 7 + K)
+
+
+def _gemv_refused(dt, N, K):
+    """An input vector beyond the kernel's 64 KiB LDS staging buffer (fp32 at K > 16384): the harness must not route the layer to
+    the fused GEMV (gemv_supported, so the model keeps the library GEMV), and a direct call is refused loudly before any launch."""
+    from cold_compress_amd import _abi
+    from cold_compress_amd.harness import glue
+
+    W = torch.empty(N, K, dtype=dt, device=DEV)
+    x = torch.empty(K, dtype=dt, device=DEV)
+    assert not glue.gemv_supported(W)
+    with pytest.raises(_abi.ColdCompressError, match="cc_gemv_fused"):
+        glue.gemv_fused(W, x)
 
 
 def test_gemv_fused_fuzz(oracle):

@@ -31,6 +31,7 @@ def main():
     ap.add_argument("--model", default="Meta-Llama-3.1-8B-Instruct", help="harness.CONFIGS key; Llama-3-70B-shape = BASELINE C5 (two layers of it)")
     ap.add_argument("--no_fuse_gemv", action="store_true", help="debugging: the sharded model's dense layers through torch (hipBLASLt)")
     ap.add_argument("--no_fuse_step", action="store_true", help="debugging: the sharded model's caches through the three-call path")
+    ap.add_argument("--one_rank_per_gpu", action="store_true", help="gloo: rank r drives GPU r instead of every rank driving cuda:0")
     ap.add_argument("--layers", type=int, default=2)
     ap.add_argument("--vocab", type=int, default=0, help="override the vocabulary size (0: the config's) — keeps eight ranks' host copies small")
     ap.add_argument("--cache", type=int, default=128, help="cache slots per layer (C5: 3488)")
@@ -45,8 +46,9 @@ def main():
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
         assert dist.get_backend() == "nccl" and dist.get_world_size() == world
     else:
-        torch.cuda.set_device(0)
-        dev = torch.device("cuda", 0)
+        d = rank if args.one_rank_per_gpu else 0
+        torch.cuda.set_device(d)
+        dev = torch.device("cuda", d)
         dist.init_process_group("gloo", rank=rank, world_size=world)
         orig = dist.all_reduce
 
