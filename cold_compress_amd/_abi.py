@@ -75,6 +75,11 @@ SIGNATURES = {
     "cc_decode_step_quant_rc": (C.c_int, [_view, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _i32, _i32, _i32,
                                           _f32, _vp, _vp, _sz, _vp, _i32]),
     "cc_decode_step_quant_single_launch": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "cc_decode_step_heavy_hitter_ring_quant": (C.c_int, [_view, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32,
+                                                         _i32, _f32, _vp, _vp, _vp, _sz, _vp]),
+    "cc_decode_step_hybrid_quant_rc": (C.c_int, [_view, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
+                                                 _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _sz, _vp]),
+    "cc_decode_step_hybrid_quant_single_launch": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "cc_decode_step_hybrid_single_launch": (_i32, [_i32, _i32, _i32, _i32, _i32]),
     "cc_decode_step_l2_single_launch": (_i32, [_i32, _i32, _i32, _i32, _i32]),
     "cc_decode_step_single_launch_enabled": (_i32, []),
@@ -167,6 +172,8 @@ DEVICE_ONLY = {"cc_error_string", "cc_device_info", "cc_decode_step_single_launc
                "cc_decode_step_hybrid_single_launch", "cc_decode_step_l2_single_launch", "cc_decode_step_single_launch_enabled", "cc_decode_step_device_single_launch",
                "cc_decode_step_qkv_available", "cc_debug_qkv_trace",
                "cc_kv_requant_batch",  # (its oracle is the per-cache twin of cc_kv_requant_pair)
+               # the fused quantised cache's ring and hybrid steps: their checker is the same policy's 16-bit step on the dequantised values
+               "cc_decode_step_heavy_hitter_ring_quant", "cc_decode_step_hybrid_quant_rc", "cc_decode_step_hybrid_quant_single_launch",
                # inter-GPU transport: no CPU twin (the oracle of the all-reduce is torch.distributed's)
                "cc_allreduce_handle_bytes", "cc_allreduce_create", "cc_allreduce_export", "cc_allreduce_connect", "cc_allreduce_sum",
                "cc_allreduce_status", "cc_allreduce_destroy"}

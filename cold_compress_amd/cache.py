@@ -128,7 +128,7 @@ class KVCache(nn.Module):
                 raise ColdCompressError("cache_quant_mode='fused' serves cache_bits=8, 16-bit models, head_dim 128")
             if not self._fused_quant_policy():
                 raise ColdCompressError(f"cache_quant_mode='fused' is not available for {type(self).__name__}: it serves "
-                                        "heavy_hitter (history_window_size 1), recent_global, full and random")
+                                        "heavy_hitter (any history_window_size), recent_global, full, random and hybrid")
             self.quantize = False  # none of the reference mode's round-trip machinery runs
         self.n_heads = n_heads
         self.head_dim = head_dim
@@ -441,6 +441,8 @@ def step_is_recoverable(cache, HQ, attention=None):
     args = (int(HQ), cache.n_heads, cache.max_cache_length, cache.head_dim, _DT[cache.k_cache.dtype])
     with torch.cuda.device(cache.k_cache.device):  # (residency and the dispatch-order verdict are facts of THAT device)
         if isinstance(cache, KVCacheHybrid):  # (isinstance: a subclass takes its parent's step)
+            if cache.fused_quant:
+                return bool(lib["cc_decode_step_hybrid_quant_single_launch"](*args, 8))
             return bool(lib["cc_decode_step_hybrid_single_launch"](*args))
         if cache.fused_quant:
             return bool(lib["cc_decode_step_quant_single_launch"](*args, 8))
@@ -839,7 +841,8 @@ class KVCacheHeavyHitter(_TrackedWindowSums, KVCacheHeadSpecific):
         return self.history_window_size == 1
 
     def _fused_quant_policy(self):
-        return 1 if int(getattr(self, "history_window_size", 1)) == 1 else 0
+        """1: cc_decode_step_quant's heavy-hitter step (W == 1); 5: cc_decode_step_heavy_hitter_ring_quant (W > 1)."""
+        return 1 if int(getattr(self, "history_window_size", 1)) == 1 else 5
 
     def update_kv(self, input_pos, k_val, v_val, is_prefill, **kwargs):
         self._next_valid = False  # the three-call path mutates pos / history outside the pipeline
@@ -880,6 +883,13 @@ class KVCacheHeavyHitter(_TrackedWindowSums, KVCacheHeadSpecific):
         code = _DT[self.k_cache.dtype]
         nbytes = _abi.lib()["cc_decode_attn_workspace_bytes"](HQ, self.n_heads, self.max_cache_length, D, code)
         ws = _workspace(nbytes, query.device)
+        if self.history_window_size != 1 and self.fused_quant:  # the ring step over the uint8 images (two launches, as in 16 bits)
+            wsum, acc = self._window_state()
+            _abi.call("cc_decode_step_heavy_hitter_ring_quant", self._view(), _ptr(self.kv_qparams), 8, _ptr(q), _ptr(k), _ptr(v), _ptr(p32),
+                      _ptr(self.attn_history_num), _ptr(self.attn_history_denom), _ptr(self.attn_counter), int(self.history_window_size),
+                      _ptr(acc), _ptr(wsum), _ptr(self.next_key), int(self.global_tokens), int(self.recent_window), HQ,
+                      1.0 / math.sqrt(D) if scale is None else scale, _ptr(y), None, _ptr(ws), ws.numel(), _stream())
+            return y
         if self.history_window_size != 1:
             wsum, acc = self._window_state()
             _abi.call("cc_decode_step_heavy_hitter_ring", self._view(), _ptr(q), _ptr(k), _ptr(v), _ptr(p32), _ptr(self.attn_history_num),
@@ -915,6 +925,8 @@ class KVCacheHeavyHitter(_TrackedWindowSums, KVCacheHeadSpecific):
     def single_launch_active(self, HQ):
         """True when decode_step runs as ONE launch for `HQ` query heads on this device."""
         if self.fused_quant:
+            if self.history_window_size != 1:  # the ring step has no single-launch form
+                return False
             return bool(self.single_launch and _abi.lib()["cc_decode_step_quant_single_launch"](
                 HQ, self.n_heads, self.max_cache_length, self.head_dim, _DT[self.k_cache.dtype], 8))
         return bool(self.single_launch and self.history_window_size == 1 and _abi.lib()["cc_decode_step_single_launch"](
@@ -1017,6 +1029,10 @@ class KVCacheHybrid(_TrackedWindowSums, KVCacheHeadSpecific):
                 "hybrid with cache_bits: the reference itself fails on this path (profile_and_update writes float rows "
                 "into the quantised int8 cache, cache.py:1228-1260: 'Index put requires the source and destination "
                 "dtypes match'), so there is no behaviour to reproduce or pin")
+        if self.fused_quant and not self._fused_shape_ok():
+            # (the 16-bit dtype and head_dim 128 are KVCache's checks; profiled heads are known at prefill, checked there)
+            raise ColdCompressError("cache_quant_mode='fused' for hybrid needs the fused decode step: at most 48 kv heads, at most 21 "
+                                    "policies and reset_history_on_evict = False")
         S, W = self.max_cache_length, self.history_window_size
         self.register_buffer("attn_history_num", torch.zeros((1, n_heads, S, W), dtype=dtype))
         self.register_buffer("attn_history_denom", torch.zeros((1, n_heads, S), dtype=torch.int32))
@@ -1104,11 +1120,34 @@ class KVCacheHybrid(_TrackedWindowSums, KVCacheHeadSpecific):
         return torch.argsort((~mask_optimal).to(torch.int8), dim=1, stable=True)
 
     # ------------------------------------------------------------------ fused decode step (1 or 2 launches per layer)
+    def _fused_quant_policy(self):
+        """cache_quant_mode='fused': cc_decode_step_hybrid_quant_rc (the step's policy code 6)."""
+        return 6
+
+    def _fused_shape_ok(self):
+        return (self.k_cache.dtype in (torch.bfloat16, torch.float16) and self.head_dim == 128 and not self.reset_history_on_evict
+                and self.n_heads <= 48 and len(self.hybrid_strategies) <= 21)
+
     def supports_fused_step(self):
         """cc_decode_step_hybrid: 16-bit caches with head_dim 128, profiled heads, and the reference's effective
         no-reset-on-evict behaviour (see the class docstring)."""
-        return (self.cache_strategies is not None and self.k_cache.dtype in (torch.bfloat16, torch.float16) and self.head_dim == 128
-                and not self.reset_history_on_evict and self.n_heads <= 48 and len(self.hybrid_strategies) <= 21)
+        return self.cache_strategies is not None and self._fused_shape_ok()
+
+    def single_launch_active(self, HQ):
+        """True when decode_step runs as ONE launch for `HQ` query heads on this device."""
+        lib = _abi.lib()
+        args = (HQ, self.n_heads, self.max_cache_length, self.head_dim, _DT[self.k_cache.dtype])
+        if not lib["cc_decode_step_single_launch_enabled"]():
+            return False
+        if self.fused_quant:
+            return bool(lib["cc_decode_step_hybrid_quant_single_launch"](*args, 8))
+        return bool(lib["cc_decode_step_hybrid_single_launch"](*args))
+
+    def step_status(self, HQ=None):
+        """0, or 1 if a single-launch step ever failed to complete its in-launch hand-off on this device (synchronises)."""
+        from .attention_utils import single_launch_status
+
+        return single_launch_status(self.pos.device)
 
     def _punc_operands(self, input_ids):
         if not hasattr(self, "punc_ids"):
@@ -1178,6 +1217,18 @@ class KVCacheHybrid(_TrackedWindowSums, KVCacheHeadSpecific):
         if self.requires_heavy_hitter:
             wsum, acc = self._window_state()
             ring, denom, counter = self.attn_history_num, self.attn_history_denom, self.attn_counter
+        if self.fused_quant:  # the same step over the uint8 images: the insert writes the token's image and row parameters
+            if not self.supports_fused_step():
+                raise ColdCompressError("cache_quant_mode='fused': the hybrid cache has no fused decode step for this state "
+                                        "(see supports_fused_step)")
+            _abi.call("cc_decode_step_hybrid_quant_rc", self._view(), _ptr(self.kv_qparams), 8, _ptr(q), _ptr(k), _ptr(v), _ptr(p32),
+                      _ptr(self.cache_strategies), _ptr(tab), tab.shape[0], _ptr(ring), _ptr(denom), _ptr(counter),
+                      self.history_window_size, _ptr(acc), _ptr(wsum), _ptr(getattr(self, "special_mask", None)),
+                      _ptr(getattr(self, "punc_mask", None)), _ptr(tok), _ptr(pids), 0 if pids is None else pids.numel(),
+                      _ptr(getattr(self, "num_special", None)), _ptr(getattr(self, "num_punc", None)), _ptr(self.next_key),
+                      _ptr(self.step_commit), int(self.global_tokens), HQ, 1.0 / math.sqrt(D) if scale is None else scale, _ptr(y),
+                      None, _ptr(ws), ws.numel(), _stream())
+            return y
         _abi.call("cc_decode_step_hybrid_rc", self._view(), _ptr(q), _ptr(k), _ptr(v), _ptr(p32), _ptr(self.cache_strategies), _ptr(tab),
                   tab.shape[0], _ptr(ring), _ptr(denom), _ptr(counter), self.history_window_size, _ptr(acc), _ptr(wsum),
                   _ptr(getattr(self, "special_mask", None)), _ptr(getattr(self, "punc_mask", None)), _ptr(tok), _ptr(pids),
@@ -1190,6 +1241,9 @@ class KVCacheHybrid(_TrackedWindowSums, KVCacheHeadSpecific):
     def _decoding_update(self, input_pos, k_val, v_val, **kwargs):
         if self.cache_strategies is None:
             raise ColdCompressError("hybrid cache used before prefill profiling (update_state with is_prefill=True)")
+        if self.fused_quant:
+            raise ColdCompressError("cache_quant_mode='fused': decode through decode_step() — the three-call path would have to "
+                                    "materialise the dequantised cache every step, which is what this mode exists to avoid")
         self._next_valid = False  # the three-call path mutates pos / counts / history outside the pipeline
         k, v = self._new_rows(k_val, v_val)
         tok = pids = None
@@ -1337,6 +1391,8 @@ class KVCacheHybrid(_TrackedWindowSums, KVCacheHeadSpecific):
         t = torch.arange(L, device=dev)
         mask_all = torch.stack([cols | (t >= L - win if win else zeros).unsqueeze(0) for cols, win in filling])  # [n,H,L]
         mask_optimal = mask_all.gather(0, self.cache_strategies.view(1, H, 1).expand(1, H, L)).squeeze(0)
+        if self.fused_quant and not self.supports_fused_step():  # (never a three-call path over the images)
+            raise ColdCompressError("cache_quant_mode='fused': the profiled hybrid cache has no fused decode step (see supports_fused_step)")
         chosen = [self.hybrid_strategies[i]["strategy"] for i in self.cache_strategies.tolist()]
         self.requires_heavy_hitter = any("heavy_hitter" in n for n in chosen)
         self.requires_punc = any("punc" in n for n in chosen)
@@ -1349,13 +1405,25 @@ class KVCacheHybrid(_TrackedWindowSums, KVCacheHeadSpecific):
         pos_ord = input_pos.to(dev).to(torch.int64).unsqueeze(0).expand(H, -1).gather(1, order).contiguous()
         self.cache_cts.zero_()
         self.mask.zero_()
-        _abi.call("cc_prefill_fill", self._view(), _ptr(k_ord), _ptr(v_ord), _ptr(pos_ord), H, L, _stream())
+        if self.fused_quant:  # the rows land in the model-dtype staging pair in partition order; quantised once the dead ones are zero
+            kw_, vw_ = self._fused_scratch()
+            kw_.zero_()
+            vw_.zero_()
+            view = C.byref(KVView(kw_.data_ptr(), vw_.data_ptr(), self.pos.data_ptr(), self.mask.data_ptr(), self.cache_cts.data_ptr(),
+                                  H, self.pos.shape[1], self.cache_cts.shape[0], S, D, _DT[self.k_cache.dtype]))
+        else:
+            kw_, vw_ = self.k_cache[0], self.v_cache[0]
+            view = self._view()
+        _abi.call("cc_prefill_fill", view, _ptr(k_ord), _ptr(v_ord), _ptr(pos_ord), H, L, _stream())
         cts = mask_optimal.sum(dim=1).to(torch.int32)
         self.cache_cts.copy_(cts)
         live = torch.arange(S, device=dev).view(1, S) < cts.view(H, 1)  # [H,S]
         self.pos[0].masked_fill_(~live, -1)
-        self.k_cache[0].masked_fill_(~live.unsqueeze(-1), 0)
-        self.v_cache[0].masked_fill_(~live.unsqueeze(-1), 0)
+        kw_.masked_fill_(~live.unsqueeze(-1), 0)
+        vw_.masked_fill_(~live.unsqueeze(-1), 0)
+        if self.fused_quant:
+            _abi.call("cc_kv_quant_rows", _ptr(kw_), _ptr(vw_), H, S, D, _DT[self.k_cache.dtype], 8, _ptr(self.k_cache_q),
+                      _ptr(self.v_cache_q), _ptr(self.kv_qparams), _stream())
         self.mask[0, :, 0, :] = live & (torch.arange(S, device=dev).view(1, S) < L)
         if hasattr(self, "special_mask"):
             self.special_mask[0, :, :L] = sm.unsqueeze(0).expand(H, -1).gather(1, order)

@@ -562,7 +562,10 @@ static int launch_split(const SplitArgs& a, const Plan& p, int H, int R, int D, 
       //  their use — was measured at S = 18432: 27.3 instead of 25.4 us per step, the uint8 instantiation 31.5 instead of 25.4; like
       //  768 / 1024 workgroups, more bytes in flight per CU make this access pattern slower, not faster.  Not instantiated.)
       int rc;
-      if (a.qparams != nullptr) {  // fused quantised cache: 4 or 8 query heads per kv head
+      if (a.qparams != nullptr && a.hyb.strategies != nullptr) {  // the hybrid cache over uint8 images
+        if (p.rt != 4 && p.rt != 8) return CC_ERR_UNSUPPORTED;
+        rc = p.nw == 8 ? launch_mfma_rt<T, false, true, 8, 1, 8>(a, p.rt, grid, block, st) : launch_mfma_rt<T, false, true, 8, 1>(a, p.rt, grid, block, st);
+      } else if (a.qparams != nullptr) {  // fused quantised cache: 4 or 8 query heads per kv head
         if (p.rt != 4 && p.rt != 8) return CC_ERR_UNSUPPORTED;
         rc = p.nw == 8 ? launch_mfma_rt<T, false, false, 8, 1, 8>(a, p.rt, grid, block, st) : launch_mfma_rt<T, false, false, 8, 1>(a, p.rt, grid, block, st);
       } else if (a.hyb.strategies != nullptr) {
@@ -661,7 +664,7 @@ static int one_capacity(void (*kernel)(CC_LEAD_TYPES SplitArgs), int threads) {
 }
 typedef void (*OneKernel)(CC_LEAD_TYPES SplitArgs);
 // The single-launch kernel that serves (query heads per kv head rt, tiles per wave nt, kind), or null.  kind: 0 = 16-bit cache
-// (heavy hitter / head-constant policies), 8 = fused quantised cache, -1 = l2, 200 = hybrid.  full: the instantiation with the
+// (heavy hitter / head-constant policies), 8 = fused quantised cache, -1 = l2, 200 = hybrid, 208 = hybrid over uint8 images.  full: the instantiation with the
 // measurement hooks and attn_out (bf16, rt = 4 only).  ONE table for the residency check and the launch.
 template <typename T>
 static OneKernel one_kernel(int rt, int nt, int kind, bool full, int nw = kNW) {
@@ -673,7 +676,12 @@ static OneKernel one_kernel(int rt, int nt, int kind, bool full, int nw = kNW) {
   if (nw == 8) {  // ONE 8-wave workgroup per CU: 4 or 8 query heads per kv head, one tile per wave (make_plan)
 #define CC_ONE_W(RT_, L2_, QB_, FULL_) decode_attn_split_mfma_kernel<T, RT_, 8, L2_, true, false, QB_, 1, 1, FULL_>
 #define CC_ONE_WH(RT_, FULL_) decode_attn_split_mfma_kernel<T, RT_, 8, false, true, true, 0, 1, 1, FULL_>
-    if ((kind != 0 && kind != 8 && kind != -1 && kind != 200) || nt != 1 || (rt != 4 && rt != 8)) return nullptr;
+    if ((kind != 0 && kind != 8 && kind != -1 && kind != 200 && kind != 208) || nt != 1 || (rt != 4 && rt != 8)) return nullptr;
+    if (kind == 208) {  // lean only
+      if (full) return nullptr;
+      return rt == 8 ? decode_attn_split_mfma_kernel<T, 8, 8, false, true, true, 8, 1, 1, false>
+                     : decode_attn_split_mfma_kernel<T, 4, 8, false, true, true, 8, 1, 1, false>;
+    }
     if (full) {
       if constexpr (ElemTraits<T>::code != CC_DT_BF16) {
         return nullptr;
@@ -703,7 +711,12 @@ static OneKernel one_kernel(int rt, int nt, int kind, bool full, int nw = kNW) {
       return nullptr;
     }
   }
-  if (kind == 200 && nt > 8) return nullptr;
+  if ((kind == 200 || kind == 208) && nt > 8) return nullptr;
+  if (kind == 208) {  // hybrid over uint8 images: 4 or 8 query heads per kv head; one tile per wave or up to eight
+    if (rt == 8) return nt == 1 ? CC_ONE_K(8, false, true, 8, 1, false) : CC_ONE_K(8, false, true, 8, 8, false);
+    if (rt == 4) return nt == 1 ? CC_ONE_K(4, false, true, 8, 1, false) : CC_ONE_K(4, false, true, 8, 8, false);
+    return nullptr;
+  }
   if (kind == 200) {  // hybrid: 4 or 8 query heads per kv head; one tile per wave or up to eight
     if (rt == 8) return nt == 1 ? CC_ONE_K(8, false, true, 0, 1, false) : CC_ONE_K(8, false, true, 0, 8, false);
     if (rt == 4) return nt == 1 ? CC_ONE_K(4, false, true, 0, 1, false) : CC_ONE_K(4, false, true, 0, 8, false);
@@ -890,6 +903,9 @@ int32_t cc_decode_step_quant_single_launch(int32_t HQ, int32_t H, int32_t S, int
 int32_t cc_decode_step_hybrid_single_launch(int32_t HQ, int32_t H, int32_t S, int32_t D, int32_t dtype) {
   return one_available(HQ, H, S, D, dtype, 200);
 }
+int32_t cc_decode_step_hybrid_quant_single_launch(int32_t HQ, int32_t H, int32_t S, int32_t D, int32_t dtype, int32_t n_bit) {
+  return n_bit == 8 ? one_available(HQ, H, S, D, dtype, 208) : 0;
+}
 int32_t cc_decode_step_l2_single_launch(int32_t HQ, int32_t H, int32_t S, int32_t D, int32_t dtype) {
   return one_available(HQ, H, S, D, dtype, -1);
 }
@@ -1016,7 +1032,7 @@ static int attn_impl(const void* q, const void* k, const void* v, const uint8_t*
   if (D != 16 && D != 32 && D != 64 && D != 128) return CC_ERR_UNSUPPORTED;
   if (workspace_bytes < cc_decode_attn_workspace_bytes(HQ, H, S, D, dtype)) return CC_ERR_WORKSPACE;
   // what rides the streaming pass decides the plan (one_kernel's kinds)
-  const int kind = !fs ? 0 : (fs->qparams ? 8 : (fs->policy == 4 ? -1 : (fs->policy == 6 ? 200 : 0)));
+  const int kind = !fs ? 0 : (fs->qparams ? (fs->policy == 6 ? 208 : 8) : (fs->policy == 4 ? -1 : (fs->policy == 6 ? 200 : 0)));
   const Plan p = make_plan(HQ, H, S, D, dtype, ((phases >> 8) & 32) != 0);  // (measurement bit 32 forces the VALU pass: 4 waves)
   if ((size_t)R * p.n_split * sizeof(float) > 64 * 1024) return CC_ERR_UNSUPPORTED;  // combine-kernel LDS budget
   char* ws = reinterpret_cast<char*>(workspace) + kOneBytes;  // the single-launch regions come first, at fixed offsets
@@ -1050,8 +1066,9 @@ static int attn_impl(const void* q, const void* k, const void* v, const uint8_t*
     sa.g = fs->g;
   }
   if (fs && fs->qparams) {
-    if (cc_dt_size(dtype) != 2 || D != 128 || (fs->policy != 1 && fs->policy != 2 && fs->policy != 3) || rh || probs_out ||
-        ((phases >> 8) & 32) || (p.rt != 4 && p.rt != 8))
+    // (the ring history rides the heavy hitter's W > 1 step (policy 5) and the hybrid step (6) only)
+    if (cc_dt_size(dtype) != 2 || D != 128 || fs->policy < 1 || fs->policy > 6 || fs->policy == 4 || (rh && fs->policy < 5) ||
+        probs_out || ((phases >> 8) & 32) || (p.rt != 4 && p.rt != 8))
       return CC_ERR_UNSUPPORTED;
     sa.qparams = fs->qparams;
   }
@@ -1451,13 +1468,29 @@ int cc_decode_step_heavy_hitter_ring(const cc_kv_view* c, const void* q, const v
                    workspace, workspace_bytes, stream, 3, &fs, &rh);
 }
 
-int cc_decode_step_hybrid_rc(const cc_kv_view* c, const void* q, const void* k_new, const void* v_new, const int32_t* input_pos,
-                             const int64_t* strategies, const int32_t* policy_table, int32_t n_policies, void* ring_num,
-                             int32_t* denom, int64_t* counter, int32_t W, uint64_t* wsum_acc, float* wsum, const uint8_t* special_mask,
-                             uint8_t* punc_mask, const int64_t* token_id, const int64_t* punc_ids, int32_t n_punc_ids,
-                             const int32_t* num_special, int32_t* num_punc, uint64_t* next_key, int32_t* step_commit,
-                             int32_t global_tokens, int32_t HQ, float scale, void* y, void* attn_out, void* workspace,
-                             size_t workspace_bytes, cc_stream_t stream) {
+int cc_decode_step_heavy_hitter_ring_quant(const cc_kv_view* c, float* qparams, int32_t n_bit, const void* q, const void* k_new,
+                                           const void* v_new, const int32_t* input_pos, void* ring_num, int32_t* denom, int64_t* counter,
+                                           int32_t W, uint64_t* wsum_acc, float* wsum, uint64_t* next_key, int32_t global_tokens,
+                                           int32_t recent_window, int32_t HQ, float scale, void* y, void* attn_out, void* workspace,
+                                           size_t workspace_bytes, cc_stream_t stream) {
+  if (!cc_view_ok(c) || !qparams || !q || !k_new || !v_new || !input_pos || !next_key || !y || c->Hp != c->H || HQ <= 0 || HQ % c->H)
+    return CC_ERR_BAD_ARG;
+  if (n_bit != 8) return CC_ERR_UNSUPPORTED;
+  FusedStep fs{c, k_new, v_new, input_pos, reinterpret_cast<unsigned long long*>(next_key), global_tokens, recent_window, 5, nullptr,
+               nullptr, nullptr, qparams};
+  RingHistory rh{ring_num, W, wsum_acc, wsum};
+  return attn_impl(q, c->k_cache, c->v_cache, c->mask, HQ, c->H, c->S, c->D, c->dtype, scale, y, attn_out, nullptr, nullptr, denom, counter,
+                   workspace, workspace_bytes, stream, 3, &fs, &rh);
+}
+
+// the hybrid step over a 16-bit cache (qparams == null) or over uint8 images (the fused quantised cache)
+static int decode_step_hybrid_impl(const cc_kv_view* c, float* qparams, const void* q, const void* k_new, const void* v_new,
+                                   const int32_t* input_pos, const int64_t* strategies, const int32_t* policy_table, int32_t n_policies,
+                                   void* ring_num, int32_t* denom, int64_t* counter, int32_t W, uint64_t* wsum_acc, float* wsum,
+                                   const uint8_t* special_mask, uint8_t* punc_mask, const int64_t* token_id, const int64_t* punc_ids,
+                                   int32_t n_punc_ids, const int32_t* num_special, int32_t* num_punc, uint64_t* next_key,
+                                   int32_t* step_commit, int32_t global_tokens, int32_t HQ, float scale, void* y, void* attn_out,
+                                   void* workspace, size_t workspace_bytes, cc_stream_t stream) {
   if (!cc_view_ok(c) || !q || !k_new || !v_new || !input_pos || !strategies || !policy_table || n_policies <= 0 || !next_key || !y ||
       c->Hp != c->H || c->Hc != c->H || HQ <= 0 || HQ % c->H || W <= 0 || (punc_ids && n_punc_ids < 0) ||
       (ring_num && (!denom || !counter || !wsum_acc || !wsum)))
@@ -1467,12 +1500,39 @@ int cc_decode_step_hybrid_rc(const cc_kv_view* c, const void* q, const void* k_n
   hs.token_id = token_id; hs.punc_ids = punc_ids; hs.n_punc_ids = n_punc_ids; hs.num_special = num_special; hs.num_punc = num_punc;
   hs.W = W; hs.n_pol = n_policies;
   if (n_policies * 3 > 64) return CC_ERR_UNSUPPORTED;  // the streaming pass fetches the whole policy table with one vector load
-  FusedStep fs{c, k_new, v_new, input_pos, reinterpret_cast<unsigned long long*>(next_key), global_tokens, 0, 6, nullptr, nullptr, &hs};
+  FusedStep fs{c, k_new, v_new, input_pos, reinterpret_cast<unsigned long long*>(next_key), global_tokens, 0, 6, nullptr, nullptr, &hs,
+               qparams};
   fs.commit = step_commit;
   RingHistory rh{ring_num, W, wsum_acc, wsum};
   return attn_impl(q, c->k_cache, c->v_cache, c->mask, HQ, c->H, c->S, c->D, c->dtype, scale, y, attn_out, nullptr, nullptr,
                    ring_num ? denom : nullptr, ring_num ? counter : nullptr, workspace, workspace_bytes, stream, 3, &fs,
                    ring_num ? &rh : nullptr);
+}
+
+int cc_decode_step_hybrid_rc(const cc_kv_view* c, const void* q, const void* k_new, const void* v_new, const int32_t* input_pos,
+                             const int64_t* strategies, const int32_t* policy_table, int32_t n_policies, void* ring_num,
+                             int32_t* denom, int64_t* counter, int32_t W, uint64_t* wsum_acc, float* wsum, const uint8_t* special_mask,
+                             uint8_t* punc_mask, const int64_t* token_id, const int64_t* punc_ids, int32_t n_punc_ids,
+                             const int32_t* num_special, int32_t* num_punc, uint64_t* next_key, int32_t* step_commit,
+                             int32_t global_tokens, int32_t HQ, float scale, void* y, void* attn_out, void* workspace,
+                             size_t workspace_bytes, cc_stream_t stream) {
+  return decode_step_hybrid_impl(c, nullptr, q, k_new, v_new, input_pos, strategies, policy_table, n_policies, ring_num, denom, counter,
+                                 W, wsum_acc, wsum, special_mask, punc_mask, token_id, punc_ids, n_punc_ids, num_special, num_punc,
+                                 next_key, step_commit, global_tokens, HQ, scale, y, attn_out, workspace, workspace_bytes, stream);
+}
+
+int cc_decode_step_hybrid_quant_rc(const cc_kv_view* c, float* qparams, int32_t n_bit, const void* q, const void* k_new,
+                                   const void* v_new, const int32_t* input_pos, const int64_t* strategies, const int32_t* policy_table,
+                                   int32_t n_policies, void* ring_num, int32_t* denom, int64_t* counter, int32_t W, uint64_t* wsum_acc,
+                                   float* wsum, const uint8_t* special_mask, uint8_t* punc_mask, const int64_t* token_id,
+                                   const int64_t* punc_ids, int32_t n_punc_ids, const int32_t* num_special, int32_t* num_punc,
+                                   uint64_t* next_key, int32_t* step_commit, int32_t global_tokens, int32_t HQ, float scale, void* y,
+                                   void* attn_out, void* workspace, size_t workspace_bytes, cc_stream_t stream) {
+  if (!qparams) return CC_ERR_BAD_ARG;
+  if (n_bit != 8) return CC_ERR_UNSUPPORTED;
+  return decode_step_hybrid_impl(c, qparams, q, k_new, v_new, input_pos, strategies, policy_table, n_policies, ring_num, denom, counter,
+                                 W, wsum_acc, wsum, special_mask, punc_mask, token_id, punc_ids, n_punc_ids, num_special, num_punc,
+                                 next_key, step_commit, global_tokens, HQ, scale, y, attn_out, workspace, workspace_bytes, stream);
 }
 
 int cc_decode_step_hybrid(const cc_kv_view* c, const void* q, const void* k_new, const void* v_new, const int32_t* input_pos,

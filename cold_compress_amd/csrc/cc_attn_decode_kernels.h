@@ -817,7 +817,8 @@ struct IntC {
 // step (heavy hitter, recent_global / full, random; with L2: l2; with HYB: the FastGen hybrid cache) — needs R == RT, at most
 // 64 workgroups per kv head, every workgroup of the grid co-resident.  HYB: the per-head decision of KVCacheHybrid at the top of
 // the pass (two-launch form: candidates, ring and counts follow in the combine pass; with ONE: in the tail, on all lanes).
-// QB = 8: the fused quantised cache (uint8 images + per-row (scale, minimum)), dequantised on the way to the LDS slabs.
+// QB = 8: the fused quantised cache (uint8 images + per-row (scale, minimum)), dequantised on the way to the LDS slabs; with HYB the
+// hybrid cache's decision and bookkeeping are unchanged, only its insert writes the token's image and row parameters.
 // NSUB = 2 (multi-tile splits only): two tiles per wave and iteration, each with its own staging registers — the loads of a
 // tile go out two half-iterations ahead of their use instead of one (twice the bytes in flight per wave).
 // NT (ONE only): tiles per wave the single-launch step keeps scores for — 1 for caches up to 64 x 64 slots per kv head (the
@@ -915,9 +916,10 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
   auto apply_lead = [&]() {};
 #endif
   static_assert(!(HYB && L2), "the hybrid decision rides the plain streaming pass or the single-launch step");
-  static_assert(QB == 0 || (QB == 8 && !L2 && !HYB), "fused quantised cache: 8 bits, heavy hitter / recent_global / random");
+  static_assert(QB == 0 || (QB == 8 && !L2), "fused quantised cache: 8 bits, heavy hitter (W = 1 or the ring) / recent_global / random / hybrid");
   static_assert(NSUB == 1 || (NSUB == 2 && !ONE), "two tiles per iteration: the two-launch streaming pass only");
-  static_assert(NT == 1 || (ONE && !L2 && QB == 0 && NSUB == 1), "several tiles per wave in the single-launch step: 16-bit caches, heavy hitter / head-constant policies");
+  static_assert(NT == 1 || (ONE && !L2 && (QB == 0 || HYB) && NSUB == 1),
+                "several tiles per wave in the single-launch step: heavy hitter / head-constant policies (16-bit), hybrid (16-bit or uint8)");
   constexpr bool ONE1 = ONE && NT == 1;  // the single-tile form: no loop tail, no rescale, per-slot state requested ahead of the tile
   // EML (r3): the workgroup's (m, l) pairs leave EARLY — right behind the scores, while the V rows are still in flight — so that
   // the final (M, L) of the head, the probabilities, the history update and the next-eviction keys run in the shadow of the
@@ -2177,8 +2179,14 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
         }
       if (HYB && blockIdx.z == 0) {  // ref: cache.py:997-1016 — bookkeeping of the hybrid decision
         const size_t slot = (size_t)h * S + ins_idx;
-        *reinterpret_cast<uint4*>(const_cast<T*>(kb) + (size_t)ins_idx * D + kcol) = kn.raw;
-        *reinterpret_cast<uint4*>(const_cast<T*>(vh) + (size_t)ins_idx * D) = vn.raw;
+        if constexpr (QB) {  // the image and row parameters of the token, whatever the head does with it (a dropped token: slot S - 1)
+          *reinterpret_cast<uint2*>(const_cast<uint8_t*>(kqb) + (size_t)ins_idx * D + c * VEC) = knq;
+          *reinterpret_cast<uint2*>(const_cast<uint8_t*>(vqh) + (size_t)ins_idx * D) = vnq;
+          if (c == 0) *reinterpret_cast<float4*>(a.qparams + slot * 4) = make_float4(knp.x, knp.y, vnp.x, vnp.y);
+        } else {
+          *reinterpret_cast<uint4*>(const_cast<T*>(kb) + (size_t)ins_idx * D + kcol) = kn.raw;
+          *reinterpret_cast<uint4*>(const_cast<T*>(vh) + (size_t)ins_idx * D) = vn.raw;
+        }
         if (c == 0) {
           a.pos[slot] = p_now;  // :1006-1007 every head, dropped tokens included
           if (hyb_kind == 0) a.mask_w[slot] = 1;  // :997-1001 appends only (an evicted slot is live already)

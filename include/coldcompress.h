@@ -465,7 +465,9 @@ int cc_kv_dequant(const void* q, const void* scales, const void* zeros, void* wo
  *     unquantised new token once and to its round trip afterwards);
  *   - the decode kernels stream the uint8 images (half the bytes of a 16-bit cache) and dequantise in registers on the way
  *     to the matrix cores; everything else of the step (scores -> dtype, softmax, P.V, history, next-eviction key) is the
- *     fused step of cc_decode_step_heavy_hitter / _recent_global / _random applied to the dequantised values.
+ *     fused step of cc_decode_step_heavy_hitter / _heavy_hitter_ring / _recent_global / _random / _hybrid applied to the
+ *     dequantised values.  Only K and V become images: history ring, denominators, counters, window sums, positions, mask
+ *     and the hybrid cache's counts and punctuation / special masks are the 16-bit caches' own.
  * qparams: float32 [H, S, 4] = (k_scale, k_min, v_scale, v_min) per (head, slot).  n_bit: 8 (others: CC_ERR_UNSUPPORTED).
  * cc_kv_quant_rows / cc_kv_dequant_rows convert whole caches ([H, S, D] model dtype <-> uint8 images + qparams).
  * cc_decode_step_quant: c->k_cache / c->v_cache are the uint8 IMAGES [H, S, D], c->dtype the MODEL dtype (of q, k_new,
@@ -494,6 +496,28 @@ int cc_decode_step_quant_rc(const cc_kv_view* c, float* qparams, int32_t n_bit, 
                             int32_t recent_window, int32_t HQ, float scale, void* y, void* workspace, size_t workspace_bytes,
                             cc_stream_t stream, int32_t phases);
 int32_t cc_decode_step_quant_single_launch(int32_t HQ, int32_t H, int32_t S, int32_t D, int32_t dtype, int32_t n_bit);
+/* The same images for the two history-ring policies.  Arguments as cc_decode_step_heavy_hitter_ring / cc_decode_step_hybrid_rc, plus
+ * qparams [H, S, 4] and n_bit (8; others: CC_ERR_UNSUPPORTED, before any launch); c->k_cache / c->v_cache are the uint8 images,
+ * c->dtype the model dtype.  16-bit dtype, D == 128, HQ / H in {4, 8} (CC_ERR_UNSUPPORTED otherwise).
+ * cc_decode_step_heavy_hitter_ring_quant (history_window_size W > 1): two launches, as in 16 bits — the streaming pass reads the
+ *   images and quantises the inserted token's rows ahead of its tile, the combine pass updates the ring, the window sums and the
+ *   next-eviction keys.  Seed next_key with cc_hh_ring_next_key_init (it never reads K / V).
+ * cc_decode_step_hybrid_quant_rc: the hybrid step (decision, ring column, counts, punctuation, commit words unchanged); only the
+ *   K / V source and the insert differ.  One launch where cc_decode_step_hybrid_quant_single_launch says so (up to eight 64-slot tiles
+ *   per wave, as the 16-bit hybrid step), two otherwise.  Seed next_key with cc_hybrid_next_key_init. */
+int cc_decode_step_heavy_hitter_ring_quant(const cc_kv_view* c, float* qparams, int32_t n_bit, const void* q, const void* k_new,
+                                           const void* v_new, const int32_t* input_pos, void* ring_num, int32_t* denom, int64_t* counter,
+                                           int32_t W, uint64_t* wsum_acc, float* wsum, uint64_t* next_key, int32_t global_tokens,
+                                           int32_t recent_window, int32_t HQ, float scale, void* y, void* attn_out, void* workspace,
+                                           size_t workspace_bytes, cc_stream_t stream);
+int cc_decode_step_hybrid_quant_rc(const cc_kv_view* c, float* qparams, int32_t n_bit, const void* q, const void* k_new,
+                                   const void* v_new, const int32_t* input_pos, const int64_t* strategies, const int32_t* policy_table,
+                                   int32_t n_policies, void* ring_num, int32_t* denom, int64_t* counter, int32_t W, uint64_t* wsum_acc,
+                                   float* wsum, const uint8_t* special_mask, uint8_t* punc_mask, const int64_t* token_id,
+                                   const int64_t* punc_ids, int32_t n_punc_ids, const int32_t* num_special, int32_t* num_punc,
+                                   uint64_t* next_key, int32_t* step_commit, int32_t global_tokens, int32_t HQ, float scale, void* y,
+                                   void* attn_out, void* workspace, size_t workspace_bytes, cc_stream_t stream);
+int32_t cc_decode_step_hybrid_quant_single_launch(int32_t HQ, int32_t H, int32_t S, int32_t D, int32_t dtype, int32_t n_bit);
 /* ... and for the l2 step (cc_decode_step_l2[_rc]); cc_decode_step_single_launch_enabled: 1 while the process-wide switch
  * (cc_decode_step_set_single_launch, include/coldcompress_debug.h) AND the current device's own (cc_decode_step_device_single_launch,
  * below) allow the single-launch forms at all.  Together with the

@@ -130,6 +130,18 @@ def main():
                 for kv in caches:
                     kv.prepare_decode(pos)
                 res["fused_step_us"] = round(timed(lambda i: caches[i % n_buf].decode_step(q, k1, k1, pos, input_ids=ids), n_buf, after=lambda: pos.add_(1)), 2)
+                res["fused_one_launch"] = caches[0].single_launch_active(HQ)
+                # the hybrid step over uint8 images (cache_quant_mode="fused")
+                del caches
+                torch.cuda.empty_cache()
+                caches = [make(strategy, H, S, D, {"cache_bits": 8, "cache_quant_mode": "fused"}) for _ in range(n_buf)]
+                for kv in caches:
+                    kv.prepare_decode(pos)
+                for i in range(n_buf):
+                    caches[i].decode_step(q, k1, k1, pos, input_ids=ids)
+                res["fused_quant8_step_us"] = round(timed(lambda i: caches[i % n_buf].decode_step(q, k1, k1, pos, input_ids=ids), n_buf,
+                                                          after=lambda: pos.add_(1)), 2)
+                res["fused_quant8_one_launch"] = caches[0].single_launch_active(HQ)
             b = 2 * H * S * D * 2
             res["kv_MB"] = round(b / 1e6, 1)
             best = res.get("fused_step_us", res["three_call_us"])
@@ -137,6 +149,26 @@ def main():
             print(json.dumps(res), flush=True)
             del caches
             torch.cuda.empty_cache()
+        # heavy hitter with a finite history window (the two-launch ring step): 16-bit and over uint8 images
+        for W in ((8, 400) if tag in ("C2", "C3") else ()):
+            strategy = f"heavy_hitter_w{W}"
+            if only and only != f"{tag}:{strategy}":
+                continue
+            res = {"cfg": tag, "strategy": strategy, "H": H, "HQ": HQ, "S": S, "W": W}
+            q = torch.randn(1, HQ, 1, D, device=dev).to(torch.bfloat16)
+            k1 = torch.randn(1, H, 1, D, device=dev).to(torch.bfloat16)
+            pos = torch.tensor([S + 100], dtype=torch.int32, device=dev)
+            n_w = max(4, min(n_buf, (900 << 20) // (H * S * (W * 2 + 2 * D * 2)) + 1))
+            for key, extra in (("fused_step_us", {}), ("fused_quant8_step_us", {"cache_bits": 8, "cache_quant_mode": "fused"})):
+                caches = [make("heavy_hitter", H, S, D, dict(extra, history_window_size=W)) for _ in range(n_w)]
+                for kv in caches:
+                    kv.prepare_decode(pos)
+                for i in range(n_w):
+                    caches[i].decode_step(q, k1, k1, pos)
+                res[key] = round(timed(lambda i: caches[i % n_w].decode_step(q, k1, k1, pos), n_w, after=lambda: pos.add_(1)), 2)
+                del caches
+                torch.cuda.empty_cache()
+            print(json.dumps(res), flush=True)
 
 
 if __name__ == "__main__":

@@ -89,6 +89,8 @@ def main():
         ("C3 random 4096", dict(cache_strategy=["random"], prompt_compression_strategy=["random"]), 8192),
         ("recent_global 4096", dict(cache_strategy=["recent_global"], prompt_compression_strategy=["recent_global"]), 8192),
         ("C4 hybrid 1.0", dict(cache_strategy=["hybrid"], prompt_compression_strategy=["full"], max_cache_length=[1.0]), 16384),
+        ("C4 hybrid 1.0 cache_bits=8 fused", dict(cache_strategy=["hybrid"], prompt_compression_strategy=["full"], max_cache_length=[1.0],
+                                                 cache_bits=8, cache_quant_mode="fused"), 16384),
         ("C4 heavy_hitter pyramid 1024", dict(max_cache_length=[1024.0], cache_length_pattern="pyramid"), 16384),
         ("heavy_hitter 4096 cache_bits=8", dict(cache_bits=8), 8192),
         ("heavy_hitter 4096 cache_bits=8 fused", dict(cache_bits=8, cache_quant_mode="fused"), 8192),
