@@ -29,8 +29,9 @@ STRATEGIES = ["full", "random", "recent_global", "heavy_hitter", "l2", "hybrid",
 def add_extension_arguments(parser: argparse.ArgumentParser):
     """Flags the reference does not have (kept out of add_cache_arguments so that its flag set stays the reference's).
     --cache_quant_mode fused: with --cache_bits 8, uint8 images on a per-(head, slot) grid, dequantised inside the decode
-    kernels — a different numerical contract (include/coldcompress.h); "reference" = cache.py:283-338 bit for bit."""
-    parser.add_argument("--cache_quant_mode", default="reference", choices=["reference", "fused"])
+    kernels — a different numerical contract (include/coldcompress.h); fp8: the same caches with OCP e4m3 images and one
+    power-of-two scale per (head, slot) row; "reference" = cache.py:283-338 bit for bit."""
+    parser.add_argument("--cache_quant_mode", default="reference", choices=["reference", "fused", "fp8"])
 
 
 def add_cache_arguments(parser: argparse.ArgumentParser):
@@ -119,15 +120,18 @@ class KVCache(nn.Module):
         self.n_bit = self.cache_bits
         self.quantization_axis = 2
         # opt-in fused quantised cache (our extension, include/coldcompress.h): the decode kernels stream uint8 images
+        # ("fused") or FP8 e4m3 images ("fp8"); quant_format is the image format the C ABI takes in its n_bit argument
         mode = getattr(self, "cache_quant_mode", None) or "reference"
-        if mode not in ("reference", "fused"):
-            raise ColdCompressError(f"cache_quant_mode={mode!r}: 'reference' or 'fused'")
-        self.fused_quant = self.quantize and mode == "fused"
+        if mode not in ("reference", "fused", "fp8"):
+            raise ColdCompressError(f"cache_quant_mode={mode!r}: 'reference', 'fused' or 'fp8'")
+        self.fused_quant = self.quantize and mode in ("fused", "fp8")
+        self.quant_format = (_abi.CC_QUANT_FP8_E4M3 if mode == "fp8" else 8) if self.fused_quant else None
+        self._fused_mode = mode if self.fused_quant else None  # (for messages)
         if self.fused_quant:
             if self.n_bit != 8 or dtype not in (torch.bfloat16, torch.float16) or head_dim != 128:
-                raise ColdCompressError("cache_quant_mode='fused' serves cache_bits=8, 16-bit models, head_dim 128")
+                raise ColdCompressError(f"cache_quant_mode={mode!r} serves cache_bits=8, 16-bit models, head_dim 128")
             if not self._fused_quant_policy():
-                raise ColdCompressError(f"cache_quant_mode='fused' is not available for {type(self).__name__}: it serves "
+                raise ColdCompressError(f"cache_quant_mode={mode!r} is not available for {type(self).__name__}: it serves "
                                         "heavy_hitter (any history_window_size), recent_global, full, random and hybrid")
             self.quantize = False  # none of the reference mode's round-trip machinery runs
         self.n_heads = n_heads
@@ -142,7 +146,8 @@ class KVCache(nn.Module):
             self.register_buffer("v_cache", torch.zeros((1, n_heads, 0, head_dim), dtype=dtype))
             self.register_buffer("k_cache_q", torch.zeros(self.cache_shape, dtype=torch.uint8))
             self.register_buffer("v_cache_q", torch.zeros(self.cache_shape, dtype=torch.uint8))
-            self.register_buffer("kv_qparams", torch.zeros((1, n_heads, S, 4), dtype=torch.float32))  # k_scale, k_min, v_scale, v_min
+            # uint8: (k_scale, k_min, v_scale, v_min); FP8: (2^e_k, 0, 2^e_v, 0)
+            self.register_buffer("kv_qparams", torch.zeros((1, n_heads, S, 4), dtype=torch.float32))
         else:
             self.register_buffer("k_cache", torch.zeros(self.cache_shape, dtype=dtype))
             self.register_buffer("v_cache", torch.zeros(self.cache_shape, dtype=dtype))
@@ -204,13 +209,13 @@ class KVCache(nn.Module):
         k = torch.empty(self.cache_shape, dtype=self.k_cache.dtype, device=self.k_cache_q.device)
         v = torch.empty_like(k)
         _abi.call("cc_kv_dequant_rows", _ptr(self.k_cache_q), _ptr(self.v_cache_q), _ptr(self.kv_qparams), H, S, D,
-                  _DT[self.k_cache.dtype], 8, _ptr(k), _ptr(v), _stream())
+                  _DT[self.k_cache.dtype], self.quant_format, _ptr(k), _ptr(v), _stream())
         return k, v
 
     def _quant_step(self, q, k, v, p32, HQ, scale, y, ws, num=None, denom=None, counter=None, rand=None, seed=0, g=0, w=0, phases=3):
         """The fused step over the uint8 images, recoverable form (cc_decode_step_quant_rc: commit words; random: `rand` = the
         injected vector, or None -> in-kernel draws from `seed`)."""
-        _abi.call("cc_decode_step_quant_rc", self._view(), _ptr(self.kv_qparams), 8, self._fused_quant_policy(), _ptr(q), _ptr(k),
+        _abi.call("cc_decode_step_quant_rc", self._view(), _ptr(self.kv_qparams), self.quant_format, self._fused_quant_policy(), _ptr(q), _ptr(k),
                   _ptr(v), _ptr(p32), _ptr(num), _ptr(denom), _ptr(counter), _ptr(rand), int(seed), _ptr(self.next_key),
                   _ptr(self.step_commit), int(g), int(w), HQ, scale, _ptr(y), _ptr(ws), ws.numel(), _stream(), phases)
 
@@ -334,7 +339,7 @@ class KVCache(nn.Module):
             tmp = KVView(ks.data_ptr(), vs.data_ptr(), self.pos.data_ptr(), self.mask.data_ptr(), self.cache_cts.data_ptr(), H,
                          self.pos.shape[1], self.cache_cts.shape[0], S, D, _DT[self.k_cache.dtype])
             _abi.call("cc_prefill_fill", C.byref(tmp), _ptr(k), _ptr(v), _ptr(p), p.shape[0], T, _stream())
-            _abi.call("cc_kv_quant_rows", _ptr(ks), _ptr(vs), H, S, D, _DT[self.k_cache.dtype], 8, _ptr(self.k_cache_q),
+            _abi.call("cc_kv_quant_rows", _ptr(ks), _ptr(vs), H, S, D, _DT[self.k_cache.dtype], self.quant_format, _ptr(self.k_cache_q),
                       _ptr(self.v_cache_q), _ptr(self.kv_qparams), _stream())
             return
         _abi.call("cc_prefill_fill", self._view(), _ptr(k), _ptr(v), _ptr(p), p.shape[0], T, _stream())
@@ -344,7 +349,7 @@ class KVCache(nn.Module):
     def _decoding_update(self, input_pos, k_val, v_val, **kwargs):
         """ref: cache.py:348-364: generic path = `_token_importances` -> base rules -> arg-min -> insert."""
         if self.fused_quant:
-            raise ColdCompressError("cache_quant_mode='fused': decode through decode_step() — the three-call path would have to "
+            raise ColdCompressError(f"cache_quant_mode={self._fused_mode!r}: decode through decode_step() — the three-call path would have to "
                                     "materialise the dequantised cache every step, which is what this mode exists to avoid")
         k, v = self._new_rows(k_val, v_val)
         self._run_select(input_pos, k, v)
@@ -442,10 +447,10 @@ def step_is_recoverable(cache, HQ, attention=None):
     with torch.cuda.device(cache.k_cache.device):  # (residency and the dispatch-order verdict are facts of THAT device)
         if isinstance(cache, KVCacheHybrid):  # (isinstance: a subclass takes its parent's step)
             if cache.fused_quant:
-                return bool(lib["cc_decode_step_hybrid_quant_single_launch"](*args, 8))
+                return bool(lib["cc_decode_step_hybrid_quant_single_launch"](*args, cache.quant_format))
             return bool(lib["cc_decode_step_hybrid_single_launch"](*args))
         if cache.fused_quant:
-            return bool(lib["cc_decode_step_quant_single_launch"](*args, 8))
+            return bool(lib["cc_decode_step_quant_single_launch"](*args, cache.quant_format))
         if isinstance(cache, KVCacheL2):
             return bool(lib["cc_decode_step_l2_single_launch"](*args))
         return bool(lib["cc_decode_step_single_launch"](*args))
@@ -885,7 +890,7 @@ class KVCacheHeavyHitter(_TrackedWindowSums, KVCacheHeadSpecific):
         ws = _workspace(nbytes, query.device)
         if self.history_window_size != 1 and self.fused_quant:  # the ring step over the uint8 images (two launches, as in 16 bits)
             wsum, acc = self._window_state()
-            _abi.call("cc_decode_step_heavy_hitter_ring_quant", self._view(), _ptr(self.kv_qparams), 8, _ptr(q), _ptr(k), _ptr(v), _ptr(p32),
+            _abi.call("cc_decode_step_heavy_hitter_ring_quant", self._view(), _ptr(self.kv_qparams), self.quant_format, _ptr(q), _ptr(k), _ptr(v), _ptr(p32),
                       _ptr(self.attn_history_num), _ptr(self.attn_history_denom), _ptr(self.attn_counter), int(self.history_window_size),
                       _ptr(acc), _ptr(wsum), _ptr(self.next_key), int(self.global_tokens), int(self.recent_window), HQ,
                       1.0 / math.sqrt(D) if scale is None else scale, _ptr(y), None, _ptr(ws), ws.numel(), _stream())
@@ -928,7 +933,7 @@ class KVCacheHeavyHitter(_TrackedWindowSums, KVCacheHeadSpecific):
             if self.history_window_size != 1:  # the ring step has no single-launch form
                 return False
             return bool(self.single_launch and _abi.lib()["cc_decode_step_quant_single_launch"](
-                HQ, self.n_heads, self.max_cache_length, self.head_dim, _DT[self.k_cache.dtype], 8))
+                HQ, self.n_heads, self.max_cache_length, self.head_dim, _DT[self.k_cache.dtype], self.quant_format))
         return bool(self.single_launch and self.history_window_size == 1 and _abi.lib()["cc_decode_step_single_launch"](
             HQ, self.n_heads, self.max_cache_length, self.head_dim, _DT[self.k_cache.dtype]))
 
@@ -1031,7 +1036,7 @@ class KVCacheHybrid(_TrackedWindowSums, KVCacheHeadSpecific):
                 "dtypes match'), so there is no behaviour to reproduce or pin")
         if self.fused_quant and not self._fused_shape_ok():
             # (the 16-bit dtype and head_dim 128 are KVCache's checks; profiled heads are known at prefill, checked there)
-            raise ColdCompressError("cache_quant_mode='fused' for hybrid needs the fused decode step: at most 48 kv heads, at most 21 "
+            raise ColdCompressError(f"cache_quant_mode={self._fused_mode!r} for hybrid needs the fused decode step: at most 48 kv heads, at most 21 "
                                     "policies and reset_history_on_evict = False")
         S, W = self.max_cache_length, self.history_window_size
         self.register_buffer("attn_history_num", torch.zeros((1, n_heads, S, W), dtype=dtype))
@@ -1140,7 +1145,7 @@ class KVCacheHybrid(_TrackedWindowSums, KVCacheHeadSpecific):
         if not lib["cc_decode_step_single_launch_enabled"]():
             return False
         if self.fused_quant:
-            return bool(lib["cc_decode_step_hybrid_quant_single_launch"](*args, 8))
+            return bool(lib["cc_decode_step_hybrid_quant_single_launch"](*args, self.quant_format))
         return bool(lib["cc_decode_step_hybrid_single_launch"](*args))
 
     def step_status(self, HQ=None):
@@ -1219,9 +1224,9 @@ class KVCacheHybrid(_TrackedWindowSums, KVCacheHeadSpecific):
             ring, denom, counter = self.attn_history_num, self.attn_history_denom, self.attn_counter
         if self.fused_quant:  # the same step over the uint8 images: the insert writes the token's image and row parameters
             if not self.supports_fused_step():
-                raise ColdCompressError("cache_quant_mode='fused': the hybrid cache has no fused decode step for this state "
+                raise ColdCompressError(f"cache_quant_mode={self._fused_mode!r}: the hybrid cache has no fused decode step for this state "
                                         "(see supports_fused_step)")
-            _abi.call("cc_decode_step_hybrid_quant_rc", self._view(), _ptr(self.kv_qparams), 8, _ptr(q), _ptr(k), _ptr(v), _ptr(p32),
+            _abi.call("cc_decode_step_hybrid_quant_rc", self._view(), _ptr(self.kv_qparams), self.quant_format, _ptr(q), _ptr(k), _ptr(v), _ptr(p32),
                       _ptr(self.cache_strategies), _ptr(tab), tab.shape[0], _ptr(ring), _ptr(denom), _ptr(counter),
                       self.history_window_size, _ptr(acc), _ptr(wsum), _ptr(getattr(self, "special_mask", None)),
                       _ptr(getattr(self, "punc_mask", None)), _ptr(tok), _ptr(pids), 0 if pids is None else pids.numel(),
@@ -1242,7 +1247,7 @@ class KVCacheHybrid(_TrackedWindowSums, KVCacheHeadSpecific):
         if self.cache_strategies is None:
             raise ColdCompressError("hybrid cache used before prefill profiling (update_state with is_prefill=True)")
         if self.fused_quant:
-            raise ColdCompressError("cache_quant_mode='fused': decode through decode_step() — the three-call path would have to "
+            raise ColdCompressError(f"cache_quant_mode={self._fused_mode!r}: decode through decode_step() — the three-call path would have to "
                                     "materialise the dequantised cache every step, which is what this mode exists to avoid")
         self._next_valid = False  # the three-call path mutates pos / counts / history outside the pipeline
         k, v = self._new_rows(k_val, v_val)
@@ -1392,7 +1397,7 @@ class KVCacheHybrid(_TrackedWindowSums, KVCacheHeadSpecific):
         mask_all = torch.stack([cols | (t >= L - win if win else zeros).unsqueeze(0) for cols, win in filling])  # [n,H,L]
         mask_optimal = mask_all.gather(0, self.cache_strategies.view(1, H, 1).expand(1, H, L)).squeeze(0)
         if self.fused_quant and not self.supports_fused_step():  # (never a three-call path over the images)
-            raise ColdCompressError("cache_quant_mode='fused': the profiled hybrid cache has no fused decode step (see supports_fused_step)")
+            raise ColdCompressError(f"cache_quant_mode={self._fused_mode!r}: the profiled hybrid cache has no fused decode step (see supports_fused_step)")
         chosen = [self.hybrid_strategies[i]["strategy"] for i in self.cache_strategies.tolist()]
         self.requires_heavy_hitter = any("heavy_hitter" in n for n in chosen)
         self.requires_punc = any("punc" in n for n in chosen)
@@ -1422,7 +1427,7 @@ class KVCacheHybrid(_TrackedWindowSums, KVCacheHeadSpecific):
         kw_.masked_fill_(~live.unsqueeze(-1), 0)
         vw_.masked_fill_(~live.unsqueeze(-1), 0)
         if self.fused_quant:
-            _abi.call("cc_kv_quant_rows", _ptr(kw_), _ptr(vw_), H, S, D, _DT[self.k_cache.dtype], 8, _ptr(self.k_cache_q),
+            _abi.call("cc_kv_quant_rows", _ptr(kw_), _ptr(vw_), H, S, D, _DT[self.k_cache.dtype], self.quant_format, _ptr(self.k_cache_q),
                       _ptr(self.v_cache_q), _ptr(self.kv_qparams), _stream())
         self.mask[0, :, 0, :] = live & (torch.arange(S, device=dev).view(1, S) < L)
         if hasattr(self, "special_mask"):

@@ -346,9 +346,9 @@ struct SplitArgs {
   //      committed for kv head h (-1 = none; null = the caller does not retry).  See "Recoverable hand-off" below.
   int32_t* commit;
   HybridStep hyb;     // HYB instantiation only
-  // ---- fused quantised cache (QB instantiation): k / v point at the uint8 images [H, S, D]; one (scale, minimum) pair per
-  //      (head, slot) row for K and one for V — dequantised in registers on the way to the LDS slabs
-  float* qparams;     // [H, S, 4]: k_scale, k_min, v_scale, v_min
+  // ---- fused quantised cache (QB instantiation): k / v point at the uint8 (QB = 8) or FP8 (kQbFp8) images [H, S, D]; one parameter
+  //      pair per (head, slot) row for K and one for V — dequantised in registers on the way to the LDS slabs
+  float* qparams;     // [H, S, 4]: k_scale, k_min, v_scale, v_min (FP8: 2^e_k, 0, 2^e_v, 0)
   QkvIn qkv;          // QKV instantiations only: q / k_new / v_new are null, the step computes them itself
   int virt8;          // XL2 instantiations (r6, CC_V_FEWXCD): the grid has 8 virtual kv heads, blocks of heads >= H exit (travels in the preloaded word)
 };
@@ -808,6 +808,47 @@ __device__ __forceinline__ uint2 quant8_row16(uint4 raw, float2& par) {
   return make_uint2(b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24), b[4] | (b[5] << 8) | (b[6] << 16) | (b[7] << 24));
 }
 
+// ---- the FP8 (OCP e4m3fn) images (QB = kQbFp8, include/coldcompress.h): par = (2^e, 0); 4 x v_cvt_scalef32_pk_{bf16,f16}_fp8 per
+// 8 values (the hardware applies the scale: one rounding of the exact product, bit for bit the contract's value — all 256 codes at
+// e = -120, -40 .. 40 and 120 in tests/test_gpu_kv_fp8.py)
+constexpr int kQbFp8 = CC_QUANT_FP8_E4M3;
+template <typename T>
+__device__ __forceinline__ uint4 dequant_fp8(uint2 raw, float2 par) {
+  return make_uint4(cc_fp8_dequant2<T>(raw.x, par.x, false), cc_fp8_dequant2<T>(raw.x, par.x, true),
+                    cc_fp8_dequant2<T>(raw.y, par.x, false), cc_fp8_dequant2<T>(raw.y, par.x, true));
+}
+// FP8 codes of the 8 values of this lane, on the power-of-two scale of its 16-lane row group (one cache row of 128 values):
+// amax over the row's finite values, e = cc_fp8_row_exp(amax), codes of x * 2^-e (exact) by v_cvt_pk_fp8_f32
+template <typename T>
+__device__ __forceinline__ uint2 quant_fp8_row16(uint4 raw, float2& par) {
+  Vec16<T> v;
+  v.raw = raw;
+  float x[8];
+  v.unpack(x);
+  float am = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; i++) am = fmaxf(am, cc_fp8_abs_finite(x[i]));
+#pragma unroll
+  for (int off = 8; off > 0; off >>= 1) am = fmaxf(am, __shfl_xor(am, off, 16));
+  const int e = cc_fp8_row_exp(am);
+  const float inv = __builtin_ldexpf(1.f, -e);
+#pragma unroll
+  for (int i = 0; i < 8; i++) x[i] = __fmul_rn(x[i], inv);
+  par = make_float2(__builtin_ldexpf(1.f, e), 0.f);
+  return make_uint2(cc_fp8_pack4(x[0], x[1], x[2], x[3]), cc_fp8_pack4(x[4], x[5], x[6], x[7]));
+}
+// the image format QB's two operations (QB = 8: the uint8 grid; kQbFp8: FP8)
+template <typename T, int QB>
+__device__ __forceinline__ uint4 dequant_qb(uint2 raw, float2 par) {
+  if constexpr (QB == kQbFp8) return dequant_fp8<T>(raw, par);
+  else return dequant8<T>(raw, par);
+}
+template <typename T, int QB>
+__device__ __forceinline__ uint2 quant_qb_row16(uint4 raw, float2& par) {
+  if constexpr (QB == kQbFp8) return quant_fp8_row16<T>(raw, par);
+  else return quant8_row16<T>(raw, par);
+}
+
 template <int V>
 struct IntC {
   static constexpr int value = V;
@@ -817,7 +858,8 @@ struct IntC {
 // step (heavy hitter, recent_global / full, random; with L2: l2; with HYB: the FastGen hybrid cache) — needs R == RT, at most
 // 64 workgroups per kv head, every workgroup of the grid co-resident.  HYB: the per-head decision of KVCacheHybrid at the top of
 // the pass (two-launch form: candidates, ring and counts follow in the combine pass; with ONE: in the tail, on all lanes).
-// QB = 8: the fused quantised cache (uint8 images + per-row (scale, minimum)), dequantised on the way to the LDS slabs; with HYB the
+// QB = 8: the fused quantised cache (uint8 images + per-row (scale, minimum)), dequantised on the way to the LDS slabs; QB = kQbFp8:
+// the same with FP8 images and a power-of-two scale per row (dequant_qb / quant_qb_row16 are the only differences); with HYB the
 // hybrid cache's decision and bookkeeping are unchanged, only its insert writes the token's image and row parameters.
 // NSUB = 2 (multi-tile splits only): two tiles per wave and iteration, each with its own staging registers — the loads of a
 // tile go out two half-iterations ahead of their use instead of one (twice the bytes in flight per wave).
@@ -916,7 +958,8 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
   auto apply_lead = [&]() {};
 #endif
   static_assert(!(HYB && L2), "the hybrid decision rides the plain streaming pass or the single-launch step");
-  static_assert(QB == 0 || (QB == 8 && !L2), "fused quantised cache: 8 bits, heavy hitter (W = 1 or the ring) / recent_global / random / hybrid");
+  static_assert(QB == 0 || ((QB == 8 || QB == kQbFp8) && !L2 && !QKV),
+                "fused quantised cache: uint8 or FP8 images, heavy hitter (W = 1 or the ring) / recent_global / random / hybrid");
   static_assert(NSUB == 1 || (NSUB == 2 && !ONE), "two tiles per iteration: the two-launch streaming pass only");
   static_assert(NT == 1 || (ONE && !L2 && (QB == 0 || HYB) && NSUB == 1),
                 "several tiles per wave in the single-launch step: heavy hitter / head-constant policies (16-bit), hybrid (16-bit or uint8)");
@@ -2151,8 +2194,8 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
       uint2 knq = make_uint2(0, 0), vnq = make_uint2(0, 0);
       float2 knp = make_float2(0.f, 0.f), vnp = make_float2(0.f, 0.f);
       if constexpr (QB) {  // by the inserting row group only; its operands were requested ahead of the tile, so this runs while the tile is in flight
-        knq = quant8_row16<T>(qb_kn.raw, knp);
-        vnq = quant8_row16<T>(qb_vn.raw, vnp);
+        knq = quant_qb_row16<T, QB>(qb_kn.raw, knp);
+        vnq = quant_qb_row16<T, QB>(qb_vn.raw, vnp);
         qb_ins_u = um;
       }
       if constexpr (DMA) {
@@ -2249,7 +2292,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
       } else
       if constexpr (QB) {  // slot c of tile row i holds chunk c ^ i; the inserted row's lane holds chunk c -> slot c ^ i
         const int i = 4 * g + u;
-        sm_k[wave][i][u == qb_ins_u ? ((c ^ i) & 15) : c] = dequant8<T>(R.kq8[u], R.kpar[u]);
+        sm_k[wave][i][u == qb_ins_u ? ((c ^ i) & 15) : c] = dequant_qb<T, QB>(R.kq8[u], R.kpar[u]);
       } else {
         sm_k[wave][4 * g + u][c] = R.kk[u].raw;
       }
@@ -2333,7 +2376,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
     if constexpr (!DMA) {
 #pragma unroll
       for (int u = 0; u < U; u++)
-        sm_v[wave][4 * g + u][(c ^ (2 * ((4 * g + u) & 7))) & 15] = QB ? dequant8<T>(R.vq8[u], R.vpar[u]) : R.vv[u].raw;
+        sm_v[wave][4 * g + u][(c ^ (2 * ((4 * g + u) & 7))) & 15] = QB ? dequant_qb<T, QB>(R.vq8[u], R.vpar[u]) : R.vv[u].raw;
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();

@@ -84,6 +84,46 @@ struct ElemTraits<f16_t> {
   __device__ static __forceinline__ float rnd(float v) { return f16_bits_to_f32(f32_to_f16_bits(v)); }
 };
 
+// ------------------------------------------------------------------ FP8 (OCP e4m3fn) fused cache (CC_QUANT_FP8_E4M3)
+// One power-of-two scale 2^e per (head, slot) row: e = the smallest exponent with amax <= 448 * 2^e (amax = m * 2^k, m in [0.5, 1):
+// 448 = 0.875 * 2^9), clamped to [-120, 120]; 0 for an all-zero row.  No division, no saturation: the scaled values never exceed 448.
+__device__ __forceinline__ int cc_fp8_row_exp(float amax) {
+  if (!(amax > 0.f)) return 0;
+  int k;
+  const float m = frexpf(amax, &k);
+  const int e = m <= 0.875f ? k - 9 : k - 8;
+  return e < -120 ? -120 : (e > 120 ? 120 : e);
+}
+// |x| for the row maximum: non-finite values do not count
+__device__ __forceinline__ float cc_fp8_abs_finite(float x) { return __builtin_isfinite(x) ? __builtin_fabsf(x) : 0.f; }
+// e4m3 codes of four values already scaled by 2^-e (v_cvt_pk_fp8_f32: OCP e4m3fn, round to nearest even), byte j = value j; a
+// non-finite value encodes to the e4m3 NaN with its sign (0x7f | sign — the instruction's own NaN does not keep the sign)
+__device__ __forceinline__ uint32_t cc_fp8_pack4(float a, float b, float c, float d) {
+  int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
+  uint32_t r = (uint32_t)w;
+  const float x[4] = {a, b, c, d};
+#pragma unroll
+  for (int j = 0; j < 4; j++)
+    if (!__builtin_isfinite(x[j])) r = (r & ~(0xffu << (8 * j))) | ((0x7fu | (__builtin_signbit(x[j]) ? 0x80u : 0u)) << (8 * j));
+  return r;
+}
+// two e4m3 codes (bytes 2 hi, 2 hi + 1 of w) -> two 16-bit values of T, times 2^e (scale = 2^e exactly): v_cvt_scalef32_pk_{bf16,f16}_fp8.
+// One rounding of the exact product (bf16: exact; f16: inf past 65504, subnormals rounded to nearest even)
+template <typename T>
+__device__ __forceinline__ uint32_t cc_fp8_dequant2(uint32_t w, float scale, bool hi) {
+  static_assert(ElemTraits<T>::code == CC_DT_BF16 || ElemTraits<T>::code == CC_DT_F16, "FP8 images decode to a 16-bit dtype");
+  if constexpr (ElemTraits<T>::code == CC_DT_BF16) {
+    typedef __bf16 cc_bf16x2 __attribute__((ext_vector_type(2)));
+    const cc_bf16x2 r = hi ? __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, scale, true) : __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, scale, false);
+    return __builtin_bit_cast(uint32_t, r);
+  } else {
+    typedef _Float16 cc_f16x2 __attribute__((ext_vector_type(2)));
+    const cc_f16x2 r = hi ? __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, scale, true) : __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, scale, false);
+    return __builtin_bit_cast(uint32_t, r);
+  }
+}
+
 // 16-byte vector of T, unpacked to floats
 template <typename T>
 struct Vec16 {

@@ -429,6 +429,48 @@ __global__ __launch_bounds__(256) void kv_dequant_rows_kernel(const uint8_t* kq,
   }
 }
 
+// The same two conversions for FP8 images (CC_QUANT_FP8_E4M3, include/coldcompress.h): one wave per row, the row's largest
+// finite |x| -> the power-of-two scale 2^e, codes of x * 2^-e (exact) by v_cvt_pk_fp8_f32; qparams = (2^e, 0) per row.  The
+// helpers are the decode kernels' own (cc_common.h), so the images and values are theirs bit for bit.
+template <typename T>
+__global__ __launch_bounds__(256) void kv_quant_rows_fp8_kernel(const T* k, const T* v, uint8_t* kq, uint8_t* vq, float* qparams,
+                                                               size_t rows, int D) {
+  const int lane = threadIdx.x & 63;
+  const size_t wid = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (wid >= 2 * rows) return;
+  const int which = wid >= rows ? 1 : 0;
+  const size_t row = which ? wid - rows : wid;
+  const T* src = (which ? v : k) + row * D;
+  uint8_t* dst = (which ? vq : kq) + row * D;
+  float am = 0.f;
+  for (int e = lane; e < D; e += 64) am = fmaxf(am, cc_fp8_abs_finite(ElemTraits<T>::load(src, e)));
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) am = fmaxf(am, __shfl_xor(am, off, 64));
+  const int ex = cc_fp8_row_exp(am);
+  const float inv = __builtin_ldexpf(1.f, -ex);
+  for (int e = lane; e < D; e += 64) {
+    const float y = __fmul_rn(ElemTraits<T>::load(src, e), inv);
+    dst[e] = (uint8_t)(cc_fp8_pack4(y, y, y, y) & 0xffu);
+  }
+  if (lane == 0) {
+    qparams[row * 4 + 2 * which] = __builtin_ldexpf(1.f, ex);
+    qparams[row * 4 + 2 * which + 1] = 0.f;
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void kv_dequant_rows_fp8_kernel(const uint8_t* kq, const uint8_t* vq, const float* qparams, T* k, T* v,
+                                                                 size_t rows, int D) {
+  const size_t total = 2 * rows * (size_t)D;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int which = i >= rows * D ? 1 : 0;
+    const size_t j = which ? i - rows * D : i;
+    const size_t row = j / D;
+    const uint32_t w = (which ? vq : kq)[j];
+    (which ? v : k)[j].x = (uint16_t)(cc_fp8_dequant2<T>(w, qparams[row * 4 + 2 * which], false) & 0xffffu);
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -437,10 +479,18 @@ int cc_kv_quant_rows(const void* k, const void* v, int32_t H, int32_t S, int32_t
                      uint8_t* v_q, float* qparams, cc_stream_t stream) {
   CC_ENTRY();
   if (!k || !v || !k_q || !v_q || !qparams || H <= 0 || S <= 0 || D <= 0 || !cc_dt_ok(dtype)) return CC_ERR_BAD_ARG;
-  if (n_bit != 8) return CC_ERR_UNSUPPORTED;
+  if (n_bit != 8 && !(n_bit == CC_QUANT_FP8_E4M3 && cc_dt_size(dtype) == 2)) return CC_ERR_UNSUPPORTED;
   const size_t rows = (size_t)H * S;
   const unsigned blocks = (unsigned)((2 * rows + 3) / 4);
   hipStream_t st = (hipStream_t)stream;
+  if (n_bit == CC_QUANT_FP8_E4M3) {
+    if (dtype == CC_DT_BF16)
+      hipLaunchKernelGGL(kv_quant_rows_fp8_kernel<bf16_t>, dim3(blocks), dim3(256), 0, st, (const bf16_t*)k, (const bf16_t*)v, k_q, v_q, qparams, rows, D);
+    else
+      hipLaunchKernelGGL(kv_quant_rows_fp8_kernel<f16_t>, dim3(blocks), dim3(256), 0, st, (const f16_t*)k, (const f16_t*)v, k_q, v_q, qparams, rows, D);
+    CC_LAUNCH_CHECK();
+    return CC_OK;
+  }
   switch (dtype) {
     case CC_DT_F32: hipLaunchKernelGGL(kv_quant_rows_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)k, (const float*)v, k_q, v_q, qparams, rows, D); break;
     case CC_DT_BF16: hipLaunchKernelGGL(kv_quant_rows_kernel<bf16_t>, dim3(blocks), dim3(256), 0, st, (const bf16_t*)k, (const bf16_t*)v, k_q, v_q, qparams, rows, D); break;
@@ -454,11 +504,19 @@ int cc_kv_dequant_rows(const uint8_t* k_q, const uint8_t* v_q, const float* qpar
                        int32_t n_bit, void* k_out, void* v_out, cc_stream_t stream) {
   CC_ENTRY();
   if (!k_q || !v_q || !qparams || !k_out || !v_out || H <= 0 || S <= 0 || D <= 0 || !cc_dt_ok(dtype)) return CC_ERR_BAD_ARG;
-  if (n_bit != 8) return CC_ERR_UNSUPPORTED;
+  if (n_bit != 8 && !(n_bit == CC_QUANT_FP8_E4M3 && cc_dt_size(dtype) == 2)) return CC_ERR_UNSUPPORTED;
   const size_t rows = (size_t)H * S;
   size_t nb = (2 * rows * D + 255) / 256;
   if (nb > 8192) nb = 8192;
   hipStream_t st = (hipStream_t)stream;
+  if (n_bit == CC_QUANT_FP8_E4M3) {
+    if (dtype == CC_DT_BF16)
+      hipLaunchKernelGGL(kv_dequant_rows_fp8_kernel<bf16_t>, dim3((unsigned)nb), dim3(256), 0, st, k_q, v_q, qparams, (bf16_t*)k_out, (bf16_t*)v_out, rows, D);
+    else
+      hipLaunchKernelGGL(kv_dequant_rows_fp8_kernel<f16_t>, dim3((unsigned)nb), dim3(256), 0, st, k_q, v_q, qparams, (f16_t*)k_out, (f16_t*)v_out, rows, D);
+    CC_LAUNCH_CHECK();
+    return CC_OK;
+  }
   switch (dtype) {
     case CC_DT_F32: hipLaunchKernelGGL(kv_dequant_rows_kernel<float>, dim3((unsigned)nb), dim3(256), 0, st, k_q, v_q, qparams, (float*)k_out, (float*)v_out, rows, D); break;
     case CC_DT_BF16: hipLaunchKernelGGL(kv_dequant_rows_kernel<bf16_t>, dim3((unsigned)nb), dim3(256), 0, st, k_q, v_q, qparams, (bf16_t*)k_out, (bf16_t*)v_out, rows, D); break;

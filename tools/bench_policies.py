@@ -58,7 +58,12 @@ def make(strategy, H, S, D, extra=None):
     with torch.device(dev):
         kv = cls(1, H, D, torch.bfloat16, **lk)
     T = S
-    if getattr(kv, "fused_quant", False):  # uint8 images of N(0, 1) rows: 255 steps over [-3.2, 3.2]
+    if getattr(kv, "fused_quant", False) and kv.quant_format != 8:  # FP8 images of N(0, 1) rows, scale 2^0
+        kv.k_cache_q.copy_(torch.randn(kv.cache_shape, device=dev).to(torch.float8_e4m3fn).view(torch.uint8))
+        kv.v_cache_q.copy_(torch.randn(kv.cache_shape, device=dev).to(torch.float8_e4m3fn).view(torch.uint8))
+        kv.kv_qparams[..., 0::2] = 1.0
+        kv.kv_qparams[..., 1::2] = 0.0
+    elif getattr(kv, "fused_quant", False):  # uint8 images of N(0, 1) rows: 255 steps over [-3.2, 3.2]
         kv.k_cache_q.copy_((torch.randn(kv.cache_shape, device=dev) * 40 + 128).clamp_(0, 255).to(torch.uint8))
         kv.v_cache_q.copy_((torch.randn(kv.cache_shape, device=dev) * 40 + 128).clamp_(0, 255).to(torch.uint8))
         kv.kv_qparams[..., 0::2] = 6.4 / 255
@@ -117,31 +122,34 @@ def main():
                     kv.prepare_decode(pos)
                 res["fused_step_us"] = round(timed(lambda i: caches[i % n_buf].decode_step(q, k1, k1, pos), n_buf, after=lambda: pos.add_(1)), 2)
             if strategy in ("heavy_hitter", "recent_global", "full", "random"):
-                # the opt-in fused quantised cache (cache_bits=8, cache_quant_mode="fused"): uint8 images streamed, dequantised in registers
-                del caches
-                torch.cuda.empty_cache()
-                caches = [make(strategy, H, S, D, {"cache_bits": 8, "cache_quant_mode": "fused"}) for _ in range(n_buf)]
-                for kv in caches:
-                    kv.prepare_decode(pos)
-                for i in range(n_buf):
-                    caches[i].decode_step(q, k1, k1, pos)
-                res["fused_quant8_step_us"] = round(timed(lambda i: caches[i % n_buf].decode_step(q, k1, k1, pos), n_buf, after=lambda: pos.add_(1)), 2)
+                # the opt-in fused quantised cache (cache_bits=8, cache_quant_mode="fused" / "fp8"): uint8 or FP8 images streamed,
+                # dequantised in registers
+                for key, mode in (("fused_quant8_step_us", "fused"), ("fused_fp8_step_us", "fp8")):
+                    del caches
+                    torch.cuda.empty_cache()
+                    caches = [make(strategy, H, S, D, {"cache_bits": 8, "cache_quant_mode": mode}) for _ in range(n_buf)]
+                    for kv in caches:
+                        kv.prepare_decode(pos)
+                    for i in range(n_buf):
+                        caches[i].decode_step(q, k1, k1, pos)
+                    res[key] = round(timed(lambda i: caches[i % n_buf].decode_step(q, k1, k1, pos), n_buf, after=lambda: pos.add_(1)), 2)
             if strategy == "hybrid" and caches[0].supports_fused_step():
                 for kv in caches:
                     kv.prepare_decode(pos)
                 res["fused_step_us"] = round(timed(lambda i: caches[i % n_buf].decode_step(q, k1, k1, pos, input_ids=ids), n_buf, after=lambda: pos.add_(1)), 2)
                 res["fused_one_launch"] = caches[0].single_launch_active(HQ)
-                # the hybrid step over uint8 images (cache_quant_mode="fused")
-                del caches
-                torch.cuda.empty_cache()
-                caches = [make(strategy, H, S, D, {"cache_bits": 8, "cache_quant_mode": "fused"}) for _ in range(n_buf)]
-                for kv in caches:
-                    kv.prepare_decode(pos)
-                for i in range(n_buf):
-                    caches[i].decode_step(q, k1, k1, pos, input_ids=ids)
-                res["fused_quant8_step_us"] = round(timed(lambda i: caches[i % n_buf].decode_step(q, k1, k1, pos, input_ids=ids), n_buf,
-                                                          after=lambda: pos.add_(1)), 2)
-                res["fused_quant8_one_launch"] = caches[0].single_launch_active(HQ)
+                # the hybrid step over uint8 images (cache_quant_mode="fused") and over FP8 images ("fp8")
+                for key, mode in (("fused_quant8", "fused"), ("fused_fp8", "fp8")):
+                    del caches
+                    torch.cuda.empty_cache()
+                    caches = [make(strategy, H, S, D, {"cache_bits": 8, "cache_quant_mode": mode}) for _ in range(n_buf)]
+                    for kv in caches:
+                        kv.prepare_decode(pos)
+                    for i in range(n_buf):
+                        caches[i].decode_step(q, k1, k1, pos, input_ids=ids)
+                    res[key + "_step_us"] = round(timed(lambda i: caches[i % n_buf].decode_step(q, k1, k1, pos, input_ids=ids), n_buf,
+                                                        after=lambda: pos.add_(1)), 2)
+                    res[key + "_one_launch"] = caches[0].single_launch_active(HQ)
             b = 2 * H * S * D * 2
             res["kv_MB"] = round(b / 1e6, 1)
             best = res.get("fused_step_us", res["three_call_us"])
@@ -149,7 +157,7 @@ def main():
             print(json.dumps(res), flush=True)
             del caches
             torch.cuda.empty_cache()
-        # heavy hitter with a finite history window (the two-launch ring step): 16-bit and over uint8 images
+        # heavy hitter with a finite history window (the two-launch ring step): 16-bit and over uint8 / FP8 images
         for W in ((8, 400) if tag in ("C2", "C3") else ()):
             strategy = f"heavy_hitter_w{W}"
             if only and only != f"{tag}:{strategy}":
@@ -159,7 +167,8 @@ def main():
             k1 = torch.randn(1, H, 1, D, device=dev).to(torch.bfloat16)
             pos = torch.tensor([S + 100], dtype=torch.int32, device=dev)
             n_w = max(4, min(n_buf, (900 << 20) // (H * S * (W * 2 + 2 * D * 2)) + 1))
-            for key, extra in (("fused_step_us", {}), ("fused_quant8_step_us", {"cache_bits": 8, "cache_quant_mode": "fused"})):
+            for key, extra in (("fused_step_us", {}), ("fused_quant8_step_us", {"cache_bits": 8, "cache_quant_mode": "fused"}),
+                               ("fused_fp8_step_us", {"cache_bits": 8, "cache_quant_mode": "fp8"})):
                 caches = [make("heavy_hitter", H, S, D, dict(extra, history_window_size=W)) for _ in range(n_w)]
                 for kv in caches:
                     kv.prepare_decode(pos)
