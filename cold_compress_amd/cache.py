@@ -30,8 +30,9 @@ def add_extension_arguments(parser: argparse.ArgumentParser):
     """Flags the reference does not have (kept out of add_cache_arguments so that its flag set stays the reference's).
     --cache_quant_mode fused: with --cache_bits 8, uint8 images on a per-(head, slot) grid, dequantised inside the decode
     kernels — a different numerical contract (include/coldcompress.h); fp8: the same caches with OCP e4m3 images and one
-    power-of-two scale per (head, slot) row; "reference" = cache.py:283-338 bit for bit."""
-    parser.add_argument("--cache_quant_mode", default="reference", choices=["reference", "fused", "fp8"])
+    power-of-two scale per (head, slot) row; uint4: with --cache_bits 4, the uint8 grid with 15 steps, two codes per byte;
+    "reference" = cache.py:283-338 bit for bit."""
+    parser.add_argument("--cache_quant_mode", default="reference", choices=["reference", "fused", "fp8", "uint4"])
 
 
 def add_cache_arguments(parser: argparse.ArgumentParser):
@@ -120,16 +121,19 @@ class KVCache(nn.Module):
         self.n_bit = self.cache_bits
         self.quantization_axis = 2
         # opt-in fused quantised cache (our extension, include/coldcompress.h): the decode kernels stream uint8 images
-        # ("fused") or FP8 e4m3 images ("fp8"); quant_format is the image format the C ABI takes in its n_bit argument
+        # ("fused"), FP8 e4m3 images ("fp8") or 4-bit images ("uint4"); quant_format is the image format the C ABI takes in its
+        # n_bit argument
         mode = getattr(self, "cache_quant_mode", None) or "reference"
-        if mode not in ("reference", "fused", "fp8"):
-            raise ColdCompressError(f"cache_quant_mode={mode!r}: 'reference', 'fused' or 'fp8'")
-        self.fused_quant = self.quantize and mode in ("fused", "fp8")
-        self.quant_format = (_abi.CC_QUANT_FP8_E4M3 if mode == "fp8" else 8) if self.fused_quant else None
+        formats = {"fused": (8, 8), "fp8": (8, _abi.CC_QUANT_FP8_E4M3), "uint4": (4, _abi.CC_QUANT_UINT4)}  # mode -> (cache_bits, format)
+        if mode != "reference" and mode not in formats:
+            raise ColdCompressError(f"cache_quant_mode={mode!r}: 'reference', 'fused', 'fp8' or 'uint4'")
+        self.fused_quant = self.quantize and mode in formats
+        self.quant_format = formats[mode][1] if self.fused_quant else None
         self._fused_mode = mode if self.fused_quant else None  # (for messages)
         if self.fused_quant:
-            if self.n_bit != 8 or dtype not in (torch.bfloat16, torch.float16) or head_dim != 128:
-                raise ColdCompressError(f"cache_quant_mode={mode!r} serves cache_bits=8, 16-bit models, head_dim 128")
+            bits = formats[mode][0]
+            if self.n_bit != bits or dtype not in (torch.bfloat16, torch.float16) or head_dim != 128:
+                raise ColdCompressError(f"cache_quant_mode={mode!r} serves cache_bits={bits}, 16-bit models, head_dim 128")
             if not self._fused_quant_policy():
                 raise ColdCompressError(f"cache_quant_mode={mode!r} is not available for {type(self).__name__}: it serves "
                                         "heavy_hitter (any history_window_size), recent_global, full, random and hybrid")
@@ -144,9 +148,11 @@ class KVCache(nn.Module):
             # the images ARE the cache; k_cache / v_cache stay as empty tensors that carry the model dtype
             self.register_buffer("k_cache", torch.zeros((1, n_heads, 0, head_dim), dtype=dtype))
             self.register_buffer("v_cache", torch.zeros((1, n_heads, 0, head_dim), dtype=dtype))
-            self.register_buffer("k_cache_q", torch.zeros(self.cache_shape, dtype=torch.uint8))
-            self.register_buffer("v_cache_q", torch.zeros(self.cache_shape, dtype=torch.uint8))
-            # uint8: (k_scale, k_min, v_scale, v_min); FP8: (2^e_k, 0, 2^e_v, 0)
+            # [1, H, S, D] bytes (4-bit: [1, H, S, D / 2], two codes per byte)
+            qshape = self.cache_shape if self.quant_format != _abi.CC_QUANT_UINT4 else (1, n_heads, S, head_dim // 2)
+            self.register_buffer("k_cache_q", torch.zeros(qshape, dtype=torch.uint8))
+            self.register_buffer("v_cache_q", torch.zeros(qshape, dtype=torch.uint8))
+            # uint8 / 4-bit: (k_scale, k_min, v_scale, v_min); FP8: (2^e_k, 0, 2^e_v, 0)
             self.register_buffer("kv_qparams", torch.zeros((1, n_heads, S, 4), dtype=torch.float32))
         else:
             self.register_buffer("k_cache", torch.zeros(self.cache_shape, dtype=dtype))
@@ -190,7 +196,7 @@ class KVCache(nn.Module):
 
     # ------------------------------------------------------------------ fused quantised cache (our extension)
     def _fused_quant_policy(self):
-        """Policy code of cc_decode_step_quant this class runs under cache_quant_mode='fused' (0: not available)."""
+        """Policy code of cc_decode_step_quant this class runs under the fused quantised modes (0: not available)."""
         return 0
 
     def _fused_scratch(self):
@@ -213,7 +219,7 @@ class KVCache(nn.Module):
         return k, v
 
     def _quant_step(self, q, k, v, p32, HQ, scale, y, ws, num=None, denom=None, counter=None, rand=None, seed=0, g=0, w=0, phases=3):
-        """The fused step over the uint8 images, recoverable form (cc_decode_step_quant_rc: commit words; random: `rand` = the
+        """The fused step over the images (uint8, FP8 or 4-bit), recoverable form (cc_decode_step_quant_rc: commit words; random: `rand` = the
         injected vector, or None -> in-kernel draws from `seed`)."""
         _abi.call("cc_decode_step_quant_rc", self._view(), _ptr(self.kv_qparams), self.quant_format, self._fused_quant_policy(), _ptr(q), _ptr(k),
                   _ptr(v), _ptr(p32), _ptr(num), _ptr(denom), _ptr(counter), _ptr(rand), int(seed), _ptr(self.next_key),
@@ -888,7 +894,7 @@ class KVCacheHeavyHitter(_TrackedWindowSums, KVCacheHeadSpecific):
         code = _DT[self.k_cache.dtype]
         nbytes = _abi.lib()["cc_decode_attn_workspace_bytes"](HQ, self.n_heads, self.max_cache_length, D, code)
         ws = _workspace(nbytes, query.device)
-        if self.history_window_size != 1 and self.fused_quant:  # the ring step over the uint8 images (two launches, as in 16 bits)
+        if self.history_window_size != 1 and self.fused_quant:  # the ring step over the images (two launches, as in 16 bits)
             wsum, acc = self._window_state()
             _abi.call("cc_decode_step_heavy_hitter_ring_quant", self._view(), _ptr(self.kv_qparams), self.quant_format, _ptr(q), _ptr(k), _ptr(v), _ptr(p32),
                       _ptr(self.attn_history_num), _ptr(self.attn_history_denom), _ptr(self.attn_counter), int(self.history_window_size),
@@ -905,7 +911,7 @@ class KVCacheHeavyHitter(_TrackedWindowSums, KVCacheHeadSpecific):
             return y
         # one launch per layer step where the shape and the device allow it (include/coldcompress.h), else two
         phases = 3 if self.single_launch else 3 | _abi.CC_PHASE_TWO_LAUNCH
-        if self.fused_quant:  # the same step over the uint8 images (cc_decode_step_quant)
+        if self.fused_quant:  # the same step over the images (cc_decode_step_quant)
             self._quant_step(q, k, v, p32, HQ, 1.0 / math.sqrt(D) if scale is None else scale, y, ws, num=self.attn_history_num,
                              denom=self.attn_history_denom, counter=self.attn_counter, g=self.global_tokens, w=self.recent_window,
                              phases=phases)
@@ -1222,7 +1228,7 @@ class KVCacheHybrid(_TrackedWindowSums, KVCacheHeadSpecific):
         if self.requires_heavy_hitter:
             wsum, acc = self._window_state()
             ring, denom, counter = self.attn_history_num, self.attn_history_denom, self.attn_counter
-        if self.fused_quant:  # the same step over the uint8 images: the insert writes the token's image and row parameters
+        if self.fused_quant:  # the same step over the images: the insert writes the token's image and row parameters
             if not self.supports_fused_step():
                 raise ColdCompressError(f"cache_quant_mode={self._fused_mode!r}: the hybrid cache has no fused decode step for this state "
                                         "(see supports_fused_step)")

@@ -837,15 +837,65 @@ __device__ __forceinline__ uint2 quant_fp8_row16(uint4 raw, float2& par) {
   par = make_float2(__builtin_ldexpf(1.f, e), 0.f);
   return make_uint2(cc_fp8_pack4(x[0], x[1], x[2], x[3]), cc_fp8_pack4(x[4], x[5], x[6], x[7]));
 }
-// the image format QB's two operations (QB = 8: the uint8 grid; kQbFp8: FP8)
+// ---- the 4-bit images (QB = kQbU4, include/coldcompress.h): the uint8 grid with 15 steps, par = (scale, minimum); a lane's 8 values
+// are ONE word (raw.x; raw.y is 0), nibble i = value i.  The low nibbles are the even values, the high ones the odd values: two
+// masks, then v_cvt_f32_ubyte{0..3} and one FMA per value as in dequant8
+constexpr int kQbU4 = CC_QUANT_UINT4;
+template <typename T>
+__device__ __forceinline__ uint4 dequant4(uint2 raw, float2 par) {
+  const uint32_t w[2] = {raw.x & 0x0f0f0f0fu, (raw.x >> 4) & 0x0f0f0f0fu};  // values 0, 2, 4, 6 / 1, 3, 5, 7
+  float f[8];
+#pragma unroll
+  for (int i = 0; i < 2; i++) {
+    f[i] = __builtin_fmaf((float)(w[i] & 0xffu), par.x, par.y);
+    f[2 + i] = __builtin_fmaf((float)((w[i] >> 8) & 0xffu), par.x, par.y);
+    f[4 + i] = __builtin_fmaf((float)((w[i] >> 16) & 0xffu), par.x, par.y);
+    f[6 + i] = __builtin_fmaf((float)(w[i] >> 24), par.x, par.y);
+  }
+  if constexpr (ElemTraits<T>::code == CC_DT_F16) {  // fp32 first, then f16 (see cc_opaque_f32)
+#pragma unroll
+    for (int i = 0; i < 8; i++) f[i] = cc_opaque_f32(f[i]);
+  }
+  return make_uint4(pack16x2<T>(f[0], f[1]), pack16x2<T>(f[2], f[3]), pack16x2<T>(f[4], f[5]), pack16x2<T>(f[6], f[7]));
+}
+// quant8_row16 on 15 steps: min / max over the row, range = max(max - min, 1e-6), scale = range / 15, q = clamp(rint((x - min) *
+// (15 / range)), 0, 15) (IEEE fp32 ops, no contraction); the lane's 8 codes packed low nibble first into one word
+template <typename T>
+__device__ __forceinline__ uint2 quant4_row16(uint4 raw, float2& par) {
+  Vec16<T> v;
+  v.raw = raw;
+  float x[8];
+  v.unpack(x);
+  float mn = x[0], mx = x[0];
+#pragma unroll
+  for (int i = 1; i < 8; i++) {
+    mn = fminf(mn, x[i]);
+    mx = fmaxf(mx, x[i]);
+  }
+#pragma unroll
+  for (int off = 8; off > 0; off >>= 1) {
+    mn = fminf(mn, __shfl_xor(mn, off, 16));
+    mx = fmaxf(mx, __shfl_xor(mx, off, 16));
+  }
+  const float range = fmaxf(__fsub_rn(mx, mn), 1e-6f);
+  const float sc = __fdiv_rn(range, 15.f), inv = __fdiv_rn(15.f, range);
+  uint32_t w = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) w |= (uint32_t)fminf(fmaxf(rintf(__fmul_rn(__fsub_rn(x[i], mn), inv)), 0.f), 15.f) << (4 * i);
+  par = make_float2(sc, mn);
+  return make_uint2(w, 0u);
+}
+// the image format QB's two operations (QB = 8: the uint8 grid; kQbFp8: FP8; kQbU4: 4-bit)
 template <typename T, int QB>
 __device__ __forceinline__ uint4 dequant_qb(uint2 raw, float2 par) {
   if constexpr (QB == kQbFp8) return dequant_fp8<T>(raw, par);
+  else if constexpr (QB == kQbU4) return dequant4<T>(raw, par);
   else return dequant8<T>(raw, par);
 }
 template <typename T, int QB>
 __device__ __forceinline__ uint2 quant_qb_row16(uint4 raw, float2& par) {
   if constexpr (QB == kQbFp8) return quant_fp8_row16<T>(raw, par);
+  else if constexpr (QB == kQbU4) return quant4_row16<T>(raw, par);
   else return quant8_row16<T>(raw, par);
 }
 
@@ -859,7 +909,8 @@ struct IntC {
 // 64 workgroups per kv head, every workgroup of the grid co-resident.  HYB: the per-head decision of KVCacheHybrid at the top of
 // the pass (two-launch form: candidates, ring and counts follow in the combine pass; with ONE: in the tail, on all lanes).
 // QB = 8: the fused quantised cache (uint8 images + per-row (scale, minimum)), dequantised on the way to the LDS slabs; QB = kQbFp8:
-// the same with FP8 images and a power-of-two scale per row (dequant_qb / quant_qb_row16 are the only differences); with HYB the
+// the same with FP8 images and a power-of-two scale per row; QB = kQbU4: 4-bit images, D / 2 bytes per row (dequant_qb /
+// quant_qb_row16 and the image's byte offsets are the only differences); with HYB the
 // hybrid cache's decision and bookkeeping are unchanged, only its insert writes the token's image and row parameters.
 // NSUB = 2 (multi-tile splits only): two tiles per wave and iteration, each with its own staging registers — the loads of a
 // tile go out two half-iterations ahead of their use instead of one (twice the bytes in flight per wave).
@@ -958,8 +1009,8 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
   auto apply_lead = [&]() {};
 #endif
   static_assert(!(HYB && L2), "the hybrid decision rides the plain streaming pass or the single-launch step");
-  static_assert(QB == 0 || ((QB == 8 || QB == kQbFp8) && !L2 && !QKV),
-                "fused quantised cache: uint8 or FP8 images, heavy hitter (W = 1 or the ring) / recent_global / random / hybrid");
+  static_assert(QB == 0 || ((QB == 8 || QB == kQbFp8 || QB == kQbU4) && !L2 && !QKV),
+                "fused quantised cache: uint8, FP8 or 4-bit images, heavy hitter (W = 1 or the ring) / recent_global / random / hybrid");
   static_assert(NSUB == 1 || (NSUB == 2 && !ONE), "two tiles per iteration: the two-launch streaming pass only");
   static_assert(NT == 1 || (ONE && !L2 && (QB == 0 || HYB) && NSUB == 1),
                 "several tiles per wave in the single-launch step: heavy hitter / head-constant policies (16-bit), hybrid (16-bit or uint8)");
@@ -1109,7 +1160,8 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
   // what hangs on the argument block's later fields (LATE: worked out again behind phase 1)
   int q0 = 0;
   const T* vh = nullptr;
-  const uint8_t *kqb = nullptr, *vqh = nullptr;  // QB: byte images (element offsets are byte offsets) ...
+  const uint8_t *kqb = nullptr, *vqh = nullptr;  // QB: byte images (a row is QRB bytes, a lane's 8-value chunk QCB) ...
+  constexpr int QRB = QB == kQbU4 ? D / 2 : D, QCB = QB == kQbU4 ? VEC / 2 : VEC;
   const float2* qpar = nullptr;                  // ... and the head's row parameters: [slot][0] = K pair, [1] = V pair
   bool has_mask = false;
   const uint8_t* mh = nullptr;
@@ -1117,8 +1169,8 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
   auto derive = [&]() {
     q0 = h * a.R + blockIdx.z * RT;
     vh = reinterpret_cast<const T*>(a.v) + (size_t)h * S * D + c * VEC;
-    kqb = reinterpret_cast<const uint8_t*>(a.k) + (size_t)h * S * D;
-    vqh = reinterpret_cast<const uint8_t*>(a.v) + (size_t)h * S * D + c * VEC;
+    kqb = reinterpret_cast<const uint8_t*>(a.k) + (size_t)h * S * QRB;
+    vqh = reinterpret_cast<const uint8_t*>(a.v) + (size_t)h * S * QRB + c * QCB;
     qpar = reinterpret_cast<const float2*>(a.qparams) + (size_t)h * S * 2;
     has_mask = a.mask != nullptr && !(a.abl & 4);
     mh = has_mask ? a.mask + (size_t)h * S : reinterpret_cast<const uint8_t*>(a.k);
@@ -1157,7 +1209,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
   struct TileRegs {            // the staging registers of one tile in flight
     uint32_t mword;
     Vec16<T> kk[U], vv[U];
-    uint2 kq8[U], vq8[U];      // QB: the rows' bytes ...
+    uint2 kq8[U], vq8[U];      // QB: the rows' bytes (4-bit images: one word, .y = 0) ...
     float2 kpar[U], vpar[U];   // ... and their (scale, minimum)
   };
   TileRegs tregs[NSUB];
@@ -1166,13 +1218,21 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
     const u32x2_nt v = __builtin_nontemporal_load(reinterpret_cast<const u32x2_nt*>(p));
     return make_uint2(v.x, v.y);
   };
+  auto load_nt_qb = [&](const uint8_t* p) {  // QB: the QCB bytes of a lane's chunk
+    if constexpr (QB == kQbU4) return make_uint2(__builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p)), 0u);
+    else return load_nt_u2(p);
+  };
+  auto store_qb = [](uint8_t* p, uint2 w) {  // QB: the insert's image store of a lane's chunk
+    if constexpr (QB == kQbU4) *reinterpret_cast<uint32_t*>(p) = w.x;
+    else *reinterpret_cast<uint2*>(p) = w;
+  };
   auto issue_k_rows = [&](TileRegs& R, int base) {
     const int row0 = base + g * U;
 #pragma unroll
     for (int u = 0; u < U; u++) {
       const int rr = row0 + u < row_end ? row0 + u : row_end - 1;
       if constexpr (QB) {
-        R.kq8[u] = load_nt_u2(kqb + (size_t)rr * D + ((c ^ (4 * g + u)) & 15) * VEC);
+        R.kq8[u] = load_nt_qb(kqb + (size_t)rr * QRB + ((c ^ (4 * g + u)) & 15) * QCB);
         R.kpar[u] = qpar[(size_t)rr * 2];
       } else {
         R.kk[u].load_nt(kb + (size_t)rr * D + ((c ^ (4 * g + u)) & 15) * VEC);
@@ -1326,7 +1386,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
     for (int u = 0; u < U; u++) {
       const int rr = row0 + u < row_end ? row0 + u : row_end - 1;
       if constexpr (QB) {
-        R.vq8[u] = load_nt_u2(vqh + (size_t)rr * D);
+        R.vq8[u] = load_nt_qb(vqh + (size_t)rr * QRB);
         R.vpar[u] = qpar[(size_t)rr * 2 + 1];
       } else {
         R.vv[u].load_nt(vh + (size_t)rr * D);
@@ -2223,8 +2283,8 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
       if (HYB && blockIdx.z == 0) {  // ref: cache.py:997-1016 — bookkeeping of the hybrid decision
         const size_t slot = (size_t)h * S + ins_idx;
         if constexpr (QB) {  // the image and row parameters of the token, whatever the head does with it (a dropped token: slot S - 1)
-          *reinterpret_cast<uint2*>(const_cast<uint8_t*>(kqb) + (size_t)ins_idx * D + c * VEC) = knq;
-          *reinterpret_cast<uint2*>(const_cast<uint8_t*>(vqh) + (size_t)ins_idx * D) = vnq;
+          store_qb(const_cast<uint8_t*>(kqb) + (size_t)ins_idx * QRB + c * QCB, knq);
+          store_qb(const_cast<uint8_t*>(vqh) + (size_t)ins_idx * QRB, vnq);
           if (c == 0) *reinterpret_cast<float4*>(a.qparams + slot * 4) = make_float4(knp.x, knp.y, vnp.x, vnp.y);
         } else {
           *reinterpret_cast<uint4*>(const_cast<T*>(kb) + (size_t)ins_idx * D + kcol) = kn.raw;
@@ -2239,8 +2299,8 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
       } else if (blockIdx.z == 0) {
         const size_t slot = (size_t)h * S + ins_idx;
         if constexpr (QB) {
-          *reinterpret_cast<uint2*>(const_cast<uint8_t*>(kqb) + (size_t)ins_idx * D + c * VEC) = knq;
-          *reinterpret_cast<uint2*>(const_cast<uint8_t*>(vqh) + (size_t)ins_idx * D) = vnq;
+          store_qb(const_cast<uint8_t*>(kqb) + (size_t)ins_idx * QRB + c * QCB, knq);
+          store_qb(const_cast<uint8_t*>(vqh) + (size_t)ins_idx * QRB, vnq);
           if (c == 0) *reinterpret_cast<float4*>(a.qparams + slot * 4) = make_float4(knp.x, knp.y, vnp.x, vnp.y);
         } else {
           *reinterpret_cast<uint4*>(const_cast<T*>(kb) + (size_t)ins_idx * D + kcol) = kn.raw;

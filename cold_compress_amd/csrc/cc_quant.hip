@@ -471,6 +471,58 @@ __global__ __launch_bounds__(256) void kv_dequant_rows_fp8_kernel(const uint8_t*
   }
 }
 
+// The same two conversions for 4-bit images (CC_QUANT_UINT4, include/coldcompress.h): the uint8 grid with 15 steps, row images of
+// D / 2 bytes, byte j = q[2j] | q[2j + 1] << 4.  One wave per row, as above; each lane writes whole bytes (two values).
+template <typename T>
+__global__ __launch_bounds__(256) void kv_quant_rows_u4_kernel(const T* k, const T* v, uint8_t* kq, uint8_t* vq, float* qparams,
+                                                              size_t rows, int D) {
+  const int lane = threadIdx.x & 63;
+  const size_t wid = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (wid >= 2 * rows) return;
+  const int which = wid >= rows ? 1 : 0;
+  const size_t row = which ? wid - rows : wid;
+  const T* src = (which ? v : k) + row * D;
+  uint8_t* dst = (which ? vq : kq) + row * (D / 2);
+  float mn = INFINITY, mx = -INFINITY;
+  for (int e = lane; e < D; e += 64) {
+    const float x = ElemTraits<T>::load(src, e);
+    mn = fminf(mn, x);
+    mx = fmaxf(mx, x);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    mn = fminf(mn, __shfl_xor(mn, off, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+  }
+  const float range = fmaxf(__fsub_rn(mx, mn), 1e-6f);
+  const float sc = __fdiv_rn(range, 15.f), inv = __fdiv_rn(15.f, range);
+  for (int j = lane; j < D / 2; j += 64) {
+    const float x0 = ElemTraits<T>::load(src, 2 * j), x1 = ElemTraits<T>::load(src, 2 * j + 1);
+    const uint32_t q0 = (uint32_t)fminf(fmaxf(rintf(__fmul_rn(__fsub_rn(x0, mn), inv)), 0.f), 15.f);
+    const uint32_t q1 = (uint32_t)fminf(fmaxf(rintf(__fmul_rn(__fsub_rn(x1, mn), inv)), 0.f), 15.f);
+    dst[j] = (uint8_t)(q0 | (q1 << 4));
+  }
+  if (lane == 0) {
+    qparams[row * 4 + 2 * which] = sc;
+    qparams[row * 4 + 2 * which + 1] = mn;
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void kv_dequant_rows_u4_kernel(const uint8_t* kq, const uint8_t* vq, const float* qparams, T* k, T* v,
+                                                                size_t rows, int D) {
+  const size_t total = 2 * rows * (size_t)D;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int which = i >= rows * D ? 1 : 0;
+    const size_t j = which ? i - rows * D : i;
+    const size_t row = j / D;
+    const float sc = qparams[row * 4 + 2 * which], mn = qparams[row * 4 + 2 * which + 1];
+    const uint32_t q = ((which ? vq : kq)[j / 2] >> (4 * (j & 1))) & 15u;  // (D even: element j of the row is nibble j & 1 of byte j / 2)
+    const float x = cc_opaque_f32(__builtin_fmaf((float)q, sc, mn));  // fp32 first, then T
+    ElemTraits<T>::store(which ? v : k, j, x);
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -479,10 +531,19 @@ int cc_kv_quant_rows(const void* k, const void* v, int32_t H, int32_t S, int32_t
                      uint8_t* v_q, float* qparams, cc_stream_t stream) {
   CC_ENTRY();
   if (!k || !v || !k_q || !v_q || !qparams || H <= 0 || S <= 0 || D <= 0 || !cc_dt_ok(dtype)) return CC_ERR_BAD_ARG;
-  if (n_bit != 8 && !(n_bit == CC_QUANT_FP8_E4M3 && cc_dt_size(dtype) == 2)) return CC_ERR_UNSUPPORTED;
+  if (n_bit != 8 && !((n_bit == CC_QUANT_FP8_E4M3 || n_bit == CC_QUANT_UINT4) && cc_dt_size(dtype) == 2)) return CC_ERR_UNSUPPORTED;
+  if (n_bit == CC_QUANT_UINT4 && D % 2) return CC_ERR_BAD_ARG;
   const size_t rows = (size_t)H * S;
   const unsigned blocks = (unsigned)((2 * rows + 3) / 4);
   hipStream_t st = (hipStream_t)stream;
+  if (n_bit == CC_QUANT_UINT4) {
+    if (dtype == CC_DT_BF16)
+      hipLaunchKernelGGL(kv_quant_rows_u4_kernel<bf16_t>, dim3(blocks), dim3(256), 0, st, (const bf16_t*)k, (const bf16_t*)v, k_q, v_q, qparams, rows, D);
+    else
+      hipLaunchKernelGGL(kv_quant_rows_u4_kernel<f16_t>, dim3(blocks), dim3(256), 0, st, (const f16_t*)k, (const f16_t*)v, k_q, v_q, qparams, rows, D);
+    CC_LAUNCH_CHECK();
+    return CC_OK;
+  }
   if (n_bit == CC_QUANT_FP8_E4M3) {
     if (dtype == CC_DT_BF16)
       hipLaunchKernelGGL(kv_quant_rows_fp8_kernel<bf16_t>, dim3(blocks), dim3(256), 0, st, (const bf16_t*)k, (const bf16_t*)v, k_q, v_q, qparams, rows, D);
@@ -504,11 +565,20 @@ int cc_kv_dequant_rows(const uint8_t* k_q, const uint8_t* v_q, const float* qpar
                        int32_t n_bit, void* k_out, void* v_out, cc_stream_t stream) {
   CC_ENTRY();
   if (!k_q || !v_q || !qparams || !k_out || !v_out || H <= 0 || S <= 0 || D <= 0 || !cc_dt_ok(dtype)) return CC_ERR_BAD_ARG;
-  if (n_bit != 8 && !(n_bit == CC_QUANT_FP8_E4M3 && cc_dt_size(dtype) == 2)) return CC_ERR_UNSUPPORTED;
+  if (n_bit != 8 && !((n_bit == CC_QUANT_FP8_E4M3 || n_bit == CC_QUANT_UINT4) && cc_dt_size(dtype) == 2)) return CC_ERR_UNSUPPORTED;
+  if (n_bit == CC_QUANT_UINT4 && D % 2) return CC_ERR_BAD_ARG;
   const size_t rows = (size_t)H * S;
   size_t nb = (2 * rows * D + 255) / 256;
   if (nb > 8192) nb = 8192;
   hipStream_t st = (hipStream_t)stream;
+  if (n_bit == CC_QUANT_UINT4) {
+    if (dtype == CC_DT_BF16)
+      hipLaunchKernelGGL(kv_dequant_rows_u4_kernel<bf16_t>, dim3((unsigned)nb), dim3(256), 0, st, k_q, v_q, qparams, (bf16_t*)k_out, (bf16_t*)v_out, rows, D);
+    else
+      hipLaunchKernelGGL(kv_dequant_rows_u4_kernel<f16_t>, dim3((unsigned)nb), dim3(256), 0, st, k_q, v_q, qparams, (f16_t*)k_out, (f16_t*)v_out, rows, D);
+    CC_LAUNCH_CHECK();
+    return CC_OK;
+  }
   if (n_bit == CC_QUANT_FP8_E4M3) {
     if (dtype == CC_DT_BF16)
       hipLaunchKernelGGL(kv_dequant_rows_fp8_kernel<bf16_t>, dim3((unsigned)nb), dim3(256), 0, st, k_q, v_q, qparams, (bf16_t*)k_out, (bf16_t*)v_out, rows, D);

@@ -453,9 +453,11 @@ int cc_kv_dequant(const void* q, const void* scales, const void* zeros, void* wo
 
 /* Image format of the fused quantised cache's FP8 mode (the n_bit argument below): OCP e4m3fn codes, a power-of-two scale per row. */
 #define CC_QUANT_FP8_E4M3 (0x100 | 8)
+/* Image format of the fused quantised cache's 4-bit mode (the n_bit argument below): the uint8 grid with 15 steps, two codes per byte. */
+#define CC_QUANT_UINT4 (0x200 | 4)
 
 /* ------------------------------------------------------------------------------------------------
- * FUSED quantised KV cache — opt-in (`cache_quant_mode="fused"`, or "fp8" below), a DIFFERENT numerical contract from the reference's
+ * FUSED quantised KV cache — opt-in (`cache_quant_mode="fused"`, or "fp8" / "uint4" below), a DIFFERENT numerical contract from the reference's
  * ("fuse dequant into the attention read instead of whole-cache round trips").
  * The reference (cache.py:283-338, quantization_utils.py:4-45) keeps ONE (scale, zero) per slot shared by all heads and
  * re-quantises the whole cache every step; its numbers are reproduced by cc_kv_requant above.  Here instead:
@@ -472,8 +474,8 @@ int cc_kv_dequant(const void* q, const void* scales, const void* zeros, void* wo
  *     dequantised values.  Only K and V become images: history ring, denominators, counters, window sums, positions, mask
  *     and the hybrid cache's counts and punctuation / special masks are the 16-bit caches' own.
  * qparams: float32 [H, S, 4] = (k_scale, k_min, v_scale, v_min) per (head, slot).
- * n_bit is the image FORMAT: 8 = the uint8 grid above; CC_QUANT_FP8_E4M3 = FP8 images (`cache_quant_mode="fp8"`); 4, 2 and
- * anything else: CC_ERR_UNSUPPORTED, before any launch.
+ * n_bit is the image FORMAT: 8 = the uint8 grid above; CC_QUANT_FP8_E4M3 = FP8 images (`cache_quant_mode="fp8"`);
+ * CC_QUANT_UINT4 = 4-bit images (`cache_quant_mode="uint4"`); 4, 2 and anything else: CC_ERR_UNSUPPORTED, before any launch.
  * FP8 images: one OCP e4m3fn code per value (the `fn` encoding: no infinities, NaN = 0x7f / 0xff; not the `fnuz` one) and one
  * power-of-two scale 2^e per (head, slot) row of K and of V; qparams holds (2^e_k, 0, 2^e_v, 0), so that buffers, loads and
  * workspace sizes are the uint8 format's:
@@ -485,8 +487,15 @@ int cc_kv_dequant(const void* q, const void* scales, const void* zeros, void* wo
  *       value = T(f32(e4m3(q[d])) * 2^e)     (exact in bf16; in f16 one round to nearest even: inf from 65520 up, subnormals rounded)
  *   The kernels decode with v_cvt_scalef32_pk_{bf16,f16}_fp8 (two values per instruction, the scale applied by the hardware) and
  *   encode the inserted token with v_cvt_pk_fp8_f32.  16-bit model dtypes only (the converters return CC_ERR_UNSUPPORTED for fp32).
- * cc_kv_quant_rows / cc_kv_dequant_rows convert whole caches ([H, S, D] model dtype <-> uint8 / FP8 images + qparams).
- * cc_decode_step_quant: c->k_cache / c->v_cache are the uint8 IMAGES [H, S, D], c->dtype the MODEL dtype (of q, k_new,
+ * 4-bit images (CC_QUANT_UINT4): the uint8 grid with 15 steps; qparams keeps its shape and meaning (k_scale, k_min, v_scale, v_min):
+ *       mn, mx = min / max over the row's D values;  range = max(mx - mn, 1e-6f);  scale = range / 15.f;
+ *       q[d]   = clamp(rintf((x[d] - mn) * (15.f / range)), 0, 15)                  (IEEE fp32 ops, round-half-even, no contraction)
+ *       value  = T(fmaf((float)q[d], scale, mn))
+ *       byte j of a row's D / 2-byte image holds q[2j] | q[2j + 1] << 4   (low nibble first, as the reference's pack_low_bit_tensor)
+ *   Images are [H, S, D / 2] bytes, a quarter of the 16-bit cache.  16-bit model dtypes only (the converters return
+ *   CC_ERR_UNSUPPORTED for fp32), even D.
+ * cc_kv_quant_rows / cc_kv_dequant_rows convert whole caches ([H, S, D] model dtype <-> uint8 / FP8 / 4-bit images + qparams).
+ * cc_decode_step_quant: c->k_cache / c->v_cache are the IMAGES [H, S, D] (4-bit: [H, S, D / 2]), c->dtype the MODEL dtype (of q, k_new,
  *   v_new, y, attn_out); 16-bit dtype, D == 128, HQ / H in {4, 8} (CC_ERR_UNSUPPORTED otherwise).
  *   policy: 1 = heavy hitter (num / denom / counter as in cc_decode_step_heavy_hitter, c->Hp == H),
  *           2 = recent_global / full (num = denom = NULL, c->Hp == 1), 3 = random (rand_next as in cc_decode_step_random).
@@ -513,8 +522,8 @@ int cc_decode_step_quant_rc(const cc_kv_view* c, float* qparams, int32_t n_bit, 
                             cc_stream_t stream, int32_t phases);
 int32_t cc_decode_step_quant_single_launch(int32_t HQ, int32_t H, int32_t S, int32_t D, int32_t dtype, int32_t n_bit);
 /* The same images for the two history-ring policies.  Arguments as cc_decode_step_heavy_hitter_ring / cc_decode_step_hybrid_rc, plus
- * qparams [H, S, 4] and n_bit (the format: 8 or CC_QUANT_FP8_E4M3; others: CC_ERR_UNSUPPORTED, before any launch); c->k_cache /
- * c->v_cache are the uint8 images,
+ * qparams [H, S, 4] and n_bit (the format: 8, CC_QUANT_FP8_E4M3 or CC_QUANT_UINT4; others: CC_ERR_UNSUPPORTED, before any launch);
+ * c->k_cache / c->v_cache are the images,
  * c->dtype the model dtype.  16-bit dtype, D == 128, HQ / H in {4, 8} (CC_ERR_UNSUPPORTED otherwise).
  * cc_decode_step_heavy_hitter_ring_quant (history_window_size W > 1): two launches, as in 16 bits — the streaming pass reads the
  *   images and quantises the inserted token's rows ahead of its tile, the combine pass updates the ring, the window sums and the

@@ -9,6 +9,7 @@ import sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import torch  # noqa: E402
 
+from cold_compress_amd import _abi  # noqa: E402
 from cold_compress_amd.attention_utils import scaled_dot_product_attention as sdpa  # noqa: E402
 from cold_compress_amd.cache import get_cache_constructor  # noqa: E402
 
@@ -46,6 +47,9 @@ def timed(fn, n, iters=8, after=None):
     return ts[len(ts) // 2]
 
 
+QBITS = {"fused": 8, "fp8": 8, "uint4": 4}  # cache_quant_mode -> the cache_bits it serves
+
+
 def make(strategy, H, S, D, extra=None):
     cls, rk = get_cache_constructor(strategy)
     kw = dict(max_cache_length=S, global_tokens=4, max_seq_length=4 * S, cache_bits=None, recent_window=10, history_window_size=1,
@@ -58,7 +62,12 @@ def make(strategy, H, S, D, extra=None):
     with torch.device(dev):
         kv = cls(1, H, D, torch.bfloat16, **lk)
     T = S
-    if getattr(kv, "fused_quant", False) and kv.quant_format != 8:  # FP8 images of N(0, 1) rows, scale 2^0
+    if getattr(kv, "fused_quant", False) and kv.quant_format == _abi.CC_QUANT_UINT4:  # 4-bit images of N(0, 1) rows: 15 steps over [-3.2, 3.2]
+        kv.k_cache_q.copy_(torch.randint(0, 256, kv.k_cache_q.shape, device=dev, dtype=torch.int32).to(torch.uint8))
+        kv.v_cache_q.copy_(torch.randint(0, 256, kv.v_cache_q.shape, device=dev, dtype=torch.int32).to(torch.uint8))
+        kv.kv_qparams[..., 0::2] = 6.4 / 15
+        kv.kv_qparams[..., 1::2] = -3.2
+    elif getattr(kv, "fused_quant", False) and kv.quant_format != 8:  # FP8 images of N(0, 1) rows, scale 2^0
         kv.k_cache_q.copy_(torch.randn(kv.cache_shape, device=dev).to(torch.float8_e4m3fn).view(torch.uint8))
         kv.v_cache_q.copy_(torch.randn(kv.cache_shape, device=dev).to(torch.float8_e4m3fn).view(torch.uint8))
         kv.kv_qparams[..., 0::2] = 1.0
@@ -122,12 +131,12 @@ def main():
                     kv.prepare_decode(pos)
                 res["fused_step_us"] = round(timed(lambda i: caches[i % n_buf].decode_step(q, k1, k1, pos), n_buf, after=lambda: pos.add_(1)), 2)
             if strategy in ("heavy_hitter", "recent_global", "full", "random"):
-                # the opt-in fused quantised cache (cache_bits=8, cache_quant_mode="fused" / "fp8"): uint8 or FP8 images streamed,
-                # dequantised in registers
-                for key, mode in (("fused_quant8_step_us", "fused"), ("fused_fp8_step_us", "fp8")):
+                # the opt-in fused quantised cache (cache_bits=8, cache_quant_mode="fused" / "fp8"; cache_bits=4, "uint4"): uint8, FP8
+                # or 4-bit images streamed, dequantised in registers
+                for key, mode in (("fused_quant8_step_us", "fused"), ("fused_fp8_step_us", "fp8"), ("fused_uint4_step_us", "uint4")):
                     del caches
                     torch.cuda.empty_cache()
-                    caches = [make(strategy, H, S, D, {"cache_bits": 8, "cache_quant_mode": mode}) for _ in range(n_buf)]
+                    caches = [make(strategy, H, S, D, {"cache_bits": QBITS[mode], "cache_quant_mode": mode}) for _ in range(n_buf)]
                     for kv in caches:
                         kv.prepare_decode(pos)
                     for i in range(n_buf):
@@ -138,11 +147,11 @@ def main():
                     kv.prepare_decode(pos)
                 res["fused_step_us"] = round(timed(lambda i: caches[i % n_buf].decode_step(q, k1, k1, pos, input_ids=ids), n_buf, after=lambda: pos.add_(1)), 2)
                 res["fused_one_launch"] = caches[0].single_launch_active(HQ)
-                # the hybrid step over uint8 images (cache_quant_mode="fused") and over FP8 images ("fp8")
-                for key, mode in (("fused_quant8", "fused"), ("fused_fp8", "fp8")):
+                # the hybrid step over uint8 images (cache_quant_mode="fused"), FP8 images ("fp8") and 4-bit images ("uint4")
+                for key, mode in (("fused_quant8", "fused"), ("fused_fp8", "fp8"), ("fused_uint4", "uint4")):
                     del caches
                     torch.cuda.empty_cache()
-                    caches = [make(strategy, H, S, D, {"cache_bits": 8, "cache_quant_mode": mode}) for _ in range(n_buf)]
+                    caches = [make(strategy, H, S, D, {"cache_bits": QBITS[mode], "cache_quant_mode": mode}) for _ in range(n_buf)]
                     for kv in caches:
                         kv.prepare_decode(pos)
                     for i in range(n_buf):
@@ -168,7 +177,8 @@ def main():
             pos = torch.tensor([S + 100], dtype=torch.int32, device=dev)
             n_w = max(4, min(n_buf, (900 << 20) // (H * S * (W * 2 + 2 * D * 2)) + 1))
             for key, extra in (("fused_step_us", {}), ("fused_quant8_step_us", {"cache_bits": 8, "cache_quant_mode": "fused"}),
-                               ("fused_fp8_step_us", {"cache_bits": 8, "cache_quant_mode": "fp8"})):
+                               ("fused_fp8_step_us", {"cache_bits": 8, "cache_quant_mode": "fp8"}),
+                               ("fused_uint4_step_us", {"cache_bits": 4, "cache_quant_mode": "uint4"})):
                 caches = [make("heavy_hitter", H, S, D, dict(extra, history_window_size=W)) for _ in range(n_w)]
                 for kv in caches:
                     kv.prepare_decode(pos)
