@@ -522,3 +522,30 @@ def generate(model, prompt, prefill, decode_one_token, max_new_tokens, next_toke
     if -1 in seq:
         seq = seq[: torch.where(seq == -1)[0][0]]
     return seq, [next_tok_probs] + tok_probs, stats
+
+
+def load_model(checkpoint_path, device, precision, use_tp):
+    """ref: generation_utils.py:534-566.  The shape is the CONFIGS entry named by the checkpoint's directory; a path naming int8
+    is a weight-only int8 checkpoint (harness/quantize.py), whose int8 buffers stay int8 through `.to(device, precision)`."""
+    from pathlib import Path
+
+    from .. import _abi
+    from .quantize import WeightOnlyInt8QuantHandler
+
+    checkpoint_path = Path(checkpoint_path)
+    if "int4" in str(checkpoint_path):
+        raise _abi.ColdCompressError(f"{checkpoint_path}: int4 weight-only checkpoints are not supported (int8 weight-only is)")
+    with torch.device("meta"):
+        model = Transformer.from_name(checkpoint_path.parent.name)
+    if "int8" in str(checkpoint_path):
+        model = WeightOnlyInt8QuantHandler(model).convert_for_runtime()
+    checkpoint = torch.load(str(checkpoint_path), mmap=True, weights_only=True)
+    if "model" in checkpoint and "stories" in str(checkpoint_path):
+        checkpoint = checkpoint["model"]
+    model.load_state_dict(checkpoint, assign=True)
+    if use_tp:
+        from ..tp import apply_tp
+
+        apply_tp(model)
+    model = model.to(device=device, dtype=precision)
+    return model.eval()

@@ -69,21 +69,42 @@ def silu_mul(a, b):
 
 
 def gemv_supported(*weights):
-    """Single-token dense layers on the device path: the input vector must fit the kernel's LDS staging buffer."""
-    return all(w.is_cuda and w.is_contiguous() and w.dtype in _DT and w.shape[1] * w.element_size() <= 64 * 1024
-               and w.shape[1] % (16 // w.element_size()) == 0 for w in weights)
+    """Single-token dense layers on the device path: the input vector must fit the kernel's LDS staging buffer.  int8 weights
+    (weight-only int8 linears) stream through cc_gemv_fused_w8: 16-bit activations, K a multiple of 16."""
+    def ok(w):
+        if not (w.is_cuda and w.is_contiguous()):
+            return False
+        if w.dtype == torch.int8:
+            return w.shape[1] * 2 <= 64 * 1024 and w.shape[1] % 16 == 0
+        return w.dtype in _DT and w.shape[1] * w.element_size() <= 64 * 1024 and w.shape[1] % (16 // w.element_size()) == 0
+    return all(ok(w) for w in weights)
 
 
 def gemv_fused(weight, x, w3=None, delta=None, norm_weight=None, eps=1e-5, h_out=None, bias=None, freqs=None, rope_rows=0,
-               head_dim=0):
+               head_dim=0, scales=None, scales3=None):
     """One decode-time dense layer with its glue fused (cc_gemv_fused): optional RMSNorm(x + delta) prologue (h_out
     receives x + delta), optional SwiGLU pairing with `w3`, optional RoPE epilogue on the first `rope_rows` rows.
-    x: [K] (any shape with K elements); returns [N] in the model dtype."""
+    x: [K] (any shape with K elements); returns [N] in the model dtype.
+    int8 `weight` (and `w3`): weight-only int8 with per-row `scales` (`scales3`) in x's dtype (cc_gemv_fused_w8)."""
     N, K = weight.shape
     xc = x.contiguous()
+    dc = delta.contiguous() if delta is not None else None
+    fc = freqs.contiguous() if freqs is not None else None
+    if weight.dtype == torch.int8:
+        if scales is None or (w3 is not None and (w3.dtype != torch.int8 or scales3 is None)):
+            raise _abi.ColdCompressError("gemv_fused: int8 weights need their per-row scales (and w3 int8 with scales3)")
+        dt = x.dtype
+        if dt not in (torch.bfloat16, torch.float16):
+            raise _abi.ColdCompressError(f"gemv_fused: int8 weights need 16-bit activations, got {dt}")
+        sc = scales.to(dt).contiguous()
+        sc3 = scales3.to(dt).contiguous() if w3 is not None else None
+        y = torch.empty((N,), dtype=dt, device=weight.device)
+        _abi.call("cc_gemv_fused_w8", _p(weight), _p(sc), _p(w3), _p(sc3), _p(xc), _p(dc), _p(norm_weight), float(eps), _p(h_out),
+                  _p(bias), _p(fc), int(rope_rows), int(head_dim), _p(y), N, K, _DT[dt], _stream())
+        return y
     y = torch.empty((N,), dtype=weight.dtype, device=weight.device)
-    _abi.call("cc_gemv_fused", _p(weight), _p(w3), _p(xc), _p(delta.contiguous() if delta is not None else None), _p(norm_weight),
-              float(eps), _p(h_out), _p(bias), _p(freqs.contiguous() if freqs is not None else None), int(rope_rows), int(head_dim),
+    _abi.call("cc_gemv_fused", _p(weight), _p(w3), _p(xc), _p(dc), _p(norm_weight),
+              float(eps), _p(h_out), _p(bias), _p(fc), int(rope_rows), int(head_dim),
               _p(y), N, K, _DT[weight.dtype], _stream())
     return y
 

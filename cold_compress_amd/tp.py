@@ -4,8 +4,9 @@ Same surface as ref: tp.py (`maybe_init_dist() -> Optional[int]`, `apply_tp(mode
 one-process-per-GPU `torch.distributed` where backend "nccl" IS RCCL on ROCm (gloo on CPU for tests).
 What shards: wqkv column-wise per q/k/v block, wo/w2 row-wise, w1/w3 column-wise; KV heads
 and ALL per-head cache state shard with them (eviction needs no exchange); embeddings and the LM head are
-replicas.  Two sum all-reduces per layer (after attention, after the FFN), issued in place on the ROCm
-stream.  At decode the messages are 2*dim bytes (8-16 KiB): latency-bound on xGMI, one RCCL call each.
+replicas.  Weight-only int8 linears (harness/quantize.py) shard like the reference's (tp.py:99-100): column-wise splits the
+weight rows and the per-row scales, row-wise splits the weight columns and keeps the scales whole; int4 is not supported.
+Two sum all-reduces per layer (after attention, after the FFN), issued in place on the ROCm stream.  At decode the messages are 2*dim bytes (8-16 KiB): latency-bound on xGMI, one RCCL call each.
 
 Unlike the reference, a rank may own a single KV head (Llama-3 70B at TP=8): the reference's
 KVCacheHeavyHitter crashes there (cache.py:751/:480); ours does not.
@@ -65,7 +66,7 @@ def _shard(x: torch.Tensor, dim: int, world: int, rank: int) -> torch.Tensor:
 
 
 def _apply_tp_linear(linear: nn.Linear, style: str, weight_splits: List[int] = ()) -> None:
-    """ref: tp.py:59-121 (bf16/fp32 linears only; weight-only int8/int4 are out of scope)."""
+    """ref: tp.py:59-121 — dense and weight-only int8 linears (the int8 weight stays a buffer; its `scales` follow the rows)."""
     world, rank = _world_rank()
     dim, attr = {"colwise": (0, "out_features"), "rowwise": (1, "in_features")}[style]
     assert getattr(linear, attr) % world == 0
@@ -75,6 +76,14 @@ def _apply_tp_linear(linear: nn.Linear, style: str, weight_splits: List[int] = (
             return torch.cat([_shard(p, d, world, rank) for p in t.split(list(weight_splits), dim=d)], dim=d)
         return _shard(t, d, world, rank)
 
+    if linear.weight.dtype == torch.int8:  # weight-only int8: weight / scales / bias are buffers
+        linear.weight = split(linear.weight, dim).contiguous()
+        if style == "colwise":
+            linear.scales = split(linear.scales, 0).contiguous()
+            if linear.bias is not None:
+                linear.bias = split(linear.bias, 0).contiguous()
+        setattr(linear, attr, getattr(linear, attr) // world)
+        return
     linear.weight = nn.Parameter(split(linear.weight, dim).contiguous(), requires_grad=False)
     if linear.bias is not None and style == "colwise":
         linear.bias = nn.Parameter(split(linear.bias, 0).contiguous(), requires_grad=False)

@@ -751,6 +751,24 @@ int cc_gemv_fused(const void* W, const void* W3, const void* x, const void* delt
                   void* h_out, const void* bias, const void* freqs, int32_t rope_rows, int32_t head_dim, void* y,
                   int32_t N, int32_t K, int32_t dtype, cc_stream_t stream);
 
+/* The same decode-time dense layer over INT8 WEIGHT-ONLY matrices (the weight-only int8 checkpoint format, ref: quantize.py
+ * WeightOnlyInt8QuantHandler / WeightOnlyInt8Linear): W, W3 int8 [N, K] row major, one scale per output row, scales / scales3 [N]
+ * in `dtype`, which is also the activation, bias, freqs and output dtype.
+ *   quantisation (the checkpoint's, per row n of w = weight.float()): lo = min(min_k w, 0), hi = max(max_k w, 0),
+ *             s32 = max(max(-lo, hi) / 127.5, FLT_EPSILON) in fp32, q = clamp(round_half_even(w / s32), -128, 127),
+ *             scales[n] = dtype(s32) (the division uses the fp32 scale, the product the rounded one: the reference's asymmetry).
+ *   prologue  exactly cc_gemv_fused's: h_out and the normalised input `in` are bit-identical to it.
+ *   product   p[n] = dtype(sum_k in[k] * q[n,k]), fp32 accumulation (int8 x 16-bit products are exact);
+ *             t[n] = dtype(p[n] * scales[n]); with bias t[n] = dtype(t[n] + bias[n])   (F.linear -> * scales -> += bias).
+ *   W3 != NULL (needs scales3): t3 likewise with scales3, y = dtype(dtype(silu(t)) * t3); no bias.
+ *   freqs != NULL: RoPE on rows [0, rope_rows) of the rounded t, as cc_gemv_fused.
+ * dtype: CC_DT_BF16 or CC_DT_F16 (CC_DT_F32: CC_ERR_UNSUPPORTED).  K % 16 == 0 and K * sizeof(dtype) <= 64 KiB, else
+ * CC_ERR_UNSUPPORTED.  Summation order inside a dot product is the kernel's own (tolerance class) but fixed: results are
+ * bit-reproducible from run to run and under graph replay.  Arguments are validated before any launch: an error writes nothing. */
+int cc_gemv_fused_w8(const int8_t* W, const void* scales, const int8_t* W3, const void* scales3, const void* x,
+                     const void* delta, const void* norm_w, float eps, void* h_out, const void* bias, const void* freqs,
+                     int32_t rope_rows, int32_t head_dim, void* y, int32_t N, int32_t K, int32_t dtype, cc_stream_t stream);
+
 /* Greedy sampling tail, ref: generation_utils.py:136-142: probs[V] = dtype(softmax_fp32(logits[V])),
  * *idx_out = first index of the largest rounded probability (torch.argmax semantics).  Two small launches; `workspace`
  * (cc_softmax_argmax_workspace_bytes) needs no initialisation. */
