@@ -1,0 +1,355 @@
+// cc_gemv_w4.hip — the int4 group-wise weight-only counterpart of cc_gemv.hip / cc_gemv_w8.hip: the same five decode-layer forms
+// (plain, RMSNorm(x + delta) prologue with h_out, SwiGLU pair, RoPE epilogue, bias) over W stored as uint8 [N, K / 2] (two 4-bit
+// codes per byte, column 2j in the low nibble) with one bf16 (scale, zero) pair per row and group of G columns, held per row as
+// [N, K / G] 32-bit words (harness/quantize.py WeightOnlyInt4Linear; the reference's formula is W = (q - 8) * scale + zero).
+//
+// Layout: one non-temporal 16-byte load per lane carries 32 codes, so a wave covers a 1 KiB segment of a row (2048 weights) per load
+// instruction.  A decode row is short at int4 (K = 4096: 2 KiB, two segments), so the four waves of a workgroup split into WS waves
+// per row (WS = 1, 2 or 4, from the segment count) and 4 / WS row groups; RB rows and CU segments per wave are in flight together,
+// and the FIRST tile's weights are requested before the input vector is touched.  A 32-column chunk never straddles a group
+// (G >= 32), so each lane fetches one (scale, zero) word per chunk and row beside the codes.
+//
+// Arithmetic, group-factored (per chunk of 32 columns, one group):  sum_k x_k ((q_k - 8) s + z) = s (sum_k x_k (128 + q_k) - 136 Sx) + z Sx
+// with Sx = sum_k x_k.  The codes become bf16 128 + q EXACTLY (v_perm puts each nibble byte under a 0x43 exponent byte) and go
+// through the 16-bit kernel's packed v_dot2_f32_bf16, starting from -136 Sx; the lane pre-pairs its inputs to the perm's column
+// order (even columns of a word, then odd) once, and Sx depends on x alone, so it is computed once per lane.  Per chunk and row:
+// 3 ops per code word + 4 perms + 4 dot2 per 8 codes, then 2 fma and 2 bit ops: about 3 VALU operations per weight byte.  The
+// cancellation costs about 7 of fp32's 24 bits, far below a bf16 ulp.
+//
+// The RMSNorm prologue runs in the 16-bit kernel's layout (8 elements per lane and chunk, the same chunk order, the same fp32
+// chains and the same LDS reduction): h_out and the normalised input are bit-identical to cc_gemv_fused's.  The normalised vector
+// is passed to the lanes that multiply it through LDS (K * 2 bytes, norm forms only).
+#include <cstdio>
+#include <cstdlib>
+
+#include "cc_common.h"
+#include "cc_gemv_core.h"
+
+namespace {
+
+struct GemvW4Args {
+  const uint8_t* W;
+  const uint8_t* W3;      // second matrix of the SwiGLU pair, or null
+  const uint32_t* qp;     // [N, K / G] (scale, zero) bf16 pairs, the scale in the low half
+  const uint32_t* qp3;    // the same for W3
+  const void* x;          // [K] bf16
+  const void* delta;      // [K] pending residual, or null
+  const void* norm_w;     // [K] RMSNorm weight, or null (no norm prologue)
+  const void* bias;       // [N] or null
+  const void* freqs;      // [head_dim/2, 2] (cos, sin) of this position, or null
+  void* h_out;            // [K] x + delta, or null
+  void* y;                // [N]
+  float eps;
+  int N, K, gshift, rope_rows, head_dim;  // gshift = log2(G / 32): the group of 32-column chunk c is c >> gshift
+};
+
+constexpr int kW4Threads = 256;
+constexpr int kW4Waves = kW4Threads / 64;
+
+__device__ __forceinline__ uint32_t nt_load_u32(const uint32_t* p) { return __builtin_nontemporal_load(p); }
+
+__device__ __forceinline__ float dot2_bf16(uint32_t a, uint32_t b, float acc) {
+  return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, a), __builtin_bit_cast(bf16x2_t, b), acc, false);
+}
+
+// acc += sum over the 8 codes of w (columns 8i .. 8i + 7 of a chunk) of (128 + q) * x; xr holds that word's inputs as the bf16
+// pairs (x0, x2), (x4, x6), (x1, x3), (x5, x7)
+__device__ __forceinline__ float dot_w4_word(uint32_t w, uint4 xr, float acc) {
+  const uint32_t lo = w & 0x0F0F0F0Fu;         // codes of columns 0, 2, 4, 6
+  const uint32_t hi = (w >> 4) & 0x0F0F0F0Fu;  // codes of columns 1, 3, 5, 7
+  constexpr uint32_t kExp = 0x43434343u;       // byte q under 0x43: the bf16 128 + q
+  acc = dot2_bf16(__builtin_amdgcn_perm(kExp, lo, 0x04010400u), xr.x, acc);
+  acc = dot2_bf16(__builtin_amdgcn_perm(kExp, lo, 0x04030402u), xr.y, acc);
+  acc = dot2_bf16(__builtin_amdgcn_perm(kExp, hi, 0x04010400u), xr.z, acc);
+  acc = dot2_bf16(__builtin_amdgcn_perm(kExp, hi, 0x04030402u), xr.w, acc);
+  return acc;
+}
+
+// one chunk (32 codes) of a row: sum x (q - 8) (from -136 Sx), then the group's scale and zero
+__device__ __forceinline__ float chunk_w4(uint4 w, uint32_t q, const uint4 (&xr)[4], float sx, float m136, float acc) {
+  float d = dot_w4_word(w.x, xr[0], m136);
+  d = dot_w4_word(w.y, xr[1], d);
+  d = dot_w4_word(w.z, xr[2], d);
+  d = dot_w4_word(w.w, xr[3], d);
+  acc = fmaf(__uint_as_float(q << 16), d, acc);              // scale
+  return fmaf(__uint_as_float(q & 0xffff0000u), sx, acc);    // zero
+}
+
+template <bool SWIGLU, int RB, int CU, int XS, int WS>
+__global__ __launch_bounds__(kW4Threads) void gemv_w4_kernel(GemvW4Args a) {
+  typedef bf16_t T;
+  constexpr int VEC = 8;             // bf16 elements per 16-byte chunk of the input
+  constexpr int RG = kW4Waves / WS;  // row groups of a workgroup
+  constexpr int RW = RB * RG;        // rows per workgroup round (even: RoPE's pair partner is lane ^ 1)
+  static_assert(RW <= 64 && RW % 2 == 0, "rows per round");
+  extern __shared__ uint4 sm_in[];   // the normalised input, norm forms only (K / 8 chunks)
+  __shared__ float sm_red[kW4Waves];
+  __shared__ float sm_part[kW4Waves][2][RB];
+  const int K = a.K, N = a.N;
+  const int nch = K / 32;            // 16-byte code chunks per row
+  const int ngr = nch >> a.gshift;   // groups per row
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int ws = wave % WS, rg = wave / WS;
+  const int nseg = (nch + 63) / 64;
+  const int nstep = (nseg + WS - 1) / WS;  // segments per wave (<= XS, checked by the launcher)
+  const uint4* Wv = reinterpret_cast<const uint4*>(a.W);
+  const uint4* W3v = reinterpret_cast<const uint4*>(a.W3);
+  uint4 w[RB][CU], w3[RB][CU];
+  uint32_t q[RB][CU], q3[RB][CU];
+  auto issue = [&](int r0, int s0) {  // r0: this wave's first row
+#pragma unroll
+    for (int u = 0; u < CU; u++) {
+      const int c = ((s0 + u) * WS + ws) * 64 + lane;
+      const bool cin = (s0 + u < nstep) && c < nch;
+#pragma unroll
+      for (int r = 0; r < RB; r++) {
+        const bool in = cin && (r0 + r < N);
+        const size_t off = (size_t)(r0 + r) * nch + c;
+        const size_t qoff = (size_t)(r0 + r) * ngr + (c >> a.gshift);
+        w[r][u] = in ? nt_load(Wv + off) : make_uint4(0, 0, 0, 0);
+        q[r][u] = in ? nt_load_u32(a.qp + qoff) : 0u;
+        if (SWIGLU) {
+          w3[r][u] = in ? nt_load(W3v + off) : make_uint4(0, 0, 0, 0);
+          q3[r][u] = in ? nt_load_u32(a.qp3 + qoff) : 0u;
+        }
+      }
+    }
+  };
+  const int row_first = blockIdx.x * RW;  // < N (the launcher sizes the grid)
+  issue(row_first + rg * RB, 0);
+
+  // ---- the input vector: the lane keeps elements [32 c, 32 c + 32) of every chunk c = (j * WS + ws) * 64 + lane it multiplies
+  uint4 xv[XS][4];
+  if (a.norm_w != nullptr) {
+    // cc_gemv.hip's prologue, operation for operation: 8-element chunks c8 = (j * 4 + wave) * 64 + lane, the same sum-of-squares
+    // chain per lane, the same wave and workgroup reductions
+    const int nch8 = K / VEC;
+    const int nstep8 = ((nch8 + 63) / 64 + kW4Waves - 1) / kW4Waves;
+    const T* xg = reinterpret_cast<const T*>(a.x);
+    const T* dg = reinterpret_cast<const T*>(a.delta);
+    const T* wg = reinterpret_cast<const T*>(a.norm_w);
+    float ss = 0.f;
+    for (int j = 0; j < nstep8; j++) {
+      const int c = (j * kW4Waves + wave) * 64 + lane;
+      if (c < nch8) {
+        Vec16<T> xl, dv;
+        float h[VEC];
+        xl.load(xg + (size_t)c * VEC);
+        xl.unpack(h);
+        if (dg != nullptr) {
+          float d[VEC];
+          dv.load(dg + (size_t)c * VEC);
+          dv.unpack(d);
+#pragma unroll
+          for (int e = 0; e < VEC; e++) h[e] = ElemTraits<T>::rnd(__fadd_rn(h[e], d[e]));  // model-dtype residual add
+        }
+#pragma unroll
+        for (int e = 0; e < VEC; e++) ss = fmaf(h[e], h[e], ss);
+        const uint4 hp = pack16<T>(h);
+        sm_in[c] = hp;
+        if (a.h_out != nullptr && blockIdx.x == 0) reinterpret_cast<uint4*>(a.h_out)[c] = hp;
+      }
+    }
+    ss = gv_wave_sum(ss);
+    if (lane == 0) sm_red[wave] = ss;
+    __syncthreads();
+    const float tot = (sm_red[0] + sm_red[1]) + (sm_red[2] + sm_red[3]);
+    const float rs = rsqrtf(tot / (float)K + a.eps);
+    for (int j = 0; j < nstep8; j++) {
+      const int c = (j * kW4Waves + wave) * 64 + lane;
+      if (c < nch8) {  // (each lane rewrites only the chunks it wrote)
+        Vec16<T> hv, nv;
+        float h[VEC], wf[VEC], o[VEC];
+        hv.raw = sm_in[c];
+        nv.load(wg + (size_t)c * VEC);
+        hv.unpack(h);
+        nv.unpack(wf);
+#pragma unroll
+        for (int e = 0; e < VEC; e++) o[e] = ElemTraits<T>::rnd(__fmul_rn(ElemTraits<T>::rnd(cc_opaque_f32(__fmul_rn(h[e], rs))), wf[e]));
+        sm_in[c] = pack16<T>(o);
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < XS; j++) {
+      const int c = (j * WS + ws) * 64 + lane;
+      const bool in = j < nstep && c < nch;
+#pragma unroll
+      for (int i = 0; i < 4; i++) xv[j][i] = in ? sm_in[4 * c + i] : make_uint4(0, 0, 0, 0);
+    }
+  } else {
+    const uint4* xg = reinterpret_cast<const uint4*>(a.x);
+#pragma unroll
+    for (int j = 0; j < XS; j++) {
+      const int c = (j * WS + ws) * 64 + lane;
+      const bool in = j < nstep && c < nch;
+#pragma unroll
+      for (int i = 0; i < 4; i++) xv[j][i] = in ? xg[4 * c + i] : make_uint4(0, 0, 0, 0);
+    }
+  }
+  // pair the inputs to the perm's column order and take the per-chunk sums (once per lane)
+  uint4 xr[XS][4];
+  float sx[XS], m136[XS];
+#pragma unroll
+  for (int j = 0; j < XS; j++) {
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const uint4 v = xv[j][i];
+      xr[j][i] = make_uint4(__builtin_amdgcn_perm(v.y, v.x, 0x05040100u), __builtin_amdgcn_perm(v.w, v.z, 0x05040100u),
+                            __builtin_amdgcn_perm(v.y, v.x, 0x07060302u), __builtin_amdgcn_perm(v.w, v.z, 0x07060302u));
+      s = dot2_bf16(v.x, 0x3F803F80u, s);  // (1, 1)
+      s = dot2_bf16(v.y, 0x3F803F80u, s);
+      s = dot2_bf16(v.z, 0x3F803F80u, s);
+      s = dot2_bf16(v.w, 0x3F803F80u, s);
+    }
+    sx[j] = s;
+    m136[j] = -136.f * s;
+  }
+
+  T* yo = reinterpret_cast<T*>(a.y);
+  bool first = true;
+  for (int r0 = row_first; r0 < N; r0 += gridDim.x * RW) {
+    const int rw0 = r0 + rg * RB;
+    float acc[RB], acc3[RB];
+#pragma unroll
+    for (int r = 0; r < RB; r++) acc[r] = acc3[r] = 0.f;
+#pragma unroll
+    for (int s0 = 0; s0 < XS; s0 += CU) {
+      if (s0 < nstep) {
+        if (!first) issue(rw0, s0);
+        first = false;
+#pragma unroll
+        for (int u = 0; u < CU; u++) {
+          const int j = s0 + u < XS ? s0 + u : XS - 1;  // beyond nstep the codes and (scale, zero) are zero-filled
+#pragma unroll
+          for (int r = 0; r < RB; r++) {
+            acc[r] = chunk_w4(w[r][u], q[r][u], xr[j], sx[j], m136[j], acc[r]);
+            if (SWIGLU) acc3[r] = chunk_w4(w3[r][u], q3[r][u], xr[j], sx[j], m136[j], acc3[r]);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < RB; r++) {
+      const float s = gv_wave_sum(acc[r]);
+      float s3 = 0.f;
+      if (SWIGLU) s3 = gv_wave_sum(acc3[r]);
+      if (lane == 0) {
+        sm_part[wave][0][r] = s;
+        if (SWIGLU) sm_part[wave][1][r] = s3;
+      }
+    }
+    __syncthreads();
+    if (wave == 0) {
+      const int l = lane < RW ? lane : 0;
+      const int g = l / RB, r = l % RB;
+      const int row = r0 + l;
+      const int rowc = row < N ? row : N - 1;
+      auto part = [&](int m) {  // the WS waves of row group g, in a fixed order
+        if (WS == 1) return sm_part[g][m][r];
+        if (WS == 2) return sm_part[2 * g][m][r] + sm_part[2 * g + 1][m][r];
+        return (sm_part[0][m][r] + sm_part[1][m][r]) + (sm_part[2][m][r] + sm_part[3][m][r]);
+      };
+      // t = bf16(p); with bias t = bf16(t + bias)
+      float s = ElemTraits<T>::rnd(cc_opaque_f32(part(0)));
+      if (a.bias != nullptr) s = ElemTraits<T>::rnd(cc_opaque_f32(__fadd_rn(s, ElemTraits<T>::load(reinterpret_cast<const T*>(a.bias), (size_t)rowc))));
+      if (SWIGLU) {
+        const float s3 = ElemTraits<T>::rnd(cc_opaque_f32(part(1)));
+        const float sl = ElemTraits<T>::rnd(__fdiv_rn(s, 1.0f + expf(-s)));  // F.silu -> dtype
+        s = __fmul_rn(sl, s3);
+      }
+      float out = s;
+      if (a.freqs != nullptr) {  // RoPE on the (even, odd) row pairs of the q / k heads, on the rounded t
+        const float other = gv_dpp<0xB1>(out);  // the pair partner lives in lane ^ 1 (r0 is even)
+        if (row < a.rope_rows) {
+          const int pr = (row % a.head_dim) >> 1;
+          const float c = ElemTraits<T>::load(reinterpret_cast<const T*>(a.freqs), (size_t)pr * 2);
+          const float sn = ElemTraits<T>::load(reinterpret_cast<const T*>(a.freqs), (size_t)pr * 2 + 1);
+          out = (row & 1) ? __fadd_rn(__fmul_rn(out, c), __fmul_rn(other, sn)) : __fsub_rn(__fmul_rn(out, c), __fmul_rn(other, sn));
+        }
+      }
+      if (lane < RW && row < N) ElemTraits<T>::store(yo, (size_t)row, cc_opaque_f32(out));
+    }
+    __syncthreads();  // sm_part is reused by the next row group
+  }
+}
+
+struct W4Cfg {
+  int rb, cu, cap;
+};
+
+// rows x segments in flight per wave, by segments per wave (nstep) and form; tools/bench_gemv_w4.py measured them
+static W4Cfg pick_w4_cfg(const GemvW4Args& a, int nstep) {
+  static int env_rb = -1, env_cu = -1, env_cap = 2048;
+  if (env_rb < 0) {  // tuning hook: CC_GEMV_W4_CFG="RB,CU[,max workgroups]"
+    env_rb = env_cu = 0;
+    if (const char* e = getenv("CC_GEMV_W4_CFG")) sscanf(e, "%d,%d,%d", &env_rb, &env_cu, &env_cap);
+  }
+  if (env_rb > 0 && env_cu > 0) return {env_rb, env_cu, env_cap};
+  // same-box sweep (profiles/w4_gemv_sweep.jsonl, G = 32): the pair 4 x 1 at 2048 / 1024 / 512 workgroups 22.7 / 20.0 / 19.2 us
+  // (2 x 1: 21.7, 8 x 1: 21.0-23.6); w2 4 x 2 x 512 10.9 us (8 x 2: 11.7-12.4, 8 x 1: 11.3); one-segment plain rows 4 x 1 x 1024
+  // (LM head 60.6 us against 62.4-65.5, wqkv 8.4, wo 5.0).  Fewer, longer-lived workgroups amortise the per-workgroup prologue.
+  // Rows of more than two segments per wave (K > 16384 at WS = 4, e.g. the 70B w2) take w2's choice; the sweep did not cover them.
+  if (nstep <= 1) return a.W3 != nullptr ? W4Cfg{4, 1, 512} : W4Cfg{4, 1, 1024};
+  return a.W3 != nullptr ? W4Cfg{2, 2, 512} : W4Cfg{4, 2, 512};
+}
+
+template <bool SWIGLU, int RB, int CU, int XS, int WS>
+static void launch_w4_cfg(const GemvW4Args& a, hipStream_t st, int cap) {
+  constexpr int RW = RB * (kW4Waves / WS);
+  int blocks = (a.N + RW - 1) / RW;
+  if (blocks > cap) blocks = cap;
+  const size_t lds = a.norm_w != nullptr ? (size_t)a.K * sizeof(bf16_t) : 0;
+  hipLaunchKernelGGL((gemv_w4_kernel<SWIGLU, RB, CU, XS, WS>), dim3(blocks), dim3(kW4Threads), lds, st, a);
+}
+
+static int launch_gemv_w4(const GemvW4Args& a, hipStream_t st) {
+  const int nseg = (a.K / 32 + 63) / 64;
+  const int ws = nseg >= 3 ? 4 : nseg;  // waves per row: a short row leaves no wave idle
+  const int nstep = (nseg + ws - 1) / ws;
+  const W4Cfg c = pick_w4_cfg(a, nstep);
+  const int xs = nstep <= 1 ? 1 : nstep <= 2 ? 2 : 4;  // input chunks kept per lane
+  if (nstep > 4 || c.cu > xs || c.cap <= 0) return CC_ERR_UNSUPPORTED;
+  const int key = (a.W3 ? 100000 : 0) + ws * 10000 + xs * 1000 + c.rb * 10 + c.cu;
+#define W4_CASE(SW, WS_, XS_, RB_, CU_) \
+  case (SW ? 100000 : 0) + WS_ * 10000 + XS_ * 1000 + RB_ * 10 + CU_: launch_w4_cfg<SW, RB_, CU_, XS_, WS_>(a, st, c.cap); break;
+  switch (key) {
+    W4_CASE(false, 1, 1, 2, 1) W4_CASE(false, 1, 1, 4, 1) W4_CASE(false, 1, 1, 8, 1)
+    W4_CASE(false, 2, 1, 2, 1) W4_CASE(false, 2, 1, 4, 1) W4_CASE(false, 2, 1, 8, 1)
+    W4_CASE(false, 4, 1, 2, 1) W4_CASE(false, 4, 1, 4, 1) W4_CASE(false, 4, 1, 8, 1)
+    W4_CASE(false, 4, 2, 4, 1) W4_CASE(false, 4, 2, 8, 1) W4_CASE(false, 4, 2, 2, 2) W4_CASE(false, 4, 2, 4, 2) W4_CASE(false, 4, 2, 8, 2)
+    W4_CASE(false, 4, 4, 2, 4) W4_CASE(false, 4, 4, 4, 2) W4_CASE(false, 4, 4, 8, 2) W4_CASE(false, 4, 4, 4, 4)
+    W4_CASE(true, 1, 1, 2, 1) W4_CASE(true, 1, 1, 4, 1) W4_CASE(true, 1, 1, 8, 1)
+    W4_CASE(true, 2, 1, 2, 1) W4_CASE(true, 2, 1, 4, 1) W4_CASE(true, 2, 1, 8, 1)
+    W4_CASE(true, 4, 1, 2, 1) W4_CASE(true, 4, 1, 4, 1) W4_CASE(true, 4, 1, 8, 1)
+    W4_CASE(true, 4, 2, 2, 1) W4_CASE(true, 4, 2, 4, 1) W4_CASE(true, 4, 2, 2, 2) W4_CASE(true, 4, 2, 4, 2)
+    W4_CASE(true, 4, 4, 2, 2) W4_CASE(true, 4, 4, 4, 2) W4_CASE(true, 4, 4, 2, 4)
+    default: return CC_ERR_UNSUPPORTED;
+  }
+#undef W4_CASE
+  CC_LAUNCH_CHECK();
+  return CC_OK;
+}
+
+}  // namespace
+
+extern "C" int cc_gemv_fused_w4(const uint8_t* W, const void* qparams, const uint8_t* W3, const void* qparams3, const void* x,
+                                const void* delta, const void* norm_w, float eps, void* h_out, const void* bias, const void* freqs,
+                                int32_t rope_rows, int32_t head_dim, void* y, int32_t N, int32_t K, int32_t groupsize, int32_t dtype,
+                                cc_stream_t stream) {
+  CC_ENTRY();
+  if (!W || !qparams || !x || !y || N <= 0 || K <= 0 || !cc_dt_ok(dtype)) return CC_ERR_BAD_ARG;
+  if ((W3 != nullptr) != (qparams3 != nullptr)) return CC_ERR_BAD_ARG;
+  if ((delta || h_out) && !norm_w) return CC_ERR_BAD_ARG;
+  if (freqs && (W3 || rope_rows < 0 || rope_rows > N || head_dim <= 0 || (head_dim & 1) || (rope_rows % head_dim))) return CC_ERR_BAD_ARG;
+  if (W3 && bias) return CC_ERR_BAD_ARG;
+  const int gshift = groupsize == 32 ? 0 : groupsize == 64 ? 1 : groupsize == 128 ? 2 : groupsize == 256 ? 3 : -1;
+  if (gshift < 0) return CC_ERR_BAD_ARG;
+  if (dtype != CC_DT_BF16) return CC_ERR_UNSUPPORTED;  // bf16 models only (the reference's int4 kernel is bf16-only)
+  if (K % groupsize) return CC_ERR_UNSUPPORTED;
+  if ((size_t)K * sizeof(bf16_t) > 64 * 1024) return CC_ERR_UNSUPPORTED;
+  GemvW4Args a{W, W3, reinterpret_cast<const uint32_t*>(qparams), reinterpret_cast<const uint32_t*>(qparams3), x, delta, norm_w, bias,
+               freqs, h_out, y, eps, N, K, gshift, freqs ? rope_rows : 0, freqs ? head_dim : 2};
+  return launch_gemv_w4(a, (hipStream_t)stream);
+}

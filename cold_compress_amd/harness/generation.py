@@ -526,17 +526,39 @@ def generate(model, prompt, prefill, decode_one_token, max_new_tokens, next_toke
 
 def load_model(checkpoint_path, device, precision, use_tp):
     """ref: generation_utils.py:534-566.  The shape is the CONFIGS entry named by the checkpoint's directory; a path naming int8
-    is a weight-only int8 checkpoint (harness/quantize.py), whose int8 buffers stay int8 through `.to(device, precision)`."""
+    is a weight-only int8 checkpoint (harness/quantize.py), whose int8 buffers stay int8 through `.to(device, precision)`.  A path
+    naming int4 is a weight-only int4 checkpoint, DIR/model_int4.gG.pth, G parsed from the name as the reference does; bf16 only.
+    Its codes stay uint8, and its (scale, zero) pairs are held per row from the load on.  Any failure to read, validate or shard
+    an int4 checkpoint raises ColdCompressError naming the path."""
     from pathlib import Path
 
     from .. import _abi
-    from .quantize import WeightOnlyInt8QuantHandler
+    from .quantize import WeightOnlyInt4QuantHandler, WeightOnlyInt8QuantHandler, check_int4_state_dict
 
     checkpoint_path = Path(checkpoint_path)
-    if "int4" in str(checkpoint_path):
-        raise _abi.ColdCompressError(f"{checkpoint_path}: int4 weight-only checkpoints are not supported (int8 weight-only is)")
+    int4 = "int4" in str(checkpoint_path)
+    if int4:
+        try:
+            groupsize = int(checkpoint_path.name.split(".")[-2][1:])
+        except (IndexError, ValueError):
+            raise _abi.ColdCompressError(f"{checkpoint_path}: an int4 checkpoint is named model_int4.gG.pth (G the groupsize)") from None
+        if precision != torch.bfloat16:
+            raise _abi.ColdCompressError(f"{checkpoint_path}: int4 weight-only models run in bfloat16 only, not {precision}")
     with torch.device("meta"):
         model = Transformer.from_name(checkpoint_path.parent.name)
+    if int4:
+        try:
+            model = WeightOnlyInt4QuantHandler(model, groupsize).convert_for_runtime()
+            checkpoint = torch.load(str(checkpoint_path), mmap=True, weights_only=True)
+            check_int4_state_dict(model, checkpoint)
+            model.load_state_dict(checkpoint, assign=True)
+            if use_tp:
+                from ..tp import apply_tp
+
+                apply_tp(model)
+        except Exception as e:
+            raise _abi.ColdCompressError(f"{checkpoint_path}: cannot load this int4 weight-only checkpoint: {e}") from e
+        return model.to(device=device, dtype=precision).eval()
     if "int8" in str(checkpoint_path):
         model = WeightOnlyInt8QuantHandler(model).convert_for_runtime()
     checkpoint = torch.load(str(checkpoint_path), mmap=True, weights_only=True)

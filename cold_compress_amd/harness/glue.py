@@ -70,26 +70,47 @@ def silu_mul(a, b):
 
 def gemv_supported(*weights):
     """Single-token dense layers on the device path: the input vector must fit the kernel's LDS staging buffer.  int8 weights
-    (weight-only int8 linears) stream through cc_gemv_fused_w8: 16-bit activations, K a multiple of 16."""
+    (weight-only int8 linears) stream through cc_gemv_fused_w8: 16-bit activations, K a multiple of 16.  uint8 weights (weight-only
+    int4 linears, two codes per byte: K = 2 * shape[1]) stream through cc_gemv_fused_w4: K a multiple of 32 (of the groupsize,
+    which the call checks)."""
     def ok(w):
         if not (w.is_cuda and w.is_contiguous()):
             return False
         if w.dtype == torch.int8:
             return w.shape[1] * 2 <= 64 * 1024 and w.shape[1] % 16 == 0
+        if w.dtype == torch.uint8:
+            return 2 * w.shape[1] * 2 <= 64 * 1024 and (2 * w.shape[1]) % 32 == 0
         return w.dtype in _DT and w.shape[1] * w.element_size() <= 64 * 1024 and w.shape[1] % (16 // w.element_size()) == 0
     return all(ok(w) for w in weights)
 
 
 def gemv_fused(weight, x, w3=None, delta=None, norm_weight=None, eps=1e-5, h_out=None, bias=None, freqs=None, rope_rows=0,
-               head_dim=0, scales=None, scales3=None):
+               head_dim=0, scales=None, scales3=None, groupsize=None):
     """One decode-time dense layer with its glue fused (cc_gemv_fused): optional RMSNorm(x + delta) prologue (h_out
     receives x + delta), optional SwiGLU pairing with `w3`, optional RoPE epilogue on the first `rope_rows` rows.
     x: [K] (any shape with K elements); returns [N] in the model dtype.
-    int8 `weight` (and `w3`): weight-only int8 with per-row `scales` (`scales3`) in x's dtype (cc_gemv_fused_w8)."""
+    int8 `weight` (and `w3`): weight-only int8 with per-row `scales` (`scales3`) in x's dtype (cc_gemv_fused_w8).
+    uint8 `weight` (and `w3`): weight-only int4, [N, K / 2] packed codes with `scales` (`scales3`) the bf16 (scale, zero) pairs
+    per row, [N, K / groupsize, 2], and bf16 activations (cc_gemv_fused_w4)."""
     N, K = weight.shape
     xc = x.contiguous()
     dc = delta.contiguous() if delta is not None else None
     fc = freqs.contiguous() if freqs is not None else None
+    if weight.dtype == torch.uint8:
+        K = 2 * K
+        if scales is None or groupsize is None or (w3 is not None and (w3.dtype != torch.uint8 or scales3 is None)):
+            raise _abi.ColdCompressError("gemv_fused: int4 weights need their (scale, zero) pairs and groupsize (and w3 uint8 with "
+                                         "scales3)")
+        if x.dtype != torch.bfloat16:
+            raise _abi.ColdCompressError(f"gemv_fused: int4 weights need bf16 activations, got {x.dtype}")
+        for t in (scales, scales3):
+            if t is not None and (t.dtype != torch.bfloat16 or not t.is_contiguous() or tuple(t.shape) != (N, K // groupsize, 2)):
+                raise _abi.ColdCompressError(f"gemv_fused: int4 (scale, zero) pairs must be contiguous bf16 [{N}, K / {groupsize}, 2] "
+                                             f"(K = {K}), got {t.dtype} {tuple(t.shape)}")
+        y = torch.empty((N,), dtype=torch.bfloat16, device=weight.device)
+        _abi.call("cc_gemv_fused_w4", _p(weight), _p(scales), _p(w3), _p(scales3), _p(xc), _p(dc), _p(norm_weight), float(eps), _p(h_out),
+                  _p(bias), _p(fc), int(rope_rows), int(head_dim), _p(y), N, K, int(groupsize), _DT[torch.bfloat16], _stream())
+        return y
     if weight.dtype == torch.int8:
         if scales is None or (w3 is not None and (w3.dtype != torch.int8 or scales3 is None)):
             raise _abi.ColdCompressError("gemv_fused: int8 weights need their per-row scales (and w3 int8 with scales3)")

@@ -97,9 +97,14 @@ def precompute_freqs_cis(seq_len, n_elem, base=10000, dtype=torch.bfloat16, rope
 
 
 
-def _scales(linear):
-    """The per-row scales of a weight-only int8 linear (harness/quantize.py), None for a dense one."""
-    return getattr(linear, "scales", None) if linear.weight.dtype == torch.int8 else None
+def _quant(linear, suffix=""):
+    """glue.gemv_fused's quantisation arguments for a weight-only linear (harness/quantize.py), none for a dense one: int8 its
+    per-row scales, int4 its per-row (scale, zero) pairs and groupsize.  suffix "3": the w3 of a SwiGLU pair."""
+    if linear.weight.dtype == torch.int8:
+        return {"scales" + suffix: linear.scales}
+    if linear.weight.dtype == torch.uint8:
+        return {"scales" + suffix: linear.scales_and_zeros, "groupsize": linear.groupsize}
+    return {}
 
 
 class RMSNorm(nn.Module):
@@ -126,8 +131,8 @@ class FeedForward(nn.Module):
         if fused is not None:
             delta, norm, h_out = fused
             g = glue.gemv_fused(self.w1.weight, x, w3=self.w3.weight, delta=delta, norm_weight=norm.weight, eps=norm.eps, h_out=h_out,
-                                scales=_scales(self.w1), scales3=_scales(self.w3))
-            return glue.gemv_fused(self.w2.weight, g, scales=_scales(self.w2)).view(1, 1, -1)
+                                **{**_quant(self.w1), **_quant(self.w3, "3")})
+            return glue.gemv_fused(self.w2.weight, g, **_quant(self.w2)).view(1, 1, -1)
         return self.w2(glue.silu_mul(self.w1(x), self.w3(x)))
 
 
@@ -164,14 +169,14 @@ class Attention(nn.Module):
             HQ, H, D = self.n_head, self.n_local_heads, self.head_dim
             cache = self.kv_cache
             if (self.fuse_qkv_step and self.fuse_decode_step and attn_top_k == 1.0 and D == 128 and hasattr(cache, "qkv_step_available")
-                    and self.wqkv.weight.dtype != torch.int8  # (the single-launch QKV step has no int8 form)
+                    and self.wqkv.weight.dtype not in (torch.int8, torch.uint8)  # (the single-launch QKV step has no int8 / int4 form)
                     and cache.supports_fused_step() and cache.qkv_step_available(HQ, x.shape[-1])):
                 # ONE launch for norm + wqkv + RoPE + update_kv + attention + update_state: the cache's K / V rows stream in the
                 # shadow of the projection's weights (q / k / v bit-identical to the two launches below)
                 y = cache.decode_step_qkv(self.wqkv.weight, self.wqkv.bias, x, delta, norm.weight, norm.eps, h_out, freqs_cis, input_pos, HQ)
-                return glue.gemv_fused(self.wo.weight, y).view(1, 1, -1)
+                return glue.gemv_fused(self.wo.weight, y, **_quant(self.wo)).view(1, 1, -1)
             qkv = glue.gemv_fused(self.wqkv.weight, x, delta=delta, norm_weight=norm.weight, eps=norm.eps, h_out=h_out,
-                                  bias=self.wqkv.bias, freqs=freqs_cis, rope_rows=(HQ + H) * D, head_dim=D, scales=_scales(self.wqkv))
+                                  bias=self.wqkv.bias, freqs=freqs_cis, rope_rows=(HQ + H) * D, head_dim=D, **_quant(self.wqkv))
             q = qkv[: HQ * D].view(1, HQ, 1, D)
             k = qkv[HQ * D: (HQ + H) * D].view(1, H, 1, D)
             v = qkv[(HQ + H) * D:].view(1, H, 1, D)
@@ -205,7 +210,7 @@ class Attention(nn.Module):
             cache.update_kv(input_pos, k, v, True, **ck)
             cache.update_state(input_pos, k, v, True, attn, **ck)
         if fused is not None:
-            return glue.gemv_fused(self.wo.weight, y, scales=_scales(self.wo)).view(1, 1, -1)
+            return glue.gemv_fused(self.wo.weight, y, **_quant(self.wo)).view(1, 1, -1)
         y = y.transpose(1, 2).contiguous().view(bsz, seqlen, self.dim)
         return self.wo(y)
 
@@ -257,7 +262,7 @@ class Transformer(nn.Module):
         """ref: model.py:191-233 — one cache + one prompt compressor per layer, each given only its relevant kwargs."""
         cache_strategy = kwargs.pop("cache_strategy")
         head_dim = self.config.dim // self.config.n_head
-        dtype = self.tok_embeddings.weight.dtype  # (the model dtype: an int8 weight-only LM head stores int8)
+        dtype = self.tok_embeddings.weight.dtype  # (the model dtype: a weight-only LM head stores int8 / uint8 codes)
         layerwise = {"max_cache_length", "recent_window", "prompt_compression_strategy"}
         for i, b in enumerate(self.layers):
             ctor, relevant = get_cache_constructor(cache_strategy=cache_strategy[i])
@@ -305,5 +310,5 @@ class Transformer(nn.Module):
                 and glue.gemv_supported(self.output.weight)):
             # final RMSNorm (with the last pending residual) fused into the streamed LM head
             return glue.gemv_fused(self.output.weight, x, delta=delta, norm_weight=self.norm.weight, eps=self.norm.eps,
-                                   scales=_scales(self.output)).view(1, 1, -1)
+                                   **_quant(self.output)).view(1, 1, -1)
         return self.output(self.norm(x, delta)[1])

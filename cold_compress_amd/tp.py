@@ -5,7 +5,9 @@ one-process-per-GPU `torch.distributed` where backend "nccl" IS RCCL on ROCm (gl
 What shards: wqkv column-wise per q/k/v block, wo/w2 row-wise, w1/w3 column-wise; KV heads
 and ALL per-head cache state shard with them (eviction needs no exchange); embeddings and the LM head are
 replicas.  Weight-only int8 linears (harness/quantize.py) shard like the reference's (tp.py:99-100): column-wise splits the
-weight rows and the per-row scales, row-wise splits the weight columns and keeps the scales whole; int4 is not supported.
+weight rows and the per-row scales, row-wise splits the weight columns and keeps the scales whole.  Weight-only int4 linears
+shard the same way: column-wise the packed code rows and the N axis of the (scale, zero) pairs (per q / k / v block for wqkv),
+row-wise the code columns (bytes) and the group axis, which needs the per-rank in_features to be a multiple of the groupsize.
 Two sum all-reduces per layer (after attention, after the FFN), issued in place on the ROCm stream.  At decode the messages are 2*dim bytes (8-16 KiB): latency-bound on xGMI, one RCCL call each.
 
 Unlike the reference, a rank may own a single KV head (Llama-3 70B at TP=8): the reference's
@@ -66,7 +68,8 @@ def _shard(x: torch.Tensor, dim: int, world: int, rank: int) -> torch.Tensor:
 
 
 def _apply_tp_linear(linear: nn.Linear, style: str, weight_splits: List[int] = ()) -> None:
-    """ref: tp.py:59-121 — dense and weight-only int8 linears (the int8 weight stays a buffer; its `scales` follow the rows)."""
+    """ref: tp.py:59-121 — dense and weight-only int8 / int4 linears (the quantised weight stays a buffer; int8 `scales` follow the
+    rows, int4 `scales_and_zeros` — held per row, [N, K / G, 2] — follow the rows or the groups)."""
     world, rank = _world_rank()
     dim, attr = {"colwise": (0, "out_features"), "rowwise": (1, "in_features")}[style]
     assert getattr(linear, attr) % world == 0
@@ -82,6 +85,18 @@ def _apply_tp_linear(linear: nn.Linear, style: str, weight_splits: List[int] = (
             linear.scales = split(linear.scales, 0).contiguous()
             if linear.bias is not None:
                 linear.bias = split(linear.bias, 0).contiguous()
+        setattr(linear, attr, getattr(linear, attr) // world)
+        return
+    if linear.weight.dtype == torch.uint8:  # weight-only int4: weight [N, K / 2] / scales_and_zeros [N, K / G, 2] / bias are buffers
+        if style == "rowwise" and (linear.in_features // world) % linear.groupsize:
+            from ._abi import ColdCompressError
+
+            raise ColdCompressError(f"int4 row-wise sharding over {world} ranks gives {linear.in_features // world} input features per "
+                                    f"rank, not a multiple of the groupsize {linear.groupsize}")
+        linear.weight = split(linear.weight, dim).contiguous()
+        linear.scales_and_zeros = split(linear.scales_and_zeros, dim).contiguous()
+        if style == "colwise" and linear.bias is not None:
+            linear.bias = split(linear.bias, 0).contiguous()
         setattr(linear, attr, getattr(linear, attr) // world)
         return
     linear.weight = nn.Parameter(split(linear.weight, dim).contiguous(), requires_grad=False)

@@ -769,6 +769,28 @@ int cc_gemv_fused_w8(const int8_t* W, const void* scales, const int8_t* W3, cons
                      const void* delta, const void* norm_w, float eps, void* h_out, const void* bias, const void* freqs,
                      int32_t rope_rows, int32_t head_dim, void* y, int32_t N, int32_t K, int32_t dtype, cc_stream_t stream);
 
+/* The same decode-time dense layer over INT4 GROUP-WISE WEIGHT-ONLY matrices (the reference's int4 weight-only mode, ref: quantize.py
+ * group_quantize_tensor / WeightOnlyInt4Linear, with this project's code layout): W, W3 uint8 [N, K / 2] row major, two 4-bit codes
+ * q in [0, 15] per byte, column 2j in the low nibble of byte j; qparams / qparams3 bf16 [N, K / groupsize, 2] row major, the
+ * (scale, zero) pair of each row and group of `groupsize` consecutive columns.  bf16 activations, bias, freqs and output.
+ *   quantisation (the checkpoint's, per group of w = bf16 weight, every step rounded to bf16): s = (max - min).clamp(min=1e-6) / 15,
+ *             z = min + s * 8, q = clamp(round((w - (z - s * 8)) / s), 0, 15).
+ *   prologue  exactly cc_gemv_fused's: h_out and the normalised input `in` are bit-identical to it.
+ *   product   p[n] = sum_k in[k] * ((q[n,k] - 8) * s + z), (s, z) the pair of k's group, the weight in fp32 (exact: the
+ *             reference's group_dequantize_tensor), fp32 accumulation; t[n] = bf16(p[n]); with bias t[n] = bf16(t[n] + bias[n]).
+ *   W3 != NULL (needs qparams3): t3 likewise, y = bf16(bf16(silu(t)) * t3); no bias.
+ *   freqs != NULL: RoPE on rows [0, rope_rows) of the rounded t, as cc_gemv_fused.
+ * The reference's backends do not round this product identically (CUDA tinygemm rounds each dequantised weight to bf16, the CPU
+ * kernel does not), so the contract is a tolerance class around p: the kernel's summation order is its own (group-factored,
+ * DESIGN §2.8) but fixed, and results are bit-reproducible from run to run and under graph replay.
+ * groupsize in {32, 64, 128, 256} (else CC_ERR_BAD_ARG).  dtype CC_DT_BF16 only (CC_DT_F16 / CC_DT_F32: CC_ERR_UNSUPPORTED).
+ * K % groupsize == 0 and K * 2 <= 64 KiB, else CC_ERR_UNSUPPORTED.  Arguments are validated before any launch: an error writes
+ * nothing. */
+int cc_gemv_fused_w4(const uint8_t* W, const void* qparams, const uint8_t* W3, const void* qparams3, const void* x,
+                     const void* delta, const void* norm_w, float eps, void* h_out, const void* bias, const void* freqs,
+                     int32_t rope_rows, int32_t head_dim, void* y, int32_t N, int32_t K, int32_t groupsize, int32_t dtype,
+                     cc_stream_t stream);
+
 /* Greedy sampling tail, ref: generation_utils.py:136-142: probs[V] = dtype(softmax_fp32(logits[V])),
  * *idx_out = first index of the largest rounded probability (torch.argmax semantics).  Two small launches; `workspace`
  * (cc_softmax_argmax_workspace_bytes) needs no initialisation. */

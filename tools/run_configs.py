@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """End-to-end runs of the SURVEY §8(d) configurations on the full Llama-3-8B shape (bf16, random weights): 8k/16k-token
 prompt prefilled through the HIP path, then hipGraph decode; prints decode tokens/s and the cache statistics per config.
---weights int8 quantises the model with the weight-only int8 handler (harness/quantize.py) first: decode streams int8 weights.
-    python tools/run_configs.py [--steps 32] [--weights bf16|int8]"""
+--weights int8 quantises the model with the weight-only int8 handler (harness/quantize.py) first: decode streams int8 weights;
+--weights int4 (--groupsize G, default 32) with the int4 group-wise handler: decode streams int4 weights.
+    python tools/run_configs.py [--steps 32] [--weights bf16|int8|int4] [--groupsize 32]"""
 import argparse
 import json
 import os
@@ -26,7 +27,7 @@ class Tok:
         return [5, 6, 7, 11, 13]
 
 
-def run(name, cache, prompt_len, steps, dev, weights="bf16"):
+def run(name, cache, prompt_len, steps, dev, weights="bf16", groupsize=32):
     cfg = dict(CONFIGS["Meta-Llama-3.1-8B-Instruct"])
     cfg["block_size"] = prompt_len + 2048 + 64
     torch.manual_seed(1234)
@@ -38,13 +39,14 @@ def run(name, cache, prompt_len, steps, dev, weights="bf16"):
         for n, p in model.named_parameters():
             p.fill_(1.0) if "norm" in n else p.normal_(0.0, 0.02, generator=g)
     model.eval()
-    if weights == "int8":
-        from cold_compress_amd.harness.quantize import WeightOnlyInt8QuantHandler
+    if weights in ("int8", "int4"):
+        from cold_compress_amd.harness.quantize import WeightOnlyInt4QuantHandler, WeightOnlyInt8QuantHandler
 
-        sd = WeightOnlyInt8QuantHandler(model).create_quantized_state_dict()
+        handler = (lambda m: WeightOnlyInt8QuantHandler(m)) if weights == "int8" else (lambda m: WeightOnlyInt4QuantHandler(m, groupsize))
+        sd = handler(model).create_quantized_state_dict()
         del model
         with torch.device("meta"):
-            model = WeightOnlyInt8QuantHandler(Transformer(ModelArgs(**cfg))).convert_for_runtime()
+            model = handler(Transformer(ModelArgs(**cfg))).convert_for_runtime()
         model.load_state_dict(sd, assign=True)
         model = model.to(device=dev, dtype=torch.bfloat16).eval()
         del sd
@@ -81,7 +83,7 @@ def run(name, cache, prompt_len, steps, dev, weights="bf16"):
         dt = time.perf_counter() - t0
     st = model.get_cache_stats(prompt_len, steps + 4)
     lens = sorted(set(int(x) for x in ck["max_cache_length"]))
-    print(json.dumps({"config": name, "weights": weights, "model_gb": round(model_gb, 3), "prompt": prompt_len, "cache_lengths": lens if len(lens) < 6 else [lens[0], "...", lens[-1]],
+    print(json.dumps({"config": name, "weights": weights if weights != "int4" else f"int4.g{groupsize}", "model_gb": round(model_gb, 3), "prompt": prompt_len, "cache_lengths": lens if len(lens) < 6 else [lens[0], "...", lens[-1]],
                       "prefill_s": round(tp, 2), "decode_tok_s": round(steps / dt, 1), "ms_per_token": round(dt / steps * 1e3, 3),
                       "compression_ratio_avg": round(st["compression_ratio_avg"], 4), "cache_memory_gb": round(st["cache_memory_gb"], 3)}),
           flush=True)
@@ -93,7 +95,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=32)
     ap.add_argument("--only", default=None)
-    ap.add_argument("--weights", default="bf16", choices=["bf16", "int8"])
+    ap.add_argument("--weights", default="bf16", choices=["bf16", "int8", "int4"])
+    ap.add_argument("--groupsize", type=int, default=32, choices=[32, 64, 128, 256])
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     cases = [
@@ -119,7 +122,7 @@ def main():
         if a.only and a.only not in name:
             continue
         try:
-            run(name, cache, pl, a.steps, dev, a.weights)
+            run(name, cache, pl, a.steps, dev, a.weights, a.groupsize)
         except Exception as e:  # keep going: this is a survey of configurations
             print(json.dumps({"config": name, "error": f"{type(e).__name__}: {e}"[:300]}), flush=True)
             torch.cuda.empty_cache()
