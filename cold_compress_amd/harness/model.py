@@ -18,6 +18,7 @@ import torch.nn as nn
 from torch import Tensor
 
 from . import glue
+from .._abi import ColdCompressError
 from ..attention_utils import scaled_dot_product_attention
 from ..cache import (KVCacheFull, KVCacheHeavyHitter, KVCacheHybrid, KVCacheL2, KVCacheRandom, KVCacheRecentGlobal, flush_quantized,
                      get_cache_constructor)
@@ -264,6 +265,14 @@ class Transformer(nn.Module):
         head_dim = self.config.dim // self.config.n_head
         dtype = self.tok_embeddings.weight.dtype  # (the model dtype: a weight-only LM head stores int8 / uint8 codes)
         layerwise = {"max_cache_length", "recent_window", "prompt_compression_strategy"}
+        quant_mode = kwargs.get("cache_quant_mode") or "reference"
+        R = self.config.n_head // self.config.n_local_heads
+        if quant_mode != "reference" and kwargs.get("cache_bits") is not None and R % 4:
+            # the decode kernels over quantised images process 4 or 8 query heads per pass (include/coldcompress.h): refuse here,
+            # where the query heads are known, rather than at the first decode token after a whole prefill
+            raise ColdCompressError(f"cache_quant_mode={quant_mode!r} serves 4, 8 or another multiple of 4 query heads per kv head; "
+                                    f"this model has {self.config.n_head} query heads over {self.config.n_local_heads} kv heads "
+                                    f"({R} per kv head)")
         for i, b in enumerate(self.layers):
             ctor, relevant = get_cache_constructor(cache_strategy=cache_strategy[i])
             lk = {k: kwargs[k][i] if k in layerwise else kwargs[k] for k in relevant}

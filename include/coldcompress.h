@@ -474,6 +474,8 @@ int cc_kv_dequant(const void* q, const void* scales, const void* zeros, void* wo
  *     dequantised values.  Only K and V become images: history ring, denominators, counters, window sums, positions, mask
  *     and the hybrid cache's counts and punctuation / special masks are the 16-bit caches' own.
  * qparams: float32 [H, S, 4] = (k_scale, k_min, v_scale, v_min) per (head, slot).
+ * Every image format serves a multiple of 4 query heads per kv head (HQ / H = 4, 8, 12, ...: 4 or 8 per pass); any other
+ * ratio (Qwen2's 7 among them) is CC_ERR_UNSUPPORTED with every cache buffer left untouched.
  * n_bit is the image FORMAT: 8 = the uint8 grid above; CC_QUANT_FP8_E4M3 = FP8 images (`cache_quant_mode="fp8"`);
  * CC_QUANT_UINT4 = 4-bit images (`cache_quant_mode="uint4"`); 4, 2 and anything else: CC_ERR_UNSUPPORTED, before any launch.
  * FP8 images: one OCP e4m3fn code per value (the `fn` encoding: no infinities, NaN = 0x7f / 0xff; not the `fnuz` one) and one

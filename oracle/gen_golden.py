@@ -20,6 +20,8 @@ Fixtures:
   f4_headconst.npz        KVCacheFull / KVCacheRecentGlobal / KVCacheKeepItOdd decode traces
   f5_compress.npz         prompt_compression.* priorities -> keep_idxs (+ boundary-tie flags)
   f7_attn_<dtype>.npz     attention_utils.scaled_dot_product_attention decode + small prefill
+  f7_attn_gqa_<dtype>.npz the same at 7 and 3 query heads per kv head (bf16, fp16)
+  f2_hh_query_r7_bf16.npz f2_hh_query at 7 query heads per kv head (H = 4, HQ = 28)
   f8_budgets.json         generation_utils budget arithmetic
   f8_budgets_random.json  the same arithmetic on 1000 random inputs (value, or the exception's type name)
   f8_setup_random.json    setup_caches on 80 random configurations: normalised keyword lists and per-layer cache / compressor classes
@@ -600,6 +602,35 @@ def attn_cases(A, dtype):
     return pack(out)
 
 
+def attn_gqa_cases(A, dtype):
+    """attention_utils.scaled_dot_product_attention at query-group ratios other than 4, driven as model.py:395-418
+    (repeat_interleave, masked decode, causal prefill, mean over the group): r7 = Qwen2's 7 query heads per kv head
+    (H = 4, D = 128), r3 = 3 per kv head (H = 2, D = 64)."""
+    gen = _gen(401 if dtype == torch.bfloat16 else 402)
+    out = {}
+    for tag, H, R, D, S, L in (("r7", 4, 7, 128, 77, 20), ("r3", 2, 3, 64, 150, 40)):
+        HQ = H * R
+        q = torch.randn(1, HQ, 1, D, generator=gen).to(dtype)
+        k = torch.randn(1, H, S, D, generator=gen).to(dtype)
+        v = torch.randn(1, H, S, D, generator=gen).to(dtype)
+        mask = torch.rand(1, H, 1, S, generator=gen) > 0.3
+        mask[..., -1] = True
+        y, p = A.scaled_dot_product_attention(q, k.repeat_interleave(R, 1), v.repeat_interleave(R, 1),
+                                              attn_mask=mask.repeat_interleave(R, 1), return_attn=True)
+        out.update({f"{tag}.dec.q": q, f"{tag}.dec.k": k, f"{tag}.dec.v": v, f"{tag}.dec.mask": mask, f"{tag}.dec.y": y,
+                    f"{tag}.dec.probs": p, f"{tag}.dec.attn_gm": p.view(1, H, R, 1, -1).mean(dim=2)})
+        q = torch.randn(1, HQ, L, D, generator=gen).to(dtype)
+        k = torch.randn(1, H, L, D, generator=gen).to(dtype)
+        v = torch.randn(1, H, L, D, generator=gen).to(dtype)
+        causal = torch.tril(torch.ones(L, L, dtype=torch.bool)).view(1, 1, L, L)
+        y, p = A.scaled_dot_product_attention(q, k.repeat_interleave(R, 1), v.repeat_interleave(R, 1),
+                                              attn_mask=causal, return_attn=True)
+        gm = p.view(1, H, R, L, -1).mean(dim=2)
+        out.update({f"{tag}.pre.q": q, f"{tag}.pre.k": k, f"{tag}.pre.v": v, f"{tag}.pre.y": y, f"{tag}.pre.attn_gm": gm,
+                    f"{tag}.pre.colsum": gm.sum(dim=2), f"{tag}.pre.obs_mean": gm[:, :, -16:, :].mean(dim=2)})
+    return pack(out)
+
+
 def attn_topk_case(A):
     """attention_utils.py:24-26, 45-50: top-k decode attention (L == 1, NO mask — with a mask the reference asserts)."""
     gen = _gen(9)
@@ -1003,6 +1034,9 @@ def main():
         if a.only == "f9":
             return
 
+    if a.only == "gqa":
+        gqa_fixtures(A, C, save)
+        return
     # F1: config C1 (README.md:103 of the reference) + companions on the same tiny model
     save("f1_e2e_recent_global.npz", run_e2e(C, G, M, "recent_global", dict(
         cache_strategy=["recent_global"], prompt_compression_strategy=["recent_global"], max_cache_length=[16],
@@ -1072,6 +1106,16 @@ def main():
     with open(os.path.join(a.out, "f8_budgets.json"), "w") as f:
         json.dump(budgets(G, M, C), f)
     print("wrote f8_budgets.json")
+    if a.only in (None, "gqa"):
+        gqa_fixtures(A, C, save)
+
+
+def gqa_fixtures(A, C, save):
+    """Query-group ratios other than 4 (written last: the families above keep their draws)."""
+    save("f7_attn_gqa_bf16.npz", attn_gqa_cases(A, torch.bfloat16))
+    save("f7_attn_gqa_f16.npz", attn_gqa_cases(A, torch.float16))
+    # Qwen2's 7 query heads per kv head, four kv heads; a shorter cache and trace than f2_hh_query_bf16 keep the file small
+    save("f2_hh_query_r7_bf16.npz", hh_query_case(A, C, torch.bfloat16, seed=203, H=4, R=7, S=96, T_prefill=88, steps=28))
 
 
 if __name__ == "__main__":

@@ -1,7 +1,8 @@
 """The reference's heavy-hitter decode driven FROM THE QUERY (tests/golden/f2_hh_query_bf16.npz, made by
 oracle/gen_golden.py::hh_query_case by importing the reference): update_kv -> repeat_interleave ->
 attention_utils.scaled_dot_product_attention(return_attn=True) -> mean over the group -> update_state, i.e.
-model.py:389-427 + cache.py:690-765, 160 steps, H = 2, HQ = 8, S = 256, D = 128, bf16.
+model.py:389-427 + cache.py:690-765, 160 steps, H = 2, HQ = 8, S = 256, D = 128, bf16 (and f2_hh_query_r7_bf16.npz: 28 steps,
+H = 4, HQ = 28, S = 96).
 
 Unlike the f2_hh_* traces (ready-made attention rows) this one ties the FUSED decode step — insert + attention + history
 in one pass, single launch and two launches — directly to the reference (VERDICT r2 "next" item 4), and the oracle's
@@ -22,7 +23,9 @@ import torch
 from helpers import from_np, load_golden, to_np
 
 BF16_ULP = 2.0 ** -8
-NAME = "f2_hh_query_bf16.npz"
+# H = 2, HQ = 8 (4 query heads per kv head), and Qwen2's geometry: H = 4, HQ = 28 (7 per kv head: several query-head blocks per kv head
+# in the decode grid, and the two-launch step — the single launch serves 4 or 8 query heads per kv head)
+NAMES = ["f2_hh_query_bf16.npz", "f2_hh_query_r7_bf16.npz"]
 
 
 def justified(f, t, h, mine, ref):
@@ -55,10 +58,11 @@ def y_close(y_mine, y_ref):
     return float((y_mine - y_ref).abs().max()) <= 1e-3 + 2 * BF16_ULP * float(y_ref.abs().max())
 
 
-def test_oracle_pipeline_on_reference_query_trace(oracle, audit):
+@pytest.mark.parametrize("name", NAMES)
+def test_oracle_pipeline_on_reference_query_trace(oracle, audit, name):
     """cc_decode_update_heavy_hitter_cpu + cc_decode_attn_gqa_cpu (history fused) against the reference's own pipeline."""
     o = oracle
-    f = load_golden(NAME)
+    f = load_golden(name)
     H, R, S, D, T, g, w, steps = f["H"], f["R"], f["S"], f["D"], f["T_prefill"], f["g"], f["w"], f["steps"]
     HQ, code, dtype = H * R, 1, torch.bfloat16
     st = dict(k=to_np(f["k_after_prefill"][0]), v=to_np(f["v_after_prefill"][0]), pos=f["pos_after_prefill"][0].numpy().astype(np.int32).copy(),
@@ -115,12 +119,14 @@ def test_oracle_pipeline_on_reference_query_trace(oracle, audit):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("name", NAMES)
 @pytest.mark.parametrize("single", [True, False])
-def test_fused_step_on_reference_query_trace(single, audit):
-    """KVCacheHeavyHitter.decode_step — single launch and two launches — replays the reference's query-driven trace."""
+def test_fused_step_on_reference_query_trace(single, audit, name):
+    """KVCacheHeavyHitter.decode_step — single launch and two launches — replays the reference's query-driven trace.  At 7 query
+    heads per kv head the single launch does not serve the shape: single=True must fall back to the two-launch step."""
     import cold_compress_amd.cache as cache
 
-    f = load_golden(NAME)
+    f = load_golden(name)
     H, R, S, D, T, g, w, steps = f["H"], f["R"], f["S"], f["D"], f["T_prefill"], f["g"], f["w"], f["steps"]
     HQ, dev = H * R, __import__("helpers").TEST_DEVICE
     cls, rk = cache.get_cache_constructor("heavy_hitter")
@@ -129,7 +135,7 @@ def test_fused_step_on_reference_query_trace(single, audit):
     with torch.device(dev):
         kv = cls(1, H, D, torch.bfloat16, **{x: kw[x] for x in rk})
     kv.single_launch = single
-    assert kv.single_launch_active(HQ) == single
+    assert kv.single_launch_active(HQ) == (single and R in (4, 8)), f"R = {R}: single launch {kv.single_launch_active(HQ)}"
     kv.k_cache.copy_(f["k_after_prefill"]); kv.v_cache.copy_(f["v_after_prefill"]); kv.pos.copy_(f["pos_after_prefill"])
     kv.mask.copy_(f["mask_after_prefill"]); kv.cache_cts.copy_(f["cts_after_prefill"]); kv.attn_history_num.copy_(f["num_after_prefill"])
     kv.attn_history_denom.copy_(f["denom_after_prefill"]); kv.attn_counter.copy_(f["counter_after_prefill"])

@@ -3,7 +3,9 @@
 the fused decode step (ONE launch where the shape allows it, two otherwise; all cases share one workspace and one set of epoch
 words) against update_kv -> attention -> update_state, every buffer bit for bit, y within one rounding of the model dtype; the
 history rings against their three-call form; the fused quantised cache against the 16-bit step on its dequantised values.
-    python tools/fuzz_step.py [--n 300] [--seed 0]"""
+    python tools/fuzz_step.py [--n 300] [--seed 0] [--ratios 3,5,6,7,12]
+`ratios` (query heads per kv head) replaces the step and hybrid-step families' draw of R; without it every draw is what it
+always was, so a seed names the same cases."""
 import argparse
 import os
 import random
@@ -18,12 +20,12 @@ from cold_compress_amd.attention_utils import scaled_dot_product_attention as sd
 DEV = "cuda"
 
 
-def one(rng, idx):
+def one(rng, idx, ratios=None):
     strategy = rng.choice(["heavy_hitter", "recent_global", "full", "random", "l2"])
     dtype = rng.choice([torch.bfloat16, torch.float16, torch.float32])
     D = rng.choice([16, 32, 64, 128, 128, 128])
     H = rng.choice([1, 2, 3, 8])
-    R = rng.choice([1, 2, 4, 8])
+    R = rng.choice(ratios or [1, 2, 4, 8])
     S = rng.choice([rng.randint(6, 40), rng.randint(41, 300), rng.randint(301, 3000), rng.choice([4096, 5000, 9000]),
                     rng.choice([8192, 12000, 18432]) if H == 8 else rng.randint(3001, 4096)])
     T = rng.choice([0, S, S, rng.randint(0, S)])
@@ -149,14 +151,14 @@ HYB_YAML = [{"strategy": "window", "recent_window": 0.1},
             {"strategy": "window_heavy_hitter", "heavy_hitter_frac": 0.5, "recent_window": 0.1}, {"strategy": "full"}]
 
 
-def one_hybrid_step(rng, idx):
+def one_hybrid_step(rng, idx, ratios=None):
     """KVCacheHybrid.decode_step (ONE launch where the shape allows it, two otherwise) against update_kv -> attention (ring update
     fused) -> update_state: every buffer bit for bit, y within one rounding; random per-head fill levels, policies, protection
     masks, punctuation tokens (3 ids or 100)."""
     dtype = rng.choice([torch.bfloat16, torch.float16])
     D = 128
     H = rng.choice([1, 2, 5, 8])
-    R = rng.choice([2, 4, 4, 8])
+    R = rng.choice(ratios or [2, 4, 4, 8])
     S = rng.choice([rng.randint(8, 200), rng.randint(201, 3000), rng.randint(3001, 4096), rng.choice([4100, 6000, 9000]),
                     18432 if H * R <= 32 else rng.randint(300, 2000)])
     strategies = rng.choice([HYB, HYB_YAML])
@@ -347,12 +349,18 @@ def main():
     ap.add_argument("--n", type=int, default=300)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--only", choices=["hybrid_step"], default=None, help="run one family of cases only")
+    ap.add_argument("--ratios", default=None, help="comma-separated query heads per kv head for the step and hybrid-step families "
+                    "(the ring and quantised families keep theirs)")
     a = ap.parse_args()
+    ratios = [int(x) for x in a.ratios.split(",")] if a.ratios else None
     rng = random.Random(a.seed)
     ran = bad = 0
     for i in range(a.n):
         try:
-            r = one_hybrid_step(rng, i) if a.only == "hybrid_step" else (one_hybrid_step(rng, i) if i % 8 == 4 else one_ring(rng, i)) if i % 4 == 0 else (one_quant(rng, i) if i % 4 == 1 else one(rng, i))
+            if ratios is not None:  # only the families that take a ratio list
+                r = one_hybrid_step(rng, i, ratios) if a.only == "hybrid_step" or i % 4 == 0 else one(rng, i, ratios)
+            else:
+                r = one_hybrid_step(rng, i) if a.only == "hybrid_step" else (one_hybrid_step(rng, i) if i % 8 == 4 else one_ring(rng, i)) if i % 4 == 0 else (one_quant(rng, i) if i % 4 == 1 else one(rng, i))
         except Exception as e:  # a crash is a finding too
             r = f"case {i}: {type(e).__name__}: {e}"
         if r is None:
