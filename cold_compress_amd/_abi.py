@@ -14,6 +14,7 @@ CC_OK = 0
 CC_DT_F32, CC_DT_BF16, CC_DT_F16 = 0, 1, 2
 CC_QUANT_FP8_E4M3 = 0x100 | 8  # image format of cache_quant_mode='fp8' (the n_bit argument of the fused-cache entry points)
 CC_QUANT_UINT4 = 0x200 | 4  # image format of cache_quant_mode='uint4': two 4-bit codes per byte
+CC_QUANT_MXFP4 = 0x300 | 4  # image format of cache_quant_mode='mxfp4': two e2m1 codes per byte, one e8m0 scale per 32 values
 CC_PRIO_F32, CC_PRIO_BF16, CC_PRIO_F16, CC_PRIO_I64 = 0, 1, 2, 3
 
 _HERE = os.path.dirname(os.path.abspath(__file__))

@@ -31,8 +31,9 @@ def add_extension_arguments(parser: argparse.ArgumentParser):
     --cache_quant_mode fused: with --cache_bits 8, uint8 images on a per-(head, slot) grid, dequantised inside the decode
     kernels — a different numerical contract (include/coldcompress.h); fp8: the same caches with OCP e4m3 images and one
     power-of-two scale per (head, slot) row; uint4: with --cache_bits 4, the uint8 grid with 15 steps, two codes per byte;
+    mxfp4: with --cache_bits 4, OCP MXFP4 images (e2m1 codes, one power-of-two scale per block of 32 channels);
     "reference" = cache.py:283-338 bit for bit."""
-    parser.add_argument("--cache_quant_mode", default="reference", choices=["reference", "fused", "fp8", "uint4"])
+    parser.add_argument("--cache_quant_mode", default="reference", choices=["reference", "fused", "fp8", "uint4", "mxfp4"])
 
 
 def add_cache_arguments(parser: argparse.ArgumentParser):
@@ -121,12 +122,13 @@ class KVCache(nn.Module):
         self.n_bit = self.cache_bits
         self.quantization_axis = 2
         # opt-in fused quantised cache (our extension, include/coldcompress.h): the decode kernels stream uint8 images
-        # ("fused"), FP8 e4m3 images ("fp8") or 4-bit images ("uint4"); quant_format is the image format the C ABI takes in its
+        # ("fused"), FP8 e4m3 images ("fp8") or 4-bit images ("uint4", "mxfp4"); quant_format is the image format the C ABI takes in its
         # n_bit argument
         mode = getattr(self, "cache_quant_mode", None) or "reference"
-        formats = {"fused": (8, 8), "fp8": (8, _abi.CC_QUANT_FP8_E4M3), "uint4": (4, _abi.CC_QUANT_UINT4)}  # mode -> (cache_bits, format)
+        formats = {"fused": (8, 8), "fp8": (8, _abi.CC_QUANT_FP8_E4M3), "uint4": (4, _abi.CC_QUANT_UINT4),
+                   "mxfp4": (4, _abi.CC_QUANT_MXFP4)}  # mode -> (cache_bits, format)
         if mode != "reference" and mode not in formats:
-            raise ColdCompressError(f"cache_quant_mode={mode!r}: 'reference', 'fused', 'fp8' or 'uint4'")
+            raise ColdCompressError(f"cache_quant_mode={mode!r}: 'reference', 'fused', 'fp8', 'uint4' or 'mxfp4'")
         self.fused_quant = self.quantize and mode in formats
         self.quant_format = formats[mode][1] if self.fused_quant else None
         self._fused_mode = mode if self.fused_quant else None  # (for messages)
@@ -149,7 +151,7 @@ class KVCache(nn.Module):
             self.register_buffer("k_cache", torch.zeros((1, n_heads, 0, head_dim), dtype=dtype))
             self.register_buffer("v_cache", torch.zeros((1, n_heads, 0, head_dim), dtype=dtype))
             # [1, H, S, D] bytes (4-bit: [1, H, S, D / 2], two codes per byte)
-            qshape = self.cache_shape if self.quant_format != _abi.CC_QUANT_UINT4 else (1, n_heads, S, head_dim // 2)
+            qshape = self.cache_shape if formats[mode][0] != 4 else (1, n_heads, S, head_dim // 2)
             self.register_buffer("k_cache_q", torch.zeros(qshape, dtype=torch.uint8))
             self.register_buffer("v_cache_q", torch.zeros(qshape, dtype=torch.uint8))
             # uint8 / 4-bit: (k_scale, k_min, v_scale, v_min); FP8: (2^e_k, 0, 2^e_v, 0)

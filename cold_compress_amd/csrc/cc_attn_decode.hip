@@ -552,7 +552,7 @@ static int launch_mfma_rt(const SplitArgs& a, int rt, dim3 grid, dim3 block, hip
   }
 }
 
-// the streaming pass over FP8 or 4-bit images (QB = kQbFp8 / kQbU4): the hybrid cache or the fused quantised cache, as for uint8
+// the streaming pass over FP8 or 4-bit images (QB = kQbFp8 / kQbU4 / kQbMx4): the hybrid cache or the fused quantised cache, as for uint8
 template <typename T, int QB>
 static int launch_mfma_img(const SplitArgs& a, const Plan& p, dim3 grid, dim3 block, hipStream_t st) {
   if (p.rt != 4 && p.rt != 8) return CC_ERR_UNSUPPORTED;
@@ -561,7 +561,7 @@ static int launch_mfma_img(const SplitArgs& a, const Plan& p, dim3 grid, dim3 bl
   return p.nw == 8 ? launch_mfma_rt<T, false, false, QB, 1, 8>(a, p.rt, grid, block, st) : launch_mfma_rt<T, false, false, QB, 1>(a, p.rt, grid, block, st);
 }
 
-// qb: the image format of the fused quantised cache (a.qparams != null): 8 = uint8, kQbFp8 = FP8, kQbU4 = 4-bit
+// qb: the image format of the fused quantised cache (a.qparams != null): 8 = uint8, kQbFp8 = FP8, kQbU4 = 4-bit, kQbMx4 = MXFP4
 template <typename T>
 static int launch_split(const SplitArgs& a, const Plan& p, int H, int R, int D, hipStream_t st, int qb = 8) {
   if constexpr (sizeof(T) == 2) {
@@ -576,6 +576,8 @@ static int launch_split(const SplitArgs& a, const Plan& p, int H, int R, int D, 
         rc = launch_mfma_img<T, kQbFp8>(a, p, grid, block, st);
       } else if (a.qparams != nullptr && qb == kQbU4) {  // 4-bit images
         rc = launch_mfma_img<T, kQbU4>(a, p, grid, block, st);
+      } else if (a.qparams != nullptr && qb == kQbMx4) {  // MXFP4 images
+        rc = launch_mfma_img<T, kQbMx4>(a, p, grid, block, st);
       } else if (a.qparams != nullptr && qb != 8) {
         return CC_ERR_UNSUPPORTED;
       } else if (a.qparams != nullptr && a.hyb.strategies != nullptr) {  // the hybrid cache over uint8 images
@@ -681,7 +683,8 @@ static int one_capacity(void (*kernel)(CC_LEAD_TYPES SplitArgs), int threads) {
 typedef void (*OneKernel)(CC_LEAD_TYPES SplitArgs);
 // The single-launch kernel that serves (query heads per kv head rt, tiles per wave nt, kind), or null.  kind: 0 = 16-bit cache
 // (heavy hitter / head-constant policies), 8 = fused quantised cache, -1 = l2, 200 = hybrid, 208 = hybrid over uint8 images;
-// kQbFp8 / 200 + kQbFp8 = the same two over FP8 images, kQbU4 / 200 + kQbU4 over 4-bit images (lean instantiations only: one_kernel_img).
+// kQbFp8 / 200 + kQbFp8 = the same two over FP8 images, kQbU4 / 200 + kQbU4 over 4-bit images, kQbMx4 / 200 + kQbMx4 over MXFP4 images (lean
+// instantiations only: one_kernel_img).
 // full: the instantiation with the measurement hooks and attn_out (bf16, rt = 4 only).  ONE table for the residency check and the launch.
 template <typename T, int QB>
 static OneKernel one_kernel_img(int rt, int nt, bool hyb, bool full, int nw) {
@@ -711,6 +714,7 @@ static OneKernel one_kernel(int rt, int nt, int kind, bool full, int nw = kNW) {
   if (nt < 1 || nt > kOneMaxTiles) return nullptr;
   if (kind == kQbFp8 || kind == 200 + kQbFp8) return one_kernel_img<T, kQbFp8>(rt, nt, kind != kQbFp8, full, nw);
   if (kind == kQbU4 || kind == 200 + kQbU4) return one_kernel_img<T, kQbU4>(rt, nt, kind != kQbU4, full, nw);
+  if (kind == kQbMx4 || kind == 200 + kQbMx4) return one_kernel_img<T, kQbMx4>(rt, nt, kind != kQbMx4, full, nw);
 #if CC_V_NW16
   if (nw == 16) return (rt == 4 && nt == 1 && kind == 0 && !full) ? decode_attn_split_mfma_kernel<T, 4, 16, false, true, false, 0, 1, 1, false> : nullptr;
 #endif
@@ -798,7 +802,7 @@ static OneKernel one_kernel_dt(int dtype, int rt, int nt, int kind, bool full, i
   return dtype == CC_DT_BF16 ? one_kernel<bf16_t>(rt, nt, kind, full, nw) : (dtype == CC_DT_F16 ? one_kernel<f16_t>(rt, nt, kind, full, nw) : nullptr);
 }
 // The XL2 instantiations (placement + L2-resident hand-off): single-tile steps of the plain 16-bit cache (kind 0), the fused
-// quantised cache (8; kQbFp8 / kQbU4 for FP8 / 4-bit images) and l2 (-1), 4 or 8 query heads per kv head, 4- or 8-wave workgroups; FULL for
+// quantised cache (8; kQbFp8 / kQbU4 / kQbMx4 for FP8 / 4-bit / MXFP4 images) and l2 (-1), 4 or 8 query heads per kv head, 4- or 8-wave workgroups; FULL for
 // bf16 / rt = 4 / kind 0 only.
 template <typename T>
 static OneKernel one_kernel_xl2(int rt, int nt, int kind, bool full, int nw) {
@@ -821,7 +825,7 @@ static OneKernel one_kernel_xl2(int rt, int nt, int kind, bool full, int nw) {
     if (rt == 8) return nt <= 4 ? CC_ONE_XM(8, false, 4) : (nt <= 8 ? CC_ONE_XM(8, false, 8) : CC_ONE_XM(8, false, 16));
     return nt <= 4 ? CC_ONE_XM(4, false, 4) : (nt <= 8 ? CC_ONE_XM(4, false, 8) : CC_ONE_XM(4, false, 16));
   }
-  if (kind != 0 && kind != 8 && kind != kQbFp8 && kind != kQbU4 && kind != -1) return nullptr;
+  if (kind != 0 && kind != 8 && kind != kQbFp8 && kind != kQbU4 && kind != kQbMx4 && kind != -1) return nullptr;
   if (full) {
     if constexpr (ElemTraits<T>::code != CC_DT_BF16) {
       return nullptr;
@@ -846,6 +850,10 @@ static OneKernel one_kernel_xl2(int rt, int nt, int kind, bool full, int nw) {
   if (kind == kQbU4) {
     if (nw == 8) return rt == 8 ? CC_ONE_X(8, 8, false, kQbU4, false) : CC_ONE_X(4, 8, false, kQbU4, false);
     return rt == 8 ? CC_ONE_X(8, 4, false, kQbU4, false) : CC_ONE_X(4, 4, false, kQbU4, false);
+  }
+  if (kind == kQbMx4) {
+    if (nw == 8) return rt == 8 ? CC_ONE_X(8, 8, false, kQbMx4, false) : CC_ONE_X(4, 8, false, kQbMx4, false);
+    return rt == 8 ? CC_ONE_X(8, 4, false, kQbMx4, false) : CC_ONE_X(4, 4, false, kQbMx4, false);
   }
   if (nw == 8) return rt == 8 ? CC_ONE_X(8, 8, true, 0, false) : CC_ONE_X(4, 8, true, 0, false);
   return rt == 8 ? CC_ONE_X(8, 4, true, 0, false) : CC_ONE_X(4, 4, true, 0, false);
@@ -948,13 +956,13 @@ int32_t cc_decode_step_single_launch(int32_t HQ, int32_t H, int32_t S, int32_t D
   return one_available(HQ, H, S, D, dtype, 0);
 }
 int32_t cc_decode_step_quant_single_launch(int32_t HQ, int32_t H, int32_t S, int32_t D, int32_t dtype, int32_t n_bit) {
-  return (n_bit == 8 || n_bit == kQbFp8 || n_bit == kQbU4) ? one_available(HQ, H, S, D, dtype, n_bit) : 0;
+  return (n_bit == 8 || n_bit == kQbFp8 || n_bit == kQbU4 || n_bit == kQbMx4) ? one_available(HQ, H, S, D, dtype, n_bit) : 0;
 }
 int32_t cc_decode_step_hybrid_single_launch(int32_t HQ, int32_t H, int32_t S, int32_t D, int32_t dtype) {
   return one_available(HQ, H, S, D, dtype, 200);
 }
 int32_t cc_decode_step_hybrid_quant_single_launch(int32_t HQ, int32_t H, int32_t S, int32_t D, int32_t dtype, int32_t n_bit) {
-  return (n_bit == 8 || n_bit == kQbFp8 || n_bit == kQbU4) ? one_available(HQ, H, S, D, dtype, 200 + n_bit) : 0;
+  return (n_bit == 8 || n_bit == kQbFp8 || n_bit == kQbU4 || n_bit == kQbMx4) ? one_available(HQ, H, S, D, dtype, 200 + n_bit) : 0;
 }
 int32_t cc_decode_step_l2_single_launch(int32_t HQ, int32_t H, int32_t S, int32_t D, int32_t dtype) {
   return one_available(HQ, H, S, D, dtype, -1);
@@ -1052,7 +1060,7 @@ struct FusedStep {
   unsigned long long rng_seed;  // policy 3 with rand_next == null: the in-kernel generator's seed
   int rng_on;
   const QkvIn* qkv;  // r5: the layer's QKV projection rides the step (q / k_new / v_new are null; single launch or CC_ERR_UNSUPPORTED)
-  int qb;  // with qparams: the image format, 8 (uint8), kQbFp8 (FP8) or kQbU4 (4-bit); 0 reads as 8
+  int qb;  // with qparams: the image format, 8 (uint8), kQbFp8 (FP8), kQbU4 (4-bit) or kQbMx4 (MXFP4); 0 reads as 8
 };
 // The W > 1 history ring folded into the combine pass (denom / counter travel as hh_denom / hh_counter).
 struct RingHistory {
@@ -1455,7 +1463,7 @@ static int decode_step_quant_impl(const cc_kv_view* c, float* qparams, int32_t n
   if (!cc_view_ok(c) || !qparams || !q || !k_new || !v_new || !input_pos || !next_key || !y || HQ <= 0 || HQ % c->H ||
       global_tokens < 0)
     return CC_ERR_BAD_ARG;
-  if (n_bit != 8 && n_bit != kQbFp8 && n_bit != kQbU4) return CC_ERR_UNSUPPORTED;
+  if (n_bit != 8 && n_bit != kQbFp8 && n_bit != kQbU4 && n_bit != kQbMx4) return CC_ERR_UNSUPPORTED;
   switch (policy) {
     case 1: if (!num || !denom || c->Hp != c->H) return CC_ERR_BAD_ARG; break;
     case 2: if (num || denom || c->Hp != 1 || global_tokens >= c->S) return CC_ERR_BAD_ARG; break;
@@ -1528,7 +1536,7 @@ int cc_decode_step_heavy_hitter_ring_quant(const cc_kv_view* c, float* qparams, 
                                            size_t workspace_bytes, cc_stream_t stream) {
   if (!cc_view_ok(c) || !qparams || !q || !k_new || !v_new || !input_pos || !next_key || !y || c->Hp != c->H || HQ <= 0 || HQ % c->H)
     return CC_ERR_BAD_ARG;
-  if (n_bit != 8 && n_bit != kQbFp8 && n_bit != kQbU4) return CC_ERR_UNSUPPORTED;
+  if (n_bit != 8 && n_bit != kQbFp8 && n_bit != kQbU4 && n_bit != kQbMx4) return CC_ERR_UNSUPPORTED;
   FusedStep fs{c, k_new, v_new, input_pos, reinterpret_cast<unsigned long long*>(next_key), global_tokens, recent_window, 5, nullptr,
                nullptr, nullptr, qparams};
   fs.qb = n_bit;
@@ -1537,7 +1545,7 @@ int cc_decode_step_heavy_hitter_ring_quant(const cc_kv_view* c, float* qparams, 
                    workspace, workspace_bytes, stream, 3, &fs, &rh);
 }
 
-// the hybrid step over a 16-bit cache (qparams == null) or over uint8 / FP8 / 4-bit images (the fused quantised cache; qb = the format)
+// the hybrid step over a 16-bit cache (qparams == null) or over uint8 / FP8 / 4-bit / MXFP4 images (the fused quantised cache; qb = the format)
 static int decode_step_hybrid_impl(const cc_kv_view* c, float* qparams, int qb, const void* q, const void* k_new, const void* v_new,
                                    const int32_t* input_pos, const int64_t* strategies, const int32_t* policy_table, int32_t n_policies,
                                    void* ring_num, int32_t* denom, int64_t* counter, int32_t W, uint64_t* wsum_acc, float* wsum,
@@ -1584,7 +1592,7 @@ int cc_decode_step_hybrid_quant_rc(const cc_kv_view* c, float* qparams, int32_t 
                                    uint64_t* next_key, int32_t* step_commit, int32_t global_tokens, int32_t HQ, float scale, void* y,
                                    void* attn_out, void* workspace, size_t workspace_bytes, cc_stream_t stream) {
   if (!qparams) return CC_ERR_BAD_ARG;
-  if (n_bit != 8 && n_bit != kQbFp8 && n_bit != kQbU4) return CC_ERR_UNSUPPORTED;
+  if (n_bit != 8 && n_bit != kQbFp8 && n_bit != kQbU4 && n_bit != kQbMx4) return CC_ERR_UNSUPPORTED;
   return decode_step_hybrid_impl(c, qparams, n_bit, q, k_new, v_new, input_pos, strategies, policy_table, n_policies, ring_num, denom, counter,
                                  W, wsum_acc, wsum, special_mask, punc_mask, token_id, punc_ids, n_punc_ids, num_special, num_punc,
                                  next_key, step_commit, global_tokens, HQ, scale, y, attn_out, workspace, workspace_bytes, stream);

@@ -885,17 +885,66 @@ __device__ __forceinline__ uint2 quant4_row16(uint4 raw, float2& par) {
   par = make_float2(sc, mn);
   return make_uint2(w, 0u);
 }
-// the image format QB's two operations (QB = 8: the uint8 grid; kQbFp8: FP8; kQbU4: 4-bit)
+// ---- the MXFP4 images (QB = kQbMx4, include/coldcompress.h): e2m1 codes, one e8m0 scale byte per block of 32 values; par.x = the
+// row's four scale bytes as a BIT PATTERN (byte b = block b; never used as a float), par.y = 0.  A lane's 8 values (chunk `chunk` of
+// the row) are ONE word as in the uint4 images and lie in block chunk >> 2: 4 x v_cvt_scalef32_pk_{bf16,f16}_fp4 (byte select
+// 0 .. 3), the hardware applies the block's power of two — FP8's instruction count at half its bytes
+constexpr int kQbMx4 = CC_QUANT_MXFP4;
+template <typename T>
+__device__ __forceinline__ uint4 dequant_mx4(uint2 raw, float2 par, int chunk) {
+  const float sc = cc_mx4_scale(__float_as_uint(par.x), chunk >> 2);
+  return make_uint4(cc_mx4_dequant2<T, 0>(raw.x, sc), cc_mx4_dequant2<T, 1>(raw.x, sc), cc_mx4_dequant2<T, 2>(raw.x, sc),
+                    cc_mx4_dequant2<T, 3>(raw.x, sc));
+}
+// MXFP4 codes of the 8 values of this lane (chunk `chunk` of its 16-lane row group's cache row): amax over the finite values of the
+// lane's block (its 4-lane group: two xor-shuffles), e = cc_mx4_block_exp(amax), codes of x * 2^-e (exact) by cc_mx4_code, low nibble
+// first; the four blocks' scale bytes are gathered into the row's word over the 16-lane group
+template <typename T>
+__device__ __forceinline__ uint2 quant_mx4_row16(uint4 raw, float2& par, int chunk) {
+  Vec16<T> v;
+  v.raw = raw;
+  float x[8];
+  v.unpack(x);
+  float am = 0.f;
+  int bad = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    am = fmaxf(am, cc_fp8_abs_finite(x[i]));
+    bad |= !__builtin_isfinite(x[i]);
+  }
+#pragma unroll
+  for (int off = 2; off > 0; off >>= 1) {
+    am = fmaxf(am, __shfl_xor(am, off, 16));
+    bad |= __shfl_xor(bad, off, 16);
+  }
+  const int e = cc_mx4_block_exp(am);
+  const float inv = __builtin_ldexpf(1.f, -e);
+  uint32_t w = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) w |= cc_mx4_code(x[i], inv) << (4 * i);
+  int sw = (int)(cc_mx4_scale_byte(e, bad != 0) << (8 * (chunk >> 2)));
+  sw |= __shfl_xor(sw, 4, 16);
+  sw |= __shfl_xor(sw, 8, 16);
+  par = make_float2(__uint_as_float((uint32_t)sw), 0.f);
+  return make_uint2(w, 0u);
+}
+// 4-bit formats: D / 2 bytes per row, one word per lane
+template <int QB>
+constexpr bool kQb4Bit = QB == kQbU4 || QB == kQbMx4;
+// the image format QB's two operations (QB = 8: the uint8 grid; kQbFp8: FP8; kQbU4: 4-bit integers; kQbMx4: MXFP4); chunk: which 8
+// values of the row the lane holds (the block-scaled format's only)
 template <typename T, int QB>
-__device__ __forceinline__ uint4 dequant_qb(uint2 raw, float2 par) {
+__device__ __forceinline__ uint4 dequant_qb(uint2 raw, float2 par, int chunk) {
   if constexpr (QB == kQbFp8) return dequant_fp8<T>(raw, par);
   else if constexpr (QB == kQbU4) return dequant4<T>(raw, par);
+  else if constexpr (QB == kQbMx4) return dequant_mx4<T>(raw, par, chunk);
   else return dequant8<T>(raw, par);
 }
 template <typename T, int QB>
-__device__ __forceinline__ uint2 quant_qb_row16(uint4 raw, float2& par) {
+__device__ __forceinline__ uint2 quant_qb_row16(uint4 raw, float2& par, int chunk) {
   if constexpr (QB == kQbFp8) return quant_fp8_row16<T>(raw, par);
   else if constexpr (QB == kQbU4) return quant4_row16<T>(raw, par);
+  else if constexpr (QB == kQbMx4) return quant_mx4_row16<T>(raw, par, chunk);
   else return quant8_row16<T>(raw, par);
 }
 
@@ -909,8 +958,8 @@ struct IntC {
 // 64 workgroups per kv head, every workgroup of the grid co-resident.  HYB: the per-head decision of KVCacheHybrid at the top of
 // the pass (two-launch form: candidates, ring and counts follow in the combine pass; with ONE: in the tail, on all lanes).
 // QB = 8: the fused quantised cache (uint8 images + per-row (scale, minimum)), dequantised on the way to the LDS slabs; QB = kQbFp8:
-// the same with FP8 images and a power-of-two scale per row; QB = kQbU4: 4-bit images, D / 2 bytes per row (dequant_qb /
-// quant_qb_row16 and the image's byte offsets are the only differences); with HYB the
+// the same with FP8 images and a power-of-two scale per row; QB = kQbU4 / kQbMx4: 4-bit images (integers on the row's grid / MXFP4),
+// D / 2 bytes per row (dequant_qb / quant_qb_row16 and the image's byte offsets are the only differences); with HYB the
 // hybrid cache's decision and bookkeeping are unchanged, only its insert writes the token's image and row parameters.
 // NSUB = 2 (multi-tile splits only): two tiles per wave and iteration, each with its own staging registers — the loads of a
 // tile go out two half-iterations ahead of their use instead of one (twice the bytes in flight per wave).
@@ -1009,7 +1058,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
   auto apply_lead = [&]() {};
 #endif
   static_assert(!(HYB && L2), "the hybrid decision rides the plain streaming pass or the single-launch step");
-  static_assert(QB == 0 || ((QB == 8 || QB == kQbFp8 || QB == kQbU4) && !L2 && !QKV),
+  static_assert(QB == 0 || ((QB == 8 || QB == kQbFp8 || QB == kQbU4 || QB == kQbMx4) && !L2 && !QKV),
                 "fused quantised cache: uint8, FP8 or 4-bit images, heavy hitter (W = 1 or the ring) / recent_global / random / hybrid");
   static_assert(NSUB == 1 || (NSUB == 2 && !ONE), "two tiles per iteration: the two-launch streaming pass only");
   static_assert(NT == 1 || (ONE && !L2 && (QB == 0 || HYB) && NSUB == 1),
@@ -1161,7 +1210,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
   int q0 = 0;
   const T* vh = nullptr;
   const uint8_t *kqb = nullptr, *vqh = nullptr;  // QB: byte images (a row is QRB bytes, a lane's 8-value chunk QCB) ...
-  constexpr int QRB = QB == kQbU4 ? D / 2 : D, QCB = QB == kQbU4 ? VEC / 2 : VEC;
+  constexpr int QRB = kQb4Bit<QB> ? D / 2 : D, QCB = kQb4Bit<QB> ? VEC / 2 : VEC;
   const float2* qpar = nullptr;                  // ... and the head's row parameters: [slot][0] = K pair, [1] = V pair
   bool has_mask = false;
   const uint8_t* mh = nullptr;
@@ -1219,11 +1268,11 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
     return make_uint2(v.x, v.y);
   };
   auto load_nt_qb = [&](const uint8_t* p) {  // QB: the QCB bytes of a lane's chunk
-    if constexpr (QB == kQbU4) return make_uint2(__builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p)), 0u);
+    if constexpr (kQb4Bit<QB>) return make_uint2(__builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p)), 0u);
     else return load_nt_u2(p);
   };
   auto store_qb = [](uint8_t* p, uint2 w) {  // QB: the insert's image store of a lane's chunk
-    if constexpr (QB == kQbU4) *reinterpret_cast<uint32_t*>(p) = w.x;
+    if constexpr (kQb4Bit<QB>) *reinterpret_cast<uint32_t*>(p) = w.x;
     else *reinterpret_cast<uint2*>(p) = w;
   };
   auto issue_k_rows = [&](TileRegs& R, int base) {
@@ -2254,8 +2303,8 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
       uint2 knq = make_uint2(0, 0), vnq = make_uint2(0, 0);
       float2 knp = make_float2(0.f, 0.f), vnp = make_float2(0.f, 0.f);
       if constexpr (QB) {  // by the inserting row group only; its operands were requested ahead of the tile, so this runs while the tile is in flight
-        knq = quant_qb_row16<T, QB>(qb_kn.raw, knp);
-        vnq = quant_qb_row16<T, QB>(qb_vn.raw, vnp);
+        knq = quant_qb_row16<T, QB>(qb_kn.raw, knp, c);
+        vnq = quant_qb_row16<T, QB>(qb_vn.raw, vnp, c);
         qb_ins_u = um;
       }
       if constexpr (DMA) {
@@ -2352,7 +2401,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
       } else
       if constexpr (QB) {  // slot c of tile row i holds chunk c ^ i; the inserted row's lane holds chunk c -> slot c ^ i
         const int i = 4 * g + u;
-        sm_k[wave][i][u == qb_ins_u ? ((c ^ i) & 15) : c] = dequant_qb<T, QB>(R.kq8[u], R.kpar[u]);
+        sm_k[wave][i][u == qb_ins_u ? ((c ^ i) & 15) : c] = dequant_qb<T, QB>(R.kq8[u], R.kpar[u], u == qb_ins_u ? c : ((c ^ i) & 15));
       } else {
         sm_k[wave][4 * g + u][c] = R.kk[u].raw;
       }
@@ -2436,7 +2485,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
     if constexpr (!DMA) {
 #pragma unroll
       for (int u = 0; u < U; u++)
-        sm_v[wave][4 * g + u][(c ^ (2 * ((4 * g + u) & 7))) & 15] = QB ? dequant_qb<T, QB>(R.vq8[u], R.vpar[u]) : R.vv[u].raw;
+        sm_v[wave][4 * g + u][(c ^ (2 * ((4 * g + u) & 7))) & 15] = QB ? dequant_qb<T, QB>(R.vq8[u], R.vpar[u], c) : R.vv[u].raw;
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();

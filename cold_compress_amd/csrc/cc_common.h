@@ -124,6 +124,45 @@ __device__ __forceinline__ uint32_t cc_fp8_dequant2(uint32_t w, float scale, boo
   }
 }
 
+// ------------------------------------------------------------------ MXFP4 (OCP e2m1, one e8m0 scale per 32 values) fused cache (CC_QUANT_MXFP4)
+// One power-of-two scale 2^e per block of 32 values: e = the smallest exponent with amax <= 6 * 2^e (amax = m * 2^k, m in [0.5, 1):
+// 6 = 0.75 * 2^3), clamped to [-120, 120]; -120 for an all-zero block.  No division; nothing finite saturates inside the clamp.
+__device__ __forceinline__ int cc_mx4_block_exp(float amax) {
+  if (!(amax > 0.f)) return -120;
+  int k;
+  const float m = frexpf(amax, &k);
+  const int e = m <= 0.75f ? k - 3 : k - 2;
+  return e < -120 ? -120 : (e > 120 ? 120 : e);
+}
+// the block's e8m0 scale byte: e + 127, or 0xff (e8m0's NaN) when the block holds a non-finite value
+__device__ __forceinline__ uint32_t cc_mx4_scale_byte(int e, bool nonfinite) { return nonfinite ? 0xffu : (uint32_t)(e + 127); }
+// e2m1 code (sign | magnitude on {0, 0.5, 1, 1.5, 2, 3, 4, 6}) of x * inv (inv = 2^-e: exact), round to nearest, ties to the even
+// mantissa (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4); past 6 (the clamp's end, +-inf): 6; NaN: 0
+// under its sign; -0 keeps its sign.  Spelled on the VALU: it runs once per inserted row.
+__device__ __forceinline__ uint32_t cc_mx4_code(float x, float inv) {
+  const float y = __builtin_fabsf(__fmul_rn(x, inv));
+  const uint32_t m = (uint32_t)(y > 0.25f) + (uint32_t)(y >= 0.75f) + (uint32_t)(y > 1.25f) + (uint32_t)(y >= 1.75f) +
+                     (uint32_t)(y > 2.5f) + (uint32_t)(y >= 3.5f) + (uint32_t)(y > 5.f);
+  return m | ((__float_as_uint(x) >> 28) & 8u);
+}
+// the scale operand of the decode: byte b of the row's word as a float's exponent field (2^(byte - 127); 0xff: +inf)
+__device__ __forceinline__ float cc_mx4_scale(uint32_t word, int block) { return __uint_as_float(((word >> (8 * block)) & 0xffu) << 23); }
+// two e2m1 codes (byte SEL of w: low nibble = the first value) -> two 16-bit values of T, times the scale operand's power of two:
+// v_cvt_scalef32_pk_{bf16,f16}_fp4.  One rounding of the exact product (bf16: exact for every scale byte 7 .. 247)
+template <typename T, int SEL>
+__device__ __forceinline__ uint32_t cc_mx4_dequant2(uint32_t w, float scale) {
+  static_assert(ElemTraits<T>::code == CC_DT_BF16 || ElemTraits<T>::code == CC_DT_F16, "MXFP4 images decode to a 16-bit dtype");
+  if constexpr (ElemTraits<T>::code == CC_DT_BF16) {
+    typedef __bf16 cc_bf16x2 __attribute__((ext_vector_type(2)));
+    const cc_bf16x2 r = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, SEL);
+    return __builtin_bit_cast(uint32_t, r);
+  } else {
+    typedef _Float16 cc_f16x2 __attribute__((ext_vector_type(2)));
+    const cc_f16x2 r = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, scale, SEL);
+    return __builtin_bit_cast(uint32_t, r);
+  }
+}
+
 // 16-byte vector of T, unpacked to floats
 template <typename T>
 struct Vec16 {

@@ -523,6 +523,58 @@ __global__ __launch_bounds__(256) void kv_dequant_rows_u4_kernel(const uint8_t* 
   }
 }
 
+// The same two conversions for MXFP4 images (CC_QUANT_MXFP4, include/coldcompress.h): e2m1 codes, two per byte, one e8m0 scale byte
+// per block of 32 values; D a multiple of 32, at most 128: the row's (up to four) scale bytes are one qparams word (word 0: K, word 2:
+// V; a bit pattern, not a float).  One wave per row; lane j owns byte j of the image (values 2j, 2j + 1; block j >> 4).  The helpers
+// are the decode kernels' own (cc_common.h), so the images and values are theirs bit for bit.
+template <typename T>
+__global__ __launch_bounds__(256) void kv_quant_rows_mx4_kernel(const T* k, const T* v, uint8_t* kq, uint8_t* vq, float* qparams,
+                                                               size_t rows, int D) {
+  const int lane = threadIdx.x & 63;
+  const size_t wid = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (wid >= 2 * rows) return;
+  const int which = wid >= rows ? 1 : 0;
+  const size_t row = which ? wid - rows : wid;
+  const T* src = (which ? v : k) + row * D;
+  uint8_t* dst = (which ? vq : kq) + row * (D / 2);
+  const bool on = lane < D / 2;
+  const float x0 = on ? ElemTraits<T>::load(src, 2 * lane) : 0.f, x1 = on ? ElemTraits<T>::load(src, 2 * lane + 1) : 0.f;
+  float am = fmaxf(cc_fp8_abs_finite(x0), cc_fp8_abs_finite(x1));
+  int bad = !__builtin_isfinite(x0) || !__builtin_isfinite(x1);
+#pragma unroll
+  for (int off = 8; off > 0; off >>= 1) {
+    am = fmaxf(am, __shfl_xor(am, off, 64));
+    bad |= __shfl_xor(bad, off, 64);
+  }
+  const int ex = cc_mx4_block_exp(am);
+  const float inv = __builtin_ldexpf(1.f, -ex);
+  if (on) dst[lane] = (uint8_t)(cc_mx4_code(x0, inv) | (cc_mx4_code(x1, inv) << 4));
+  int sw = (on && (lane & 15) == 0) ? (int)(cc_mx4_scale_byte(ex, bad != 0) << (8 * (lane >> 4))) : 0;
+  sw |= __shfl_xor(sw, 16, 64);
+  sw |= __shfl_xor(sw, 32, 64);
+  if (lane == 0) {
+    qparams[row * 4 + 2 * which] = __uint_as_float((uint32_t)sw);
+    qparams[row * 4 + 2 * which + 1] = 0.f;
+  }
+}
+
+// one thread per image word (8 values): the decode kernels' four conversions, byte select 0 .. 3
+template <typename T>
+__global__ __launch_bounds__(256) void kv_dequant_rows_mx4_kernel(const uint8_t* kq, const uint8_t* vq, const float* qparams, T* k, T* v,
+                                                                 size_t rows, int D) {
+  const size_t wpr = (size_t)D / 8, half = rows * wpr, total = 2 * half;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int which = i >= half ? 1 : 0;
+    const size_t j = which ? i - half : i;
+    const size_t row = j / wpr;
+    const int wi = (int)(j - row * wpr);
+    const uint32_t w = reinterpret_cast<const uint32_t*>(which ? vq : kq)[j];
+    const float sc = cc_mx4_scale(__float_as_uint(qparams[row * 4 + 2 * which]), wi >> 2);
+    reinterpret_cast<uint4*>(which ? v : k)[j] = make_uint4(cc_mx4_dequant2<T, 0>(w, sc), cc_mx4_dequant2<T, 1>(w, sc),
+                                                            cc_mx4_dequant2<T, 2>(w, sc), cc_mx4_dequant2<T, 3>(w, sc));
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -531,11 +583,20 @@ int cc_kv_quant_rows(const void* k, const void* v, int32_t H, int32_t S, int32_t
                      uint8_t* v_q, float* qparams, cc_stream_t stream) {
   CC_ENTRY();
   if (!k || !v || !k_q || !v_q || !qparams || H <= 0 || S <= 0 || D <= 0 || !cc_dt_ok(dtype)) return CC_ERR_BAD_ARG;
-  if (n_bit != 8 && !((n_bit == CC_QUANT_FP8_E4M3 || n_bit == CC_QUANT_UINT4) && cc_dt_size(dtype) == 2)) return CC_ERR_UNSUPPORTED;
+  if (n_bit != 8 && !((n_bit == CC_QUANT_FP8_E4M3 || n_bit == CC_QUANT_UINT4 || n_bit == CC_QUANT_MXFP4) && cc_dt_size(dtype) == 2)) return CC_ERR_UNSUPPORTED;
   if (n_bit == CC_QUANT_UINT4 && D % 2) return CC_ERR_BAD_ARG;
+  if (n_bit == CC_QUANT_MXFP4 && (D % 32 || D > 128)) return CC_ERR_BAD_ARG;
   const size_t rows = (size_t)H * S;
   const unsigned blocks = (unsigned)((2 * rows + 3) / 4);
   hipStream_t st = (hipStream_t)stream;
+  if (n_bit == CC_QUANT_MXFP4) {
+    if (dtype == CC_DT_BF16)
+      hipLaunchKernelGGL(kv_quant_rows_mx4_kernel<bf16_t>, dim3(blocks), dim3(256), 0, st, (const bf16_t*)k, (const bf16_t*)v, k_q, v_q, qparams, rows, D);
+    else
+      hipLaunchKernelGGL(kv_quant_rows_mx4_kernel<f16_t>, dim3(blocks), dim3(256), 0, st, (const f16_t*)k, (const f16_t*)v, k_q, v_q, qparams, rows, D);
+    CC_LAUNCH_CHECK();
+    return CC_OK;
+  }
   if (n_bit == CC_QUANT_UINT4) {
     if (dtype == CC_DT_BF16)
       hipLaunchKernelGGL(kv_quant_rows_u4_kernel<bf16_t>, dim3(blocks), dim3(256), 0, st, (const bf16_t*)k, (const bf16_t*)v, k_q, v_q, qparams, rows, D);
@@ -565,12 +626,21 @@ int cc_kv_dequant_rows(const uint8_t* k_q, const uint8_t* v_q, const float* qpar
                        int32_t n_bit, void* k_out, void* v_out, cc_stream_t stream) {
   CC_ENTRY();
   if (!k_q || !v_q || !qparams || !k_out || !v_out || H <= 0 || S <= 0 || D <= 0 || !cc_dt_ok(dtype)) return CC_ERR_BAD_ARG;
-  if (n_bit != 8 && !((n_bit == CC_QUANT_FP8_E4M3 || n_bit == CC_QUANT_UINT4) && cc_dt_size(dtype) == 2)) return CC_ERR_UNSUPPORTED;
+  if (n_bit != 8 && !((n_bit == CC_QUANT_FP8_E4M3 || n_bit == CC_QUANT_UINT4 || n_bit == CC_QUANT_MXFP4) && cc_dt_size(dtype) == 2)) return CC_ERR_UNSUPPORTED;
   if (n_bit == CC_QUANT_UINT4 && D % 2) return CC_ERR_BAD_ARG;
+  if (n_bit == CC_QUANT_MXFP4 && (D % 32 || D > 128)) return CC_ERR_BAD_ARG;
   const size_t rows = (size_t)H * S;
   size_t nb = (2 * rows * D + 255) / 256;
   if (nb > 8192) nb = 8192;
   hipStream_t st = (hipStream_t)stream;
+  if (n_bit == CC_QUANT_MXFP4) {
+    if (dtype == CC_DT_BF16)
+      hipLaunchKernelGGL(kv_dequant_rows_mx4_kernel<bf16_t>, dim3((unsigned)nb), dim3(256), 0, st, k_q, v_q, qparams, (bf16_t*)k_out, (bf16_t*)v_out, rows, D);
+    else
+      hipLaunchKernelGGL(kv_dequant_rows_mx4_kernel<f16_t>, dim3((unsigned)nb), dim3(256), 0, st, k_q, v_q, qparams, (f16_t*)k_out, (f16_t*)v_out, rows, D);
+    CC_LAUNCH_CHECK();
+    return CC_OK;
+  }
   if (n_bit == CC_QUANT_UINT4) {
     if (dtype == CC_DT_BF16)
       hipLaunchKernelGGL(kv_dequant_rows_u4_kernel<bf16_t>, dim3((unsigned)nb), dim3(256), 0, st, k_q, v_q, qparams, (bf16_t*)k_out, (bf16_t*)v_out, rows, D);

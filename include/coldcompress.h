@@ -455,9 +455,11 @@ int cc_kv_dequant(const void* q, const void* scales, const void* zeros, void* wo
 #define CC_QUANT_FP8_E4M3 (0x100 | 8)
 /* Image format of the fused quantised cache's 4-bit mode (the n_bit argument below): the uint8 grid with 15 steps, two codes per byte. */
 #define CC_QUANT_UINT4 (0x200 | 4)
+/* Image format of the fused quantised cache's MXFP4 mode (the n_bit argument below): OCP e2m1 codes, two per byte, one e8m0 scale per 32 values. */
+#define CC_QUANT_MXFP4 (0x300 | 4)
 
 /* ------------------------------------------------------------------------------------------------
- * FUSED quantised KV cache — opt-in (`cache_quant_mode="fused"`, or "fp8" / "uint4" below), a DIFFERENT numerical contract from the reference's
+ * FUSED quantised KV cache — opt-in (`cache_quant_mode="fused"`, or "fp8" / "uint4" / "mxfp4" below), a DIFFERENT numerical contract from the reference's
  * ("fuse dequant into the attention read instead of whole-cache round trips").
  * The reference (cache.py:283-338, quantization_utils.py:4-45) keeps ONE (scale, zero) per slot shared by all heads and
  * re-quantises the whole cache every step; its numbers are reproduced by cc_kv_requant above.  Here instead:
@@ -477,7 +479,8 @@ int cc_kv_dequant(const void* q, const void* scales, const void* zeros, void* wo
  * Every image format serves a multiple of 4 query heads per kv head (HQ / H = 4, 8, 12, ...: 4 or 8 per pass); any other
  * ratio (Qwen2's 7 among them) is CC_ERR_UNSUPPORTED with every cache buffer left untouched.
  * n_bit is the image FORMAT: 8 = the uint8 grid above; CC_QUANT_FP8_E4M3 = FP8 images (`cache_quant_mode="fp8"`);
- * CC_QUANT_UINT4 = 4-bit images (`cache_quant_mode="uint4"`); 4, 2 and anything else: CC_ERR_UNSUPPORTED, before any launch.
+ * CC_QUANT_UINT4 = 4-bit images (`cache_quant_mode="uint4"`); CC_QUANT_MXFP4 = MXFP4 images (`cache_quant_mode="mxfp4"`); 4, 2 and
+ * anything else: CC_ERR_UNSUPPORTED, before any launch.
  * FP8 images: one OCP e4m3fn code per value (the `fn` encoding: no infinities, NaN = 0x7f / 0xff; not the `fnuz` one) and one
  * power-of-two scale 2^e per (head, slot) row of K and of V; qparams holds (2^e_k, 0, 2^e_v, 0), so that buffers, loads and
  * workspace sizes are the uint8 format's:
@@ -496,8 +499,29 @@ int cc_kv_dequant(const void* q, const void* scales, const void* zeros, void* wo
  *       byte j of a row's D / 2-byte image holds q[2j] | q[2j + 1] << 4   (low nibble first, as the reference's pack_low_bit_tensor)
  *   Images are [H, S, D / 2] bytes, a quarter of the 16-bit cache.  16-bit model dtypes only (the converters return
  *   CC_ERR_UNSUPPORTED for fp32), even D.
- * cc_kv_quant_rows / cc_kv_dequant_rows convert whole caches ([H, S, D] model dtype <-> uint8 / FP8 / 4-bit images + qparams).
- * cc_decode_step_quant: c->k_cache / c->v_cache are the IMAGES [H, S, D] (4-bit: [H, S, D / 2]), c->dtype the MODEL dtype (of q, k_new,
+ * MXFP4 images (CC_QUANT_MXFP4): OCP microscaling FP4.  A row's D values are blocks of 32 consecutive channels (D = 128: four), each
+ * with its own power-of-two scale 2^e_b, stored as an e8m0 byte; the values are e2m1 codes (sign | magnitude on {0, 0.5, 1, 1.5, 2,
+ * 3, 4, 6}):
+ *       amax_b = max |x[d]| over the block's FINITE values;  amax_b = m * 2^k with m in [0.5, 1) (frexpf)
+ *       e_b    = m <= 0.75 ? k - 3 : k - 2   (the smallest e with amax_b <= 6 * 2^e; 6 = 0.75 * 2^3), clamped to [-120, 120];
+ *                e_b = -120 for an all-zero block.  (The OCP recipe's floor(log2 amax) - 2 lets (6, 8) * 2^e saturate; this rule does
+ *                not, and the image is a valid MXFP4 image all the same.)  Scale byte = e_b + 127.
+ *       code   = sign(x[d]) << 3 | e2m1 magnitude of |f32(x[d]) * 2^-e_b| (exact scaling), round to nearest, ties to the even
+ *                mantissa (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4); -0 keeps its sign; above 6 (only
+ *                where e_b was clamped at 120): 6
+ *       value  = T(e2m1(code) * 2^e_b)       (exact in bf16; in f16 one round to nearest even: +-inf from 65520 up, subnormals
+ *                rounded, +-0 below half the smallest subnormal)
+ *       a block that holds a non-finite value: scale byte 0xff (e8m0's NaN), e_b and the codes as above from the finite values
+ *                (+-inf: code 7 under its sign, NaN: code 0 under its sign); EVERY element of such a block decodes to the
+ *                quiet NaN the conversion instruction returns (bf16 0xffc0, f16 0xfe00), whatever its code
+ *       byte j of a row's D / 2-byte image holds code[2j] | code[2j + 1] << 4   (low nibble first, the uint4 images' order)
+ *   qparams keeps its shape: word 0 = K's four scale bytes (byte b = block b, little end first), word 2 = V's, words 1 and 3 zero.
+ *   They are BIT PATTERNS held in float32 storage, never used as floats (read them as int32).
+ *   The kernels decode with v_cvt_scalef32_pk_{bf16,f16}_fp4 (one byte = two values per instruction, the block's power of two applied
+ *   by the hardware: four instructions per 8 values) and encode the inserted token on the VALU.  Images are [H, S, D / 2] bytes.
+ *   16-bit model dtypes only (the converters return CC_ERR_UNSUPPORTED for fp32); D a multiple of 32, at most 128.
+ * cc_kv_quant_rows / cc_kv_dequant_rows convert whole caches ([H, S, D] model dtype <-> uint8 / FP8 / 4-bit / MXFP4 images + qparams).
+ * cc_decode_step_quant: c->k_cache / c->v_cache are the IMAGES [H, S, D] (4-bit and MXFP4: [H, S, D / 2]), c->dtype the MODEL dtype (of q, k_new,
  *   v_new, y, attn_out); 16-bit dtype, D == 128, HQ / H in {4, 8} (CC_ERR_UNSUPPORTED otherwise).
  *   policy: 1 = heavy hitter (num / denom / counter as in cc_decode_step_heavy_hitter, c->Hp == H),
  *           2 = recent_global / full (num = denom = NULL, c->Hp == 1), 3 = random (rand_next as in cc_decode_step_random).
@@ -524,7 +548,7 @@ int cc_decode_step_quant_rc(const cc_kv_view* c, float* qparams, int32_t n_bit, 
                             cc_stream_t stream, int32_t phases);
 int32_t cc_decode_step_quant_single_launch(int32_t HQ, int32_t H, int32_t S, int32_t D, int32_t dtype, int32_t n_bit);
 /* The same images for the two history-ring policies.  Arguments as cc_decode_step_heavy_hitter_ring / cc_decode_step_hybrid_rc, plus
- * qparams [H, S, 4] and n_bit (the format: 8, CC_QUANT_FP8_E4M3 or CC_QUANT_UINT4; others: CC_ERR_UNSUPPORTED, before any launch);
+ * qparams [H, S, 4] and n_bit (the format: 8, CC_QUANT_FP8_E4M3, CC_QUANT_UINT4 or CC_QUANT_MXFP4; others: CC_ERR_UNSUPPORTED, before any launch);
  * c->k_cache / c->v_cache are the images,
  * c->dtype the model dtype.  16-bit dtype, D == 128, HQ / H in {4, 8} (CC_ERR_UNSUPPORTED otherwise).
  * cc_decode_step_heavy_hitter_ring_quant (history_window_size W > 1): two launches, as in 16 bits — the streaming pass reads the

@@ -47,7 +47,7 @@ def timed(fn, n, iters=8, after=None):
     return ts[len(ts) // 2]
 
 
-QBITS = {"fused": 8, "fp8": 8, "uint4": 4}  # cache_quant_mode -> the cache_bits it serves
+QBITS = {"fused": 8, "fp8": 8, "uint4": 4, "mxfp4": 4}  # cache_quant_mode -> the cache_bits it serves
 
 
 def make(strategy, H, S, D, extra=None):
@@ -67,6 +67,10 @@ def make(strategy, H, S, D, extra=None):
         kv.v_cache_q.copy_(torch.randint(0, 256, kv.v_cache_q.shape, device=dev, dtype=torch.int32).to(torch.uint8))
         kv.kv_qparams[..., 0::2] = 6.4 / 15
         kv.kv_qparams[..., 1::2] = -3.2
+    elif getattr(kv, "fused_quant", False) and kv.quant_format == _abi.CC_QUANT_MXFP4:  # MXFP4 images: any code, block scales 2^-1
+        kv.k_cache_q.copy_(torch.randint(0, 256, kv.k_cache_q.shape, device=dev, dtype=torch.int32).to(torch.uint8))
+        kv.v_cache_q.copy_(torch.randint(0, 256, kv.v_cache_q.shape, device=dev, dtype=torch.int32).to(torch.uint8))
+        kv.kv_qparams.view(torch.int32)[..., 0::2] = 0x7E7E7E7E  # (bit patterns: four e8m0 bytes per row)
     elif getattr(kv, "fused_quant", False) and kv.quant_format != 8:  # FP8 images of N(0, 1) rows, scale 2^0
         kv.k_cache_q.copy_(torch.randn(kv.cache_shape, device=dev).to(torch.float8_e4m3fn).view(torch.uint8))
         kv.v_cache_q.copy_(torch.randn(kv.cache_shape, device=dev).to(torch.float8_e4m3fn).view(torch.uint8))
@@ -131,9 +135,10 @@ def main():
                     kv.prepare_decode(pos)
                 res["fused_step_us"] = round(timed(lambda i: caches[i % n_buf].decode_step(q, k1, k1, pos), n_buf, after=lambda: pos.add_(1)), 2)
             if strategy in ("heavy_hitter", "recent_global", "full", "random"):
-                # the opt-in fused quantised cache (cache_bits=8, cache_quant_mode="fused" / "fp8"; cache_bits=4, "uint4"): uint8, FP8
-                # or 4-bit images streamed, dequantised in registers
-                for key, mode in (("fused_quant8_step_us", "fused"), ("fused_fp8_step_us", "fp8"), ("fused_uint4_step_us", "uint4")):
+                # the opt-in fused quantised cache (cache_bits=8, cache_quant_mode="fused" / "fp8"; cache_bits=4, "uint4" / "mxfp4"):
+                # uint8, FP8, 4-bit or MXFP4 images streamed, dequantised in registers
+                for key, mode in (("fused_quant8_step_us", "fused"), ("fused_fp8_step_us", "fp8"), ("fused_uint4_step_us", "uint4"),
+                                  ("fused_mxfp4_step_us", "mxfp4")):
                     del caches
                     torch.cuda.empty_cache()
                     caches = [make(strategy, H, S, D, {"cache_bits": QBITS[mode], "cache_quant_mode": mode}) for _ in range(n_buf)]
@@ -147,8 +152,9 @@ def main():
                     kv.prepare_decode(pos)
                 res["fused_step_us"] = round(timed(lambda i: caches[i % n_buf].decode_step(q, k1, k1, pos, input_ids=ids), n_buf, after=lambda: pos.add_(1)), 2)
                 res["fused_one_launch"] = caches[0].single_launch_active(HQ)
-                # the hybrid step over uint8 images (cache_quant_mode="fused"), FP8 images ("fp8") and 4-bit images ("uint4")
-                for key, mode in (("fused_quant8", "fused"), ("fused_fp8", "fp8"), ("fused_uint4", "uint4")):
+                # the hybrid step over uint8 images (cache_quant_mode="fused"), FP8 images ("fp8"), 4-bit images ("uint4") and MXFP4
+                # images ("mxfp4")
+                for key, mode in (("fused_quant8", "fused"), ("fused_fp8", "fp8"), ("fused_uint4", "uint4"), ("fused_mxfp4", "mxfp4")):
                     del caches
                     torch.cuda.empty_cache()
                     caches = [make(strategy, H, S, D, {"cache_bits": QBITS[mode], "cache_quant_mode": mode}) for _ in range(n_buf)]
@@ -178,7 +184,8 @@ def main():
             n_w = max(4, min(n_buf, (900 << 20) // (H * S * (W * 2 + 2 * D * 2)) + 1))
             for key, extra in (("fused_step_us", {}), ("fused_quant8_step_us", {"cache_bits": 8, "cache_quant_mode": "fused"}),
                                ("fused_fp8_step_us", {"cache_bits": 8, "cache_quant_mode": "fp8"}),
-                               ("fused_uint4_step_us", {"cache_bits": 4, "cache_quant_mode": "uint4"})):
+                               ("fused_uint4_step_us", {"cache_bits": 4, "cache_quant_mode": "uint4"}),
+                               ("fused_mxfp4_step_us", {"cache_bits": 4, "cache_quant_mode": "mxfp4"})):
                 caches = [make("heavy_hitter", H, S, D, dict(extra, history_window_size=W)) for _ in range(n_w)]
                 for kv in caches:
                     kv.prepare_decode(pos)
