@@ -1,0 +1,329 @@
+// cc_gemv_mx4.hip — the MXFP4 weight-only counterpart of cc_gemv.hip / cc_gemv_w8.hip / cc_gemv_w4.hip: the same five decode-layer
+// forms (plain, RMSNorm(x + delta) prologue with h_out, SwiGLU pair, RoPE epilogue, bias) over W stored as uint8 [N, K / 2] (two OCP
+// e2m1 codes per byte, column 2j in the low nibble) with one e8m0 scale byte per row and block of 32 consecutive columns, held per row
+// as uint8 [N, K / 32] (harness/quantize.py WeightOnlyMxfp4Linear; W = e2m1(q) * 2^(byte - 127)).
+//
+// Layout: cc_gemv_w4.hip's.  One non-temporal 16-byte load per lane carries 32 codes, which is exactly one MX block, so a wave covers
+// a 1 KiB segment of a row (2048 weights) per load instruction and reads 64 contiguous scale bytes beside it, one per lane.  The four
+// waves of a workgroup split into WS waves per row (WS = 1, 2 or 4, from the segment count) and 4 / WS row groups; RB rows and CU
+// segments per wave are in flight together, and the FIRST tile's codes and scale bytes are requested before the input vector is
+// touched.
+//
+// Arithmetic: the scale byte moves into a float's exponent field (cc_mx4_scale's trick, on a byte) and is the scale operand of
+// v_cvt_scalef32_pk_bf16_fp4 (cc_mx4_dequant2): four conversions per code word give its eight scaled weights as bf16 pairs in column
+// order, exactly (code x 2^e is a bf16 value for every scale byte 7 .. 247), and four v_dot2_f32_bf16 multiply them against the input
+// pairs in natural order into the row's one fp32 accumulator.  Per chunk and row: 1 shift, 16 conversions, 16 dot2 for 16 weight
+// bytes, about 2 VALU operations per weight byte; no nibble masks, no re-pairing of x, no zero point, no per-chunk accumulator.
+//
+// The RMSNorm prologue runs in the 16-bit kernel's layout (8 elements per lane and chunk, the same chunk order, the same fp32
+// chains and the same LDS reduction): h_out and the normalised input are bit-identical to cc_gemv_fused's.  The normalised vector
+// is passed to the lanes that multiply it through LDS (K * 2 bytes, norm forms only).
+#include <cstdio>
+#include <cstdlib>
+
+#include "cc_common.h"
+#include "cc_gemv_core.h"
+
+namespace {
+
+struct GemvMx4Args {
+  const uint8_t* W;
+  const uint8_t* W3;      // second matrix of the SwiGLU pair, or null
+  const uint8_t* sc;      // [N, K / 32] e8m0 scale bytes: block c of row n is byte n * (K / 32) + c
+  const uint8_t* sc3;     // the same for W3
+  const void* x;          // [K] bf16
+  const void* delta;      // [K] pending residual, or null
+  const void* norm_w;     // [K] RMSNorm weight, or null (no norm prologue)
+  const void* bias;       // [N] or null
+  const void* freqs;      // [head_dim/2, 2] (cos, sin) of this position, or null
+  void* h_out;            // [K] x + delta, or null
+  void* y;                // [N]
+  float eps;
+  int N, K, rope_rows, head_dim;
+};
+
+constexpr int kMx4Threads = 256;
+constexpr int kMx4Waves = kMx4Threads / 64;
+
+__device__ __forceinline__ uint32_t nt_load_u8(const uint8_t* p) { return __builtin_nontemporal_load(p); }
+
+__device__ __forceinline__ float dot2_bf16(uint32_t a, uint32_t b, float acc) {
+  return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, a), __builtin_bit_cast(bf16x2_t, b), acc, false);
+}
+
+// acc += sum over the 8 codes of w (columns 8i .. 8i + 7 of a chunk) of e2m1(q) * scale * x; xv holds that word's inputs in
+// natural order, the pairs (x0, x1) .. (x6, x7), which is the order the conversion returns the weights in
+__device__ __forceinline__ float dot_mx4_word(uint32_t w, float scale, uint4 xv, float acc) {
+  acc = dot2_bf16(cc_mx4_dequant2<bf16_t, 0>(w, scale), xv.x, acc);
+  acc = dot2_bf16(cc_mx4_dequant2<bf16_t, 1>(w, scale), xv.y, acc);
+  acc = dot2_bf16(cc_mx4_dequant2<bf16_t, 2>(w, scale), xv.z, acc);
+  acc = dot2_bf16(cc_mx4_dequant2<bf16_t, 3>(w, scale), xv.w, acc);
+  return acc;
+}
+
+// one chunk (32 codes, one MX block) of a row; sb: the block's e8m0 byte, moved into a float's exponent field (2^(sb - 127))
+__device__ __forceinline__ float chunk_mx4(uint4 w, uint32_t sb, const uint4 (&xv)[4], float acc) {
+  const float scale = __uint_as_float(sb << 23);
+  acc = dot_mx4_word(w.x, scale, xv[0], acc);
+  acc = dot_mx4_word(w.y, scale, xv[1], acc);
+  acc = dot_mx4_word(w.z, scale, xv[2], acc);
+  return dot_mx4_word(w.w, scale, xv[3], acc);
+}
+
+template <bool SWIGLU, int RB, int CU, int XS, int WS>
+__global__ __launch_bounds__(kMx4Threads) void gemv_mx4_kernel(GemvMx4Args a) {
+  typedef bf16_t T;
+  constexpr int VEC = 8;             // bf16 elements per 16-byte chunk of the input
+  constexpr int RG = kMx4Waves / WS;  // row groups of a workgroup
+  constexpr int RW = RB * RG;        // rows per workgroup round (even: RoPE's pair partner is lane ^ 1)
+  static_assert(RW <= 64 && RW % 2 == 0, "rows per round");
+  extern __shared__ uint4 sm_in[];   // the normalised input, norm forms only (K / 8 chunks)
+  __shared__ float sm_red[kMx4Waves];
+  __shared__ float sm_part[kMx4Waves][2][RB];
+  const int K = a.K, N = a.N;
+  const int nch = K / 32;            // 16-byte code chunks (MX blocks) per row
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int ws = wave % WS, rg = wave / WS;
+  const int nseg = (nch + 63) / 64;
+  const int nstep = (nseg + WS - 1) / WS;  // segments per wave (<= XS, checked by the launcher)
+  const uint4* Wv = reinterpret_cast<const uint4*>(a.W);
+  const uint4* W3v = reinterpret_cast<const uint4*>(a.W3);
+  uint4 w[RB][CU], w3[RB][CU];
+  uint32_t q[RB][CU], q3[RB][CU];  // the chunks' scale bytes (127, i.e. 1.0, beside zero-filled codes)
+  auto issue = [&](int r0, int s0) {  // r0: this wave's first row
+#pragma unroll
+    for (int u = 0; u < CU; u++) {
+      const int c = ((s0 + u) * WS + ws) * 64 + lane;
+      const bool cin = (s0 + u < nstep) && c < nch;
+#pragma unroll
+      for (int r = 0; r < RB; r++) {
+        const bool in = cin && (r0 + r < N);
+        const size_t off = (size_t)(r0 + r) * nch + c;
+        w[r][u] = in ? nt_load(Wv + off) : make_uint4(0, 0, 0, 0);
+        q[r][u] = in ? nt_load_u8(a.sc + off) : 127u;
+        if (SWIGLU) {
+          w3[r][u] = in ? nt_load(W3v + off) : make_uint4(0, 0, 0, 0);
+          q3[r][u] = in ? nt_load_u8(a.sc3 + off) : 127u;
+        }
+      }
+    }
+  };
+  const int row_first = blockIdx.x * RW;  // < N (the launcher sizes the grid)
+  issue(row_first + rg * RB, 0);
+
+  // ---- the input vector: the lane keeps elements [32 c, 32 c + 32) of every chunk c = (j * WS + ws) * 64 + lane it multiplies
+  uint4 xv[XS][4];
+  if (a.norm_w != nullptr) {
+    // cc_gemv.hip's prologue, operation for operation: 8-element chunks c8 = (j * 4 + wave) * 64 + lane, the same sum-of-squares
+    // chain per lane, the same wave and workgroup reductions
+    const int nch8 = K / VEC;
+    const int nstep8 = ((nch8 + 63) / 64 + kMx4Waves - 1) / kMx4Waves;
+    const T* xg = reinterpret_cast<const T*>(a.x);
+    const T* dg = reinterpret_cast<const T*>(a.delta);
+    const T* wg = reinterpret_cast<const T*>(a.norm_w);
+    float ss = 0.f;
+    for (int j = 0; j < nstep8; j++) {
+      const int c = (j * kMx4Waves + wave) * 64 + lane;
+      if (c < nch8) {
+        Vec16<T> xl, dv;
+        float h[VEC];
+        xl.load(xg + (size_t)c * VEC);
+        xl.unpack(h);
+        if (dg != nullptr) {
+          float d[VEC];
+          dv.load(dg + (size_t)c * VEC);
+          dv.unpack(d);
+#pragma unroll
+          for (int e = 0; e < VEC; e++) h[e] = ElemTraits<T>::rnd(__fadd_rn(h[e], d[e]));  // model-dtype residual add
+        }
+#pragma unroll
+        for (int e = 0; e < VEC; e++) ss = fmaf(h[e], h[e], ss);
+        const uint4 hp = pack16<T>(h);
+        sm_in[c] = hp;
+        if (a.h_out != nullptr && blockIdx.x == 0) reinterpret_cast<uint4*>(a.h_out)[c] = hp;
+      }
+    }
+    ss = gv_wave_sum(ss);
+    if (lane == 0) sm_red[wave] = ss;
+    __syncthreads();
+    const float tot = (sm_red[0] + sm_red[1]) + (sm_red[2] + sm_red[3]);
+    const float rs = rsqrtf(tot / (float)K + a.eps);
+    for (int j = 0; j < nstep8; j++) {
+      const int c = (j * kMx4Waves + wave) * 64 + lane;
+      if (c < nch8) {  // (each lane rewrites only the chunks it wrote)
+        Vec16<T> hv, nv;
+        float h[VEC], wf[VEC], o[VEC];
+        hv.raw = sm_in[c];
+        nv.load(wg + (size_t)c * VEC);
+        hv.unpack(h);
+        nv.unpack(wf);
+#pragma unroll
+        for (int e = 0; e < VEC; e++) o[e] = ElemTraits<T>::rnd(__fmul_rn(ElemTraits<T>::rnd(cc_opaque_f32(__fmul_rn(h[e], rs))), wf[e]));
+        sm_in[c] = pack16<T>(o);
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < XS; j++) {
+      const int c = (j * WS + ws) * 64 + lane;
+      const bool in = j < nstep && c < nch;
+#pragma unroll
+      for (int i = 0; i < 4; i++) xv[j][i] = in ? sm_in[4 * c + i] : make_uint4(0, 0, 0, 0);
+    }
+  } else {
+    const uint4* xg = reinterpret_cast<const uint4*>(a.x);
+#pragma unroll
+    for (int j = 0; j < XS; j++) {
+      const int c = (j * WS + ws) * 64 + lane;
+      const bool in = j < nstep && c < nch;
+#pragma unroll
+      for (int i = 0; i < 4; i++) xv[j][i] = in ? xg[4 * c + i] : make_uint4(0, 0, 0, 0);
+    }
+  }
+
+  T* yo = reinterpret_cast<T*>(a.y);
+  bool first = true;
+  for (int r0 = row_first; r0 < N; r0 += gridDim.x * RW) {
+    const int rw0 = r0 + rg * RB;
+    float acc[RB], acc3[RB];
+#pragma unroll
+    for (int r = 0; r < RB; r++) acc[r] = acc3[r] = 0.f;
+#pragma unroll
+    for (int s0 = 0; s0 < XS; s0 += CU) {
+      if (s0 < nstep) {
+        if (!first) issue(rw0, s0);
+        first = false;
+#pragma unroll
+        for (int u = 0; u < CU; u++) {
+          const int j = s0 + u < XS ? s0 + u : XS - 1;  // beyond nstep the codes are zero-filled
+#pragma unroll
+          for (int r = 0; r < RB; r++) {
+            acc[r] = chunk_mx4(w[r][u], q[r][u], xv[j], acc[r]);
+            if (SWIGLU) acc3[r] = chunk_mx4(w3[r][u], q3[r][u], xv[j], acc3[r]);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < RB; r++) {
+      const float s = gv_wave_sum(acc[r]);
+      float s3 = 0.f;
+      if (SWIGLU) s3 = gv_wave_sum(acc3[r]);
+      if (lane == 0) {
+        sm_part[wave][0][r] = s;
+        if (SWIGLU) sm_part[wave][1][r] = s3;
+      }
+    }
+    __syncthreads();
+    if (wave == 0) {
+      const int l = lane < RW ? lane : 0;
+      const int g = l / RB, r = l % RB;
+      const int row = r0 + l;
+      const int rowc = row < N ? row : N - 1;
+      auto part = [&](int m) {  // the WS waves of row group g, in a fixed order
+        if (WS == 1) return sm_part[g][m][r];
+        if (WS == 2) return sm_part[2 * g][m][r] + sm_part[2 * g + 1][m][r];
+        return (sm_part[0][m][r] + sm_part[1][m][r]) + (sm_part[2][m][r] + sm_part[3][m][r]);
+      };
+      // t = bf16(p); with bias t = bf16(t + bias)
+      float s = ElemTraits<T>::rnd(cc_opaque_f32(part(0)));
+      if (a.bias != nullptr) s = ElemTraits<T>::rnd(cc_opaque_f32(__fadd_rn(s, ElemTraits<T>::load(reinterpret_cast<const T*>(a.bias), (size_t)rowc))));
+      if (SWIGLU) {
+        const float s3 = ElemTraits<T>::rnd(cc_opaque_f32(part(1)));
+        const float sl = ElemTraits<T>::rnd(__fdiv_rn(s, 1.0f + expf(-s)));  // F.silu -> dtype
+        s = __fmul_rn(sl, s3);
+      }
+      float out = s;
+      if (a.freqs != nullptr) {  // RoPE on the (even, odd) row pairs of the q / k heads, on the rounded t
+        const float other = gv_dpp<0xB1>(out);  // the pair partner lives in lane ^ 1 (r0 is even)
+        if (row < a.rope_rows) {
+          const int pr = (row % a.head_dim) >> 1;
+          const float c = ElemTraits<T>::load(reinterpret_cast<const T*>(a.freqs), (size_t)pr * 2);
+          const float sn = ElemTraits<T>::load(reinterpret_cast<const T*>(a.freqs), (size_t)pr * 2 + 1);
+          out = (row & 1) ? __fadd_rn(__fmul_rn(out, c), __fmul_rn(other, sn)) : __fsub_rn(__fmul_rn(out, c), __fmul_rn(other, sn));
+        }
+      }
+      if (lane < RW && row < N) ElemTraits<T>::store(yo, (size_t)row, cc_opaque_f32(out));
+    }
+    __syncthreads();  // sm_part is reused by the next row group
+  }
+}
+
+struct Mx4Cfg {
+  int rb, cu, cap;
+};
+
+// rows x segments in flight per wave, by segments per wave (nstep) and form; tools/bench_gemv_mx4.py measures them
+static Mx4Cfg pick_mx4_cfg(const GemvMx4Args& a, int nstep) {
+  static int env_rb = -1, env_cu = -1, env_cap = 2048;
+  if (env_rb < 0) {  // tuning hook: CC_GEMV_MX4_CFG="RB,CU[,max workgroups]"
+    env_rb = env_cu = 0;
+    if (const char* e = getenv("CC_GEMV_MX4_CFG")) sscanf(e, "%d,%d,%d", &env_rb, &env_cu, &env_cap);
+  }
+  if (env_rb > 0 && env_cu > 0) return {env_rb, env_cu, env_cap};
+  // the int4 kernel's choices (cc_gemv_w4.hip: the same bytes per row, the same loads in flight): fewer, longer-lived workgroups
+  // amortise the per-workgroup prologue
+  if (nstep <= 1) return a.W3 != nullptr ? Mx4Cfg{4, 1, 512} : Mx4Cfg{4, 1, 1024};
+  return a.W3 != nullptr ? Mx4Cfg{2, 2, 512} : Mx4Cfg{4, 2, 512};
+}
+
+template <bool SWIGLU, int RB, int CU, int XS, int WS>
+static void launch_mx4_cfg(const GemvMx4Args& a, hipStream_t st, int cap) {
+  constexpr int RW = RB * (kMx4Waves / WS);
+  int blocks = (a.N + RW - 1) / RW;
+  if (blocks > cap) blocks = cap;
+  const size_t lds = a.norm_w != nullptr ? (size_t)a.K * sizeof(bf16_t) : 0;
+  hipLaunchKernelGGL((gemv_mx4_kernel<SWIGLU, RB, CU, XS, WS>), dim3(blocks), dim3(kMx4Threads), lds, st, a);
+}
+
+static int launch_gemv_mx4(const GemvMx4Args& a, hipStream_t st) {
+  const int nseg = (a.K / 32 + 63) / 64;
+  const int ws = nseg >= 3 ? 4 : nseg;  // waves per row: a short row leaves no wave idle
+  const int nstep = (nseg + ws - 1) / ws;
+  const Mx4Cfg c = pick_mx4_cfg(a, nstep);
+  const int xs = nstep <= 1 ? 1 : nstep <= 2 ? 2 : 4;  // input chunks kept per lane
+  if (nstep > 4 || c.cu > xs || c.cap <= 0) return CC_ERR_UNSUPPORTED;
+  const int key = (a.W3 ? 100000 : 0) + ws * 10000 + xs * 1000 + c.rb * 10 + c.cu;
+#define MX4_CASE(SW, WS_, XS_, RB_, CU_) \
+  case (SW ? 100000 : 0) + WS_ * 10000 + XS_ * 1000 + RB_ * 10 + CU_: launch_mx4_cfg<SW, RB_, CU_, XS_, WS_>(a, st, c.cap); break;
+  switch (key) {
+    MX4_CASE(false, 1, 1, 2, 1) MX4_CASE(false, 1, 1, 4, 1) MX4_CASE(false, 1, 1, 8, 1)
+    MX4_CASE(false, 2, 1, 2, 1) MX4_CASE(false, 2, 1, 4, 1) MX4_CASE(false, 2, 1, 8, 1)
+    MX4_CASE(false, 4, 1, 2, 1) MX4_CASE(false, 4, 1, 4, 1) MX4_CASE(false, 4, 1, 8, 1)
+    MX4_CASE(false, 4, 2, 4, 1) MX4_CASE(false, 4, 2, 8, 1) MX4_CASE(false, 4, 2, 2, 2) MX4_CASE(false, 4, 2, 4, 2) MX4_CASE(false, 4, 2, 8, 2)
+    MX4_CASE(false, 4, 4, 2, 4) MX4_CASE(false, 4, 4, 4, 2) MX4_CASE(false, 4, 4, 8, 2) MX4_CASE(false, 4, 4, 4, 4)
+    MX4_CASE(true, 1, 1, 2, 1) MX4_CASE(true, 1, 1, 4, 1) MX4_CASE(true, 1, 1, 8, 1)
+    MX4_CASE(true, 2, 1, 2, 1) MX4_CASE(true, 2, 1, 4, 1) MX4_CASE(true, 2, 1, 8, 1)
+    MX4_CASE(true, 4, 1, 2, 1) MX4_CASE(true, 4, 1, 4, 1) MX4_CASE(true, 4, 1, 8, 1)
+    MX4_CASE(true, 4, 2, 2, 1) MX4_CASE(true, 4, 2, 4, 1) MX4_CASE(true, 4, 2, 2, 2) MX4_CASE(true, 4, 2, 4, 2)
+    MX4_CASE(true, 4, 4, 2, 2) MX4_CASE(true, 4, 4, 4, 2) MX4_CASE(true, 4, 4, 2, 4)
+    default: return CC_ERR_UNSUPPORTED;
+  }
+#undef MX4_CASE
+  CC_LAUNCH_CHECK();
+  return CC_OK;
+}
+
+}  // namespace
+
+static inline bool mx4_aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+extern "C" int cc_gemv_fused_mx4(const uint8_t* W, const uint8_t* scales, const uint8_t* W3, const uint8_t* scales3, const void* x,
+                                 const void* delta, const void* norm_w, float eps, void* h_out, const void* bias, const void* freqs,
+                                 int32_t rope_rows, int32_t head_dim, void* y, int32_t N, int32_t K, int32_t dtype, cc_stream_t stream) {
+  CC_ENTRY();
+  if (!W || !scales || !x || !y || N <= 0 || K <= 0 || !cc_dt_ok(dtype)) return CC_ERR_BAD_ARG;
+  if ((W3 != nullptr) != (scales3 != nullptr)) return CC_ERR_BAD_ARG;
+  if ((delta || h_out) && !norm_w) return CC_ERR_BAD_ARG;
+  if (freqs && (W3 || rope_rows < 0 || rope_rows > N || head_dim <= 0 || (head_dim & 1) || (rope_rows % head_dim))) return CC_ERR_BAD_ARG;
+  if (W3 && bias) return CC_ERR_BAD_ARG;
+  // 16-byte vector accesses to the codes, the input vector and the prologue's operands; 2-byte elements elsewhere (null: aligned)
+  if (!mx4_aligned(W, 16) || !mx4_aligned(W3, 16) || !mx4_aligned(x, 16) || !mx4_aligned(delta, 16) || !mx4_aligned(norm_w, 16) ||
+      !mx4_aligned(h_out, 16) || !mx4_aligned(bias, 2) || !mx4_aligned(freqs, 2) || !mx4_aligned(y, 2))
+    return CC_ERR_BAD_ARG;
+  if (dtype != CC_DT_BF16) return CC_ERR_UNSUPPORTED;  // bf16 models only
+  if (K % 32) return CC_ERR_UNSUPPORTED;               // whole MX blocks
+  if ((size_t)K * sizeof(bf16_t) > 64 * 1024) return CC_ERR_UNSUPPORTED;
+  GemvMx4Args a{W, W3, scales, scales3, x, delta, norm_w, bias, freqs, h_out, y, eps, N, K, freqs ? rope_rows : 0, freqs ? head_dim : 2};
+  return launch_gemv_mx4(a, (hipStream_t)stream);
+}

@@ -529,13 +529,32 @@ def load_model(checkpoint_path, device, precision, use_tp):
     is a weight-only int8 checkpoint (harness/quantize.py), whose int8 buffers stay int8 through `.to(device, precision)`.  A path
     naming int4 is a weight-only int4 checkpoint, DIR/model_int4.gG.pth, G parsed from the name as the reference does; bf16 only.
     Its codes stay uint8, and its (scale, zero) pairs are held per row from the load on.  Any failure to read, validate or shard
-    an int4 checkpoint raises ColdCompressError naming the path."""
+    an int4 checkpoint raises ColdCompressError naming the path.  A path naming mxfp4 is a weight-only MXFP4 checkpoint
+    (DIR/model_mxfp4.pth): bf16 only, its codes and e8m0 scale bytes stay uint8, and any failure raises ColdCompressError naming the
+    path likewise."""
     from pathlib import Path
 
     from .. import _abi
-    from .quantize import WeightOnlyInt4QuantHandler, WeightOnlyInt8QuantHandler, check_int4_state_dict
+    from .quantize import (WeightOnlyInt4QuantHandler, WeightOnlyInt8QuantHandler, WeightOnlyMxfp4QuantHandler, check_int4_state_dict,
+                           check_mxfp4_state_dict)
 
     checkpoint_path = Path(checkpoint_path)
+    if "mxfp4" in str(checkpoint_path):
+        if precision != torch.bfloat16:
+            raise _abi.ColdCompressError(f"{checkpoint_path}: MXFP4 weight-only models run in bfloat16 only, not {precision}")
+        try:
+            with torch.device("meta"):
+                model = WeightOnlyMxfp4QuantHandler(Transformer.from_name(checkpoint_path.parent.name)).convert_for_runtime()
+            checkpoint = torch.load(str(checkpoint_path), mmap=True, weights_only=True)
+            check_mxfp4_state_dict(model, checkpoint)
+            model.load_state_dict(checkpoint, assign=True)
+            if use_tp:
+                from ..tp import apply_tp
+
+                apply_tp(model)
+        except Exception as e:
+            raise _abi.ColdCompressError(f"{checkpoint_path}: cannot load this mxfp4 weight-only checkpoint: {e}") from e
+        return model.to(device=device, dtype=precision).eval()
     int4 = "int4" in str(checkpoint_path)
     if int4:
         try:

@@ -72,7 +72,7 @@ def gemv_supported(*weights):
     """Single-token dense layers on the device path: the input vector must fit the kernel's LDS staging buffer.  int8 weights
     (weight-only int8 linears) stream through cc_gemv_fused_w8: 16-bit activations, K a multiple of 16.  uint8 weights (weight-only
     int4 linears, two codes per byte: K = 2 * shape[1]) stream through cc_gemv_fused_w4: K a multiple of 32 (of the groupsize,
-    which the call checks)."""
+    which the call checks) or, MXFP4 linears, through cc_gemv_fused_mx4: the same bound."""
     def ok(w):
         if not (w.is_cuda and w.is_contiguous()):
             return False
@@ -91,11 +91,28 @@ def gemv_fused(weight, x, w3=None, delta=None, norm_weight=None, eps=1e-5, h_out
     x: [K] (any shape with K elements); returns [N] in the model dtype.
     int8 `weight` (and `w3`): weight-only int8 with per-row `scales` (`scales3`) in x's dtype (cc_gemv_fused_w8).
     uint8 `weight` (and `w3`): weight-only int4, [N, K / 2] packed codes with `scales` (`scales3`) the bf16 (scale, zero) pairs
-    per row, [N, K / groupsize, 2], and bf16 activations (cc_gemv_fused_w4)."""
+    per row, [N, K / groupsize, 2], and bf16 activations (cc_gemv_fused_w4).
+    uint8 `weight` with uint8 `scales` and no groupsize: weight-only MXFP4, [N, K / 2] packed e2m1 codes with `scales` (`scales3`)
+    the e8m0 block-scale bytes, [N, K / 32], and bf16 activations (cc_gemv_fused_mx4)."""
     N, K = weight.shape
     xc = x.contiguous()
     dc = delta.contiguous() if delta is not None else None
     fc = freqs.contiguous() if freqs is not None else None
+    if weight.dtype == torch.uint8 and groupsize is None and (scales is None or scales.dtype == torch.uint8):  # MXFP4 (before int4)
+        K = 2 * K
+        if scales is None or (w3 is not None and (w3.dtype != torch.uint8 or scales3 is None)):
+            raise _abi.ColdCompressError("gemv_fused: uint8 weights need their scales: MXFP4 its uint8 block scales (and w3 uint8 with "
+                                         "scales3), int4 its (scale, zero) pairs and groupsize")
+        if x.dtype != torch.bfloat16:
+            raise _abi.ColdCompressError(f"gemv_fused: MXFP4 weights need bf16 activations, got {x.dtype}")
+        for t in (scales, scales3):
+            if t is not None and (t.dtype != torch.uint8 or not t.is_contiguous() or tuple(t.shape) != (N, K // 32)):
+                raise _abi.ColdCompressError(f"gemv_fused: MXFP4 block scales must be contiguous uint8 [{N}, K / 32] (K = {K}), got "
+                                             f"{t.dtype} {tuple(t.shape)}")
+        y = torch.empty((N,), dtype=torch.bfloat16, device=weight.device)
+        _abi.call("cc_gemv_fused_mx4", _p(weight), _p(scales), _p(w3), _p(scales3), _p(xc), _p(dc), _p(norm_weight), float(eps),
+                  _p(h_out), _p(bias), _p(fc), int(rope_rows), int(head_dim), _p(y), N, K, _DT[torch.bfloat16], _stream())
+        return y
     if weight.dtype == torch.uint8:
         K = 2 * K
         if scales is None or groupsize is None or (w3 is not None and (w3.dtype != torch.uint8 or scales3 is None)):

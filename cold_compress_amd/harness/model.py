@@ -100,7 +100,10 @@ def precompute_freqs_cis(seq_len, n_elem, base=10000, dtype=torch.bfloat16, rope
 
 def _quant(linear, suffix=""):
     """glue.gemv_fused's quantisation arguments for a weight-only linear (harness/quantize.py), none for a dense one: int8 its
-    per-row scales, int4 its per-row (scale, zero) pairs and groupsize.  suffix "3": the w3 of a SwiGLU pair."""
+    per-row scales, int4 its per-row (scale, zero) pairs and groupsize, MXFP4 its e8m0 block-scale bytes (uint8 codes like int4's:
+    told apart by the module's buffer, before the int4 branch).  suffix "3": the w3 of a SwiGLU pair."""
+    if linear.weight.dtype == torch.uint8 and hasattr(linear, "block_scales"):
+        return {"scales" + suffix: linear.block_scales}
     if linear.weight.dtype == torch.int8:
         return {"scales" + suffix: linear.scales}
     if linear.weight.dtype == torch.uint8:
@@ -170,7 +173,7 @@ class Attention(nn.Module):
             HQ, H, D = self.n_head, self.n_local_heads, self.head_dim
             cache = self.kv_cache
             if (self.fuse_qkv_step and self.fuse_decode_step and attn_top_k == 1.0 and D == 128 and hasattr(cache, "qkv_step_available")
-                    and self.wqkv.weight.dtype not in (torch.int8, torch.uint8)  # (the single-launch QKV step has no int8 / int4 form)
+                    and self.wqkv.weight.dtype not in (torch.int8, torch.uint8)  # (the single-launch QKV step has no int8 / int4 / MXFP4 form)
                     and cache.supports_fused_step() and cache.qkv_step_available(HQ, x.shape[-1])):
                 # ONE launch for norm + wqkv + RoPE + update_kv + attention + update_state: the cache's K / V rows stream in the
                 # shadow of the projection's weights (q / k / v bit-identical to the two launches below)

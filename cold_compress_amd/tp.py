@@ -8,6 +8,8 @@ replicas.  Weight-only int8 linears (harness/quantize.py) shard like the referen
 weight rows and the per-row scales, row-wise splits the weight columns and keeps the scales whole.  Weight-only int4 linears
 shard the same way: column-wise the packed code rows and the N axis of the (scale, zero) pairs (per q / k / v block for wqkv),
 row-wise the code columns (bytes) and the group axis, which needs the per-rank in_features to be a multiple of the groupsize.
+Weight-only MXFP4 linears likewise: column-wise the code rows and the rows of the e8m0 block scales, row-wise the code columns
+(bytes) and the scale columns, which needs the per-rank in_features to be a multiple of the block of 32.
 Two sum all-reduces per layer (after attention, after the FFN), issued in place on the ROCm stream.  At decode the messages are 2*dim bytes (8-16 KiB): latency-bound on xGMI, one RCCL call each.
 
 Unlike the reference, a rank may own a single KV head (Llama-3 70B at TP=8): the reference's
@@ -85,6 +87,18 @@ def _apply_tp_linear(linear: nn.Linear, style: str, weight_splits: List[int] = (
             linear.scales = split(linear.scales, 0).contiguous()
             if linear.bias is not None:
                 linear.bias = split(linear.bias, 0).contiguous()
+        setattr(linear, attr, getattr(linear, attr) // world)
+        return
+    if linear.weight.dtype == torch.uint8 and hasattr(linear, "block_scales"):  # weight-only MXFP4 (before int4: uint8 codes too)
+        if style == "rowwise" and (linear.in_features // world) % 32:
+            from ._abi import ColdCompressError
+
+            raise ColdCompressError(f"MXFP4 row-wise sharding over {world} ranks gives {linear.in_features // world} input features per "
+                                    "rank, not a multiple of the block of 32")
+        linear.weight = split(linear.weight, dim).contiguous()  # [N, K / 2]
+        linear.block_scales = split(linear.block_scales, dim).contiguous()  # [N, K / 32]
+        if style == "colwise" and linear.bias is not None:
+            linear.bias = split(linear.bias, 0).contiguous()
         setattr(linear, attr, getattr(linear, attr) // world)
         return
     if linear.weight.dtype == torch.uint8:  # weight-only int4: weight [N, K / 2] / scales_and_zeros [N, K / G, 2] / bias are buffers

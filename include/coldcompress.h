@@ -817,6 +817,29 @@ int cc_gemv_fused_w4(const uint8_t* W, const void* qparams, const uint8_t* W3, c
                      int32_t rope_rows, int32_t head_dim, void* y, int32_t N, int32_t K, int32_t groupsize, int32_t dtype,
                      cc_stream_t stream);
 
+/* The same decode-time dense layer over MXFP4 WEIGHT-ONLY matrices (OCP microscaling FP4, the 4-bit format of gfx950's conversion
+ * instructions; harness/quantize.py WeightOnlyMxfp4Linear): W, W3 uint8 [N, K / 2] row major, two e2m1 codes per byte, column 2j in
+ * the low nibble of byte j (the int4 / uint4 / MXFP4-KV order, and the order v_cvt_scalef32_pk_bf16_fp4 reads); scales / scales3
+ * uint8 [N, K / 32] row major, one e8m0 byte per row and block of 32 consecutive columns, value 2^(byte - 127).  A code is a sign bit
+ * over a magnitude in {0, 0.5, 1, 1.5, 2, 3, 4, 6}.  bf16 activations, bias, freqs and output.
+ *   quantisation (the checkpoint's, per block b of w = weight.float()): e_b = the smallest integer with amax_b <= 6 * 2^e_b (from
+ *             frexp, no division), clamped to [-120, 120]; -120 for an all-zero block (the MXFP4 KV mode's rule: nothing finite
+ *             saturates).  codes = round-to-nearest of w * 2^-e_b (an exact product), ties to the even mantissa; -0 keeps its sign.
+ *             byte = e_b + 127, so stored scale bytes lie in [7, 247], where code x scale is exact in bf16; the loader refuses any
+ *             other byte, and the quantiser refuses a non-finite weight.
+ *   prologue  exactly cc_gemv_fused's: h_out and the normalised input `in` are bit-identical to it.
+ *   product   p[n] = sum_k in[k] * (e2m1(q[n,k]) * 2^(byte - 127)), the byte of k's block, fp32 accumulation;
+ *             t[n] = bf16(p[n]); with bias t[n] = bf16(t[n] + bias[n]).
+ *   W3 != NULL (needs scales3): t3 likewise, y = bf16(bf16(silu(t)) * t3); no bias.
+ *   freqs != NULL: RoPE on rows [0, rope_rows) of the rounded t, as cc_gemv_fused.
+ * The summation order is the kernel's own (tolerance class) but fixed: results are bit-reproducible from run to run and under graph
+ * replay.  dtype CC_DT_BF16 only (CC_DT_F16 / CC_DT_F32: CC_ERR_UNSUPPORTED).  K % 32 == 0 and K * 2 <= 64 KiB, else
+ * CC_ERR_UNSUPPORTED.  A null required pointer, W / W3 / x / delta / norm_w / h_out not 16-byte aligned, or bias / freqs / y not
+ * 2-byte aligned: CC_ERR_BAD_ARG.  Arguments are validated before any launch: an error writes nothing. */
+int cc_gemv_fused_mx4(const uint8_t* W, const uint8_t* scales, const uint8_t* W3, const uint8_t* scales3, const void* x,
+                      const void* delta, const void* norm_w, float eps, void* h_out, const void* bias, const void* freqs,
+                      int32_t rope_rows, int32_t head_dim, void* y, int32_t N, int32_t K, int32_t dtype, cc_stream_t stream);
+
 /* Greedy sampling tail, ref: generation_utils.py:136-142: probs[V] = dtype(softmax_fp32(logits[V])),
  * *idx_out = first index of the largest rounded probability (torch.argmax semantics).  Two small launches; `workspace`
  * (cc_softmax_argmax_workspace_bytes) needs no initialisation. */

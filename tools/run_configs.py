@@ -2,8 +2,9 @@
 """End-to-end runs of the SURVEY §8(d) configurations on the full Llama-3-8B shape (bf16, random weights): 8k/16k-token
 prompt prefilled through the HIP path, then hipGraph decode; prints decode tokens/s and the cache statistics per config.
 --weights int8 quantises the model with the weight-only int8 handler (harness/quantize.py) first: decode streams int8 weights;
---weights int4 (--groupsize G, default 32) with the int4 group-wise handler: decode streams int4 weights.
-    python tools/run_configs.py [--steps 32] [--weights bf16|int8|int4] [--groupsize 32]"""
+--weights int4 (--groupsize G, default 32) with the int4 group-wise handler: decode streams int4 weights;
+--weights mxfp4 with the MXFP4 handler: decode streams e2m1 codes and e8m0 block scales.
+    python tools/run_configs.py [--steps 32] [--weights bf16|int8|int4|mxfp4] [--groupsize 32]"""
 import argparse
 import json
 import os
@@ -39,10 +40,11 @@ def run(name, cache, prompt_len, steps, dev, weights="bf16", groupsize=32):
         for n, p in model.named_parameters():
             p.fill_(1.0) if "norm" in n else p.normal_(0.0, 0.02, generator=g)
     model.eval()
-    if weights in ("int8", "int4"):
-        from cold_compress_amd.harness.quantize import WeightOnlyInt4QuantHandler, WeightOnlyInt8QuantHandler
+    if weights in ("int8", "int4", "mxfp4"):
+        from cold_compress_amd.harness.quantize import WeightOnlyInt4QuantHandler, WeightOnlyInt8QuantHandler, WeightOnlyMxfp4QuantHandler
 
-        handler = (lambda m: WeightOnlyInt8QuantHandler(m)) if weights == "int8" else (lambda m: WeightOnlyInt4QuantHandler(m, groupsize))
+        handler = {"int8": lambda m: WeightOnlyInt8QuantHandler(m), "int4": lambda m: WeightOnlyInt4QuantHandler(m, groupsize),
+                   "mxfp4": lambda m: WeightOnlyMxfp4QuantHandler(m)}[weights]
         sd = handler(model).create_quantized_state_dict()
         del model
         with torch.device("meta"):
@@ -95,7 +97,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=32)
     ap.add_argument("--only", default=None)
-    ap.add_argument("--weights", default="bf16", choices=["bf16", "int8", "int4"])
+    ap.add_argument("--weights", default="bf16", choices=["bf16", "int8", "int4", "mxfp4"])
     ap.add_argument("--groupsize", type=int, default=32, choices=[32, 64, 128, 256])
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
