@@ -1,0 +1,283 @@
+// cc_sample.hip — seeded temperature / top-k sampling tail (include/coldcompress.h, cc_sample_topk): the reference's
+// logits_to_probs (generation_utils.py:125-133) followed by a STATELESS Gumbel-max draw, so that one (logits, temperature, top_k,
+// seed, position) has one answer in eager launches, under hipGraph replay and on every tensor-parallel rank.
+// Launches over a fixed grid of kSpBlocks workgroups, every one a pure function of what the launches before it left in the workspace
+// (no atomics on global memory, no tickets: per-workgroup partials folded in a fixed order):
+//   select    one launch per 8-bit digit of the scaled value's orderable pattern, most significant first (two for bf16 / f16, four for
+//             fp32; none without top_k): a 256-bin LDS histogram per workgroup of the elements that match the digits chosen so far.
+//             The next launch folds the 128 histograms itself and walks the counts from the top to the digit that holds the k-th
+//             largest element.  The first of them also leaves the per-workgroup maxima (the largest kept value IS the global maximum).
+//   draw      folds the last histogram into the pivot; per workgroup the sum of exp(x - m) over the kept set and the best Gumbel key.
+//   write     folds the sums, writes the probabilities (exactly 0 outside the kept set); workgroup 0 folds the keys into the token.
+#include "cc_common.h"
+
+namespace {
+constexpr int kSpThreads = 256;
+constexpr int kSpBlocks = 128;
+constexpr int kSpWaves = kSpThreads / CC_WAVE;
+
+struct SpWs {  // caller-provided scratch (cc_sample_topk_workspace_bytes); nothing in it is read before a launch of the call wrote it
+  unsigned int hist[2][kSpBlocks][256];  // digit counts of select pass P in hist[P & 1]
+  float maxpart[kSpBlocks];
+  float sumpart[kSpBlocks];
+  unsigned long long keypart[kSpBlocks];
+  unsigned int prefix[4], krem[4];  // after pass P: the digits chosen so far, and the rank of the pivot among the elements that match them
+};
+
+template <typename T>
+__device__ __forceinline__ float sp_exp(float x) {  // cc_softmax_argmax's accuracy class (cc_glue.hip, sm_exp)
+  if constexpr (sizeof(T) == 4) return expf(x);
+  return __builtin_amdgcn_exp2f(x * 1.4426950408889634f);
+}
+
+// "larger is better" orderable pattern of a scaled value (already rounded to T), NB bits; -0 is +0 (they compare equal)
+template <typename T>
+struct SpKey;
+template <>
+struct SpKey<float> {
+  static constexpr int NB = 32;
+  __device__ static __forceinline__ uint32_t key(float x) {
+    const uint32_t u = __float_as_uint(x == 0.f ? 0.f : x);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  }
+};
+__device__ __forceinline__ uint32_t sp_key16(uint32_t b) {
+  if ((b & 0x7fffu) == 0u) b = 0u;
+  return (b & 0x8000u) ? (~b & 0xffffu) : (b | 0x8000u);
+}
+template <>
+struct SpKey<bf16_t> {
+  static constexpr int NB = 16;
+  __device__ static __forceinline__ uint32_t key(float x) { return sp_key16(__float_as_uint(x) >> 16); }
+};
+template <>
+struct SpKey<f16_t> {
+  static constexpr int NB = 16;
+  __device__ static __forceinline__ uint32_t key(float x) { return sp_key16(f32_to_f16_bits(x)); }
+};
+
+__device__ __forceinline__ void sp_slice(int V, int& lo, int& hi) {
+  const long long per = (((long long)V + kSpBlocks - 1) / kSpBlocks + 7) & ~7ll;
+  lo = (int)min((long long)V, (long long)blockIdx.x * per);
+  hi = (int)min((long long)V, (long long)lo + per);
+}
+
+// step 1 of the contract: one IEEE fp32 division, then the model dtype's rounding
+template <typename T>
+__device__ __forceinline__ float sp_scaled(const T* logits, int i, float tmax) {
+  return ElemTraits<T>::rnd(__fdiv_rn(ElemTraits<T>::load(logits, (size_t)i), tmax));
+}
+
+// Fold the 128 histograms of select pass P (thread t owns digit t) and walk the counts from digit 255 down to the digit that holds
+// the element of rank krem: -> the digits chosen so far including this one, and the pivot's rank among the elements that match them.
+// Every workgroup computes the same pair; workgroup 0 leaves it for the NEXT launch's fold.  s_w: kSpWaves + 2 words.
+__device__ __forceinline__ void sp_fold(SpWs* ws, int P, int k, unsigned int* s_w, uint32_t& prefix, uint32_t& krem) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint32_t pfx = 0u, kr = (uint32_t)k;
+  if (P > 0) {
+    pfx = ws->prefix[P - 1];
+    kr = ws->krem[P - 1];
+  }
+  uint32_t c = 0u;
+  for (int g = 0; g < kSpBlocks; g++) c += ws->hist[P & 1][g][threadIdx.x];
+  uint32_t s = c;  // inclusive suffix sum over the wave's digits (digit = threadIdx.x: higher lanes hold larger values)
+#pragma unroll
+  for (int off = 1; off < CC_WAVE; off <<= 1) {
+    const uint32_t o = __shfl_down(s, off, CC_WAVE);
+    if (lane + off < CC_WAVE) s += o;
+  }
+  if (lane == 0) s_w[wave] = s;
+  if (threadIdx.x == 0) {  // (unreachable fall-back: the matching elements number at least kr)
+    s_w[kSpWaves] = pfx << 8;
+    s_w[kSpWaves + 1] = 1u;
+  }
+  __syncthreads();
+  uint32_t above = 0u;
+  for (int w = wave + 1; w < kSpWaves; w++) above += s_w[w];
+  const uint32_t incl = s + above, excl = incl - c;
+  if (excl < kr && kr <= incl) {  // exactly one digit
+    s_w[kSpWaves] = (pfx << 8) | (uint32_t)threadIdx.x;
+    s_w[kSpWaves + 1] = kr - excl;
+  }
+  __syncthreads();
+  prefix = s_w[kSpWaves];
+  krem = s_w[kSpWaves + 1];
+  __syncthreads();
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    ws->prefix[P] = prefix;
+    ws->krem[P] = krem;
+  }
+}
+
+// select pass P (k > 0), and for P == 0 the per-workgroup maxima (k == 0: those alone)
+template <typename T, int P>
+__global__ __launch_bounds__(kSpThreads) void sample_hist_kernel(const T* logits, int V, float tmax, int k, SpWs* ws) {
+  constexpr int NB = SpKey<T>::NB;
+  __shared__ unsigned int sh[256];
+  __shared__ unsigned int s_w[kSpWaves + 2];
+  __shared__ float s_f[kSpWaves];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int lo, hi;
+  sp_slice(V, lo, hi);
+  uint32_t prefix = 0u, krem = 0u;
+  if constexpr (P > 0) sp_fold(ws, P - 1, k, s_w, prefix, krem);
+  sh[threadIdx.x] = 0u;
+  __syncthreads();
+  float mx = -INFINITY;
+  for (int i = lo + threadIdx.x; i < hi; i += kSpThreads) {
+    const float x = sp_scaled<T>(logits, i, tmax);
+    if constexpr (P == 0) mx = fmaxf(mx, x);
+    if (k > 0) {
+      const uint32_t key = SpKey<T>::key(x);
+      bool match = true;
+      if constexpr (P > 0) match = (key >> (NB - 8 * P)) == prefix;
+      if (match) atomicAdd(&sh[(key >> (NB - 8 * (P + 1))) & 0xffu], 1u);
+    }
+  }
+  __syncthreads();
+  if (k > 0) ws->hist[P & 1][blockIdx.x][threadIdx.x] = sh[threadIdx.x];
+  if constexpr (P == 0) {
+    mx = wave_max_f32(mx);
+    if (lane == 0) s_f[wave] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) ws->maxpart[blockIdx.x] = fmaxf(fmaxf(s_f[0], s_f[1]), fmaxf(s_f[2], s_f[3]));
+  }
+}
+
+// the global maximum of the scaled values from the per-workgroup maxima (NaN never counts: fmaxf); valid in every thread
+__device__ __forceinline__ float sp_fold_max(const SpWs* ws, float* s_f) {
+  if (threadIdx.x < CC_WAVE) {
+    float m = -INFINITY;
+    for (int g = threadIdx.x; g < kSpBlocks; g += CC_WAVE) m = fmaxf(m, ws->maxpart[g]);
+    m = wave_max_f32(m);
+    if (threadIdx.x == 0) s_f[0] = m;
+  }
+  __syncthreads();
+  return s_f[0];
+}
+
+// steps 4 and 5 of the contract.  -log(u) through log1pf for u > 1/2 (1 - u is exact there): libm-grade where the winners come from
+__device__ __forceinline__ float sp_gumbel_key(float d, uint64_t seed, int32_t pos, int i) {
+  const uint64_t h = cc_mix64(cc_mix64((seed ^ 0x53414D504C45ull) + (uint64_t)(uint32_t)pos * 0x9E3779B97F4A7C15ull + (uint64_t)(uint32_t)i));
+  const float u = (float)(uint32_t)(2u * (uint32_t)(h >> 41) + 1u) * 5.9604644775390625e-08f;  // odd multiple of 2^-24: exact, never 0 or 1
+  const float e = u > 0.5f ? -log1pf(__fsub_rn(u, 1.0f)) : -logf(u);
+  return __fsub_rn(d, logf(e));
+}
+
+template <typename T, int NP>  // NP: select passes that ran (0: everything is kept)
+__global__ __launch_bounds__(kSpThreads) void sample_draw_kernel(const T* logits, int V, float tmax, int k, unsigned long long seed,
+                                                                 const int32_t* input_pos, SpWs* ws) {
+  __shared__ unsigned int s_w[kSpWaves + 2];
+  __shared__ float s_f[kSpWaves];
+  __shared__ unsigned long long s_k[kSpWaves + 1];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int lo, hi;
+  sp_slice(V, lo, hi);
+  uint32_t pivot = 0u, krem = 0u;
+  if constexpr (NP > 0) sp_fold(ws, NP - 1, k, s_w, pivot, krem);
+  const float m = sp_fold_max(ws, s_f);
+  __syncthreads();
+  const int32_t pos = *input_pos;
+  float sum = 0.f;
+  unsigned long long best = ~0ull;
+  for (int i = lo + threadIdx.x; i < hi; i += kSpThreads) {
+    const float x = sp_scaled<T>(logits, i, tmax);
+    unsigned long long cand = ~0ull;
+    if (x != x) {
+      cand = (unsigned long long)(unsigned)i;  // upper half 0 beats every number: the first NaN's index (cc_softmax_argmax's rule)
+    } else if (SpKey<T>::key(x) >= pivot) {
+      const float d = __fsub_rn(x, m);
+      sum += sp_exp<T>(d);
+      cand = ((unsigned long long)(~orderable_f32(sp_gumbel_key(d, seed, pos, i))) << 32) | (unsigned)i;
+    }
+    best = cand < best ? cand : best;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, CC_WAVE);
+  if (lane == 0) s_f[wave] = sum;
+  best = block_min_u64(best, s_k);  // (its barriers also publish s_f)
+  if (threadIdx.x == 0) {
+    ws->sumpart[blockIdx.x] = (s_f[0] + s_f[1]) + (s_f[2] + s_f[3]);
+    ws->keypart[blockIdx.x] = best;
+  }
+}
+
+template <typename T, int NP>
+__global__ __launch_bounds__(kSpThreads) void sample_write_kernel(const T* logits, int V, float tmax, T* probs, int32_t* idx_out, SpWs* ws) {
+  __shared__ float s_f[kSpWaves];
+  __shared__ float s_sum;
+  int lo, hi;
+  sp_slice(V, lo, hi);
+  const float m = sp_fold_max(ws, s_f);
+  if (threadIdx.x < CC_WAVE) {  // one wave folds the sums in a fixed order
+    float s = 0.f;
+    for (int g = threadIdx.x; g < kSpBlocks; g += CC_WAVE) s += ws->sumpart[g];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, CC_WAVE);
+    if (threadIdx.x == 0) s_sum = s;
+  }
+  __syncthreads();
+  const float sum = s_sum;
+  uint32_t pivot = 0u;
+  if constexpr (NP > 0) pivot = ws->prefix[NP - 1];
+  for (int i = lo + threadIdx.x; i < hi; i += kSpThreads) {
+    const float x = sp_scaled<T>(logits, i, tmax);
+    float p = 0.f;
+    if (x != x || SpKey<T>::key(x) >= pivot) p = ElemTraits<T>::rnd(__fdiv_rn(sp_exp<T>(__fsub_rn(x, m)), sum));
+    ElemTraits<T>::store(probs, (size_t)i, p);
+  }
+  if (blockIdx.x == 0 && threadIdx.x < CC_WAVE) {
+    unsigned long long b = ~0ull;
+    for (int g = threadIdx.x; g < kSpBlocks; g += CC_WAVE) {
+      const unsigned long long o = ws->keypart[g];
+      b = o < b ? o : b;
+    }
+    b = wave_min_u64(b);
+    if (threadIdx.x == 0) *idx_out = b == ~0ull ? 0 : (int32_t)(b & 0xffffffffull);  // (no candidate at all cannot happen for V > 0: a valid index anyway)
+  }
+}
+
+template <typename T>
+void sp_launch(const void* logits_, int V, float tmax, int k, unsigned long long seed, const int32_t* input_pos, void* probs_, int32_t* idx_out,
+               SpWs* ws, hipStream_t st) {
+  const T* logits = (const T*)logits_;
+  T* probs = (T*)probs_;
+  dim3 grid(kSpBlocks), block(kSpThreads);
+  hipLaunchKernelGGL((sample_hist_kernel<T, 0>), grid, block, 0, st, logits, V, tmax, k, ws);
+  if (k <= 0) {
+    hipLaunchKernelGGL((sample_draw_kernel<T, 0>), grid, block, 0, st, logits, V, tmax, k, seed, input_pos, ws);
+    hipLaunchKernelGGL((sample_write_kernel<T, 0>), grid, block, 0, st, logits, V, tmax, probs, idx_out, ws);
+    return;
+  }
+  hipLaunchKernelGGL((sample_hist_kernel<T, 1>), grid, block, 0, st, logits, V, tmax, k, ws);
+  constexpr int NP = SpKey<T>::NB / 8;
+  if constexpr (NP == 4) {
+    hipLaunchKernelGGL((sample_hist_kernel<T, 2>), grid, block, 0, st, logits, V, tmax, k, ws);
+    hipLaunchKernelGGL((sample_hist_kernel<T, 3>), grid, block, 0, st, logits, V, tmax, k, ws);
+  }
+  hipLaunchKernelGGL((sample_draw_kernel<T, NP>), grid, block, 0, st, logits, V, tmax, k, seed, input_pos, ws);
+  hipLaunchKernelGGL((sample_write_kernel<T, NP>), grid, block, 0, st, logits, V, tmax, probs, idx_out, ws);
+}
+}  // namespace
+
+extern "C" size_t cc_sample_topk_workspace_bytes(void) { return sizeof(SpWs); }
+
+extern "C" int cc_sample_topk(const void* logits, int32_t V, int32_t dtype, float temperature, int32_t top_k, uint64_t seed,
+                              const int32_t* input_pos, void* probs, int32_t* idx_out, void* workspace, size_t workspace_bytes,
+                              cc_stream_t stream) {
+  CC_ENTRY();
+  if (!logits || !probs || !idx_out || !input_pos || !workspace || V <= 0 || !cc_dt_ok(dtype) || !(temperature > 0.f)) return CC_ERR_BAD_ARG;
+  if (workspace_bytes < sizeof(SpWs)) return CC_ERR_WORKSPACE;
+  if (((uintptr_t)workspace & 7u) != 0) return CC_ERR_BAD_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  SpWs* ws = reinterpret_cast<SpWs*>(workspace);
+  const float tmax = temperature > 1e-5f ? temperature : 1e-5f;
+  const int k = (top_k <= 0 || top_k >= V) ? 0 : top_k;  // k = min(top_k, V) = V keeps everything, as no top_k does
+  switch (dtype) {
+    case CC_DT_F32: sp_launch<float>(logits, V, tmax, k, seed, input_pos, probs, idx_out, ws, st); break;
+    case CC_DT_BF16: sp_launch<bf16_t>(logits, V, tmax, k, seed, input_pos, probs, idx_out, ws, st); break;
+    default: sp_launch<f16_t>(logits, V, tmax, k, seed, input_pos, probs, idx_out, ws, st); break;
+  }
+  CC_LAUNCH_CHECK();
+  return CC_OK;
+}

@@ -104,25 +104,91 @@ def greedy(logits, next_token):
     return idx_next, probs
 
 
-def prefill(model, x, input_pos, next_token=None, **_):
-    """ref: generation_utils.py:145-160 — the causal mask is implicit in the HIP prefill kernel."""
+_M64 = (1 << 64) - 1
+
+
+def _i64(v):
+    """The uint64 `v` as the int64 with the same bits (torch has no uint64 arithmetic: int64 wraps the same way)."""
+    v &= _M64
+    return v - (1 << 64) if v >> 63 else v
+
+
+def _mix64(x):
+    """murmur3's finaliser on int64 tensors holding uint64 bit patterns (logical shifts spelled with a mask)."""
+    lo31 = (1 << 31) - 1
+    x = x ^ ((x >> 33) & lo31)
+    x = x * _i64(0xFF51AFD7ED558CCD)
+    x = x ^ ((x >> 33) & lo31)
+    x = x * _i64(0xC4CEB9FE1A85EC53)
+    return x ^ ((x >> 33) & lo31)
+
+
+def _sample_host(row, temperature, top_k, seed, pos):
+    """cc_sample_topk's contract (include/coldcompress.h) in torch on a CPU tensor: the same six steps, fp32 where the kernel is."""
+    V, dt = row.numel(), row.dtype
+    tmax = torch.maximum(torch.tensor(float(temperature), dtype=torch.float32), torch.tensor(1e-5, dtype=torch.float32))
+    x = (row.float() / tmax).to(dt).float()  # 1. one fp32 division, rounded to the model dtype
+    kept = torch.ones(V, dtype=torch.bool)
+    if top_k is not None and top_k > 0:  # 2. ties at the pivot are all kept
+        kept = x >= torch.topk(x, min(int(top_k), V)).values[-1]
+    m = x[kept].max() if bool(kept.any()) else x.max()
+    e = torch.where(kept, torch.exp(x - m), torch.zeros_like(x))  # 3.
+    probs = (e / e.sum()).to(dt)
+    i = torch.arange(V, dtype=torch.int64)  # 4. (p and i widened from unsigned 32 bits)
+    h = _mix64(_mix64(torch.tensor(_i64((int(seed) ^ 0x53414D504C45) + (int(pos) & 0xFFFFFFFF) * 0x9E3779B97F4A7C15), dtype=torch.int64) + i))
+    u = (2 * ((h >> 41) & ((1 << 23) - 1)) + 1).to(torch.float32) * 2.0 ** -24
+    ee = torch.where(u > 0.5, -torch.log1p(u - 1.0), -torch.log(u))
+    key = (x - m) - torch.log(ee)  # 5. Gumbel-max; argmax returns the first maximal index
+    key = torch.where(kept, key, torch.full_like(key, -float("inf")))
+    nan = torch.isnan(x)
+    idx = torch.argmax(nan.to(torch.int8)) if bool(nan.any()) else torch.argmax(key)  # 6. the first NaN's index
+    return idx.view(1).to(torch.int), probs
+
+
+def sample(logits, next_token, temperature, top_k, seed, input_pos):
+    """The reference's logits_to_probs (generation_utils.py:125-133) and a stateless draw from it: one token per (logits,
+    temperature, top_k, seed, position), whatever launches, replays or ranks computed it (include/coldcompress.h, cc_sample_topk).
+    `input_pos`: one element, the position of the step whose logits these are.  Device tensors run the kernel; CPU tensors the same
+    contract in torch.  A forced `next_token` is returned as given, with the sampled distribution's probabilities."""
+    row = logits[0, -1]
+    if row.is_cuda:
+        from . import glue
+
+        probs, idx_next = glue.sample_topk(row, temperature, top_k, seed, input_pos.view(-1)[-1:].to(torch.int32))
+    else:
+        if not float(temperature) > 0:
+            raise ValueError(f"sample: temperature must be > 0, got {temperature}")
+        idx_next, probs = _sample_host(row, temperature, top_k, seed, int(input_pos.view(-1)[-1]))
+    return (idx_next if next_token is None else next_token), probs
+
+
+def prefill(model, x, input_pos, next_token=None, temperature=None, top_k=None, seed=0, **_):
+    """ref: generation_utils.py:145-160 — the causal mask is implicit in the HIP prefill kernel.  `temperature` None: greedy;
+    otherwise the token is drawn at the last prompt position (sample)."""
     logits = model(x, input_pos, mask=None, is_prefill=True)
-    return greedy(logits, next_token)
+    if temperature is None:
+        return greedy(logits, next_token)
+    return sample(logits, next_token, temperature, top_k, seed, input_pos[-1:])
 
 
-def decode_one_token(model, x, input_pos, next_token=None, attn_top_k=1.0, **_):
-    """ref: generation_utils.py:163-178."""
+def decode_one_token(model, x, input_pos, next_token=None, attn_top_k=1.0, temperature=None, top_k=None, seed=0, **_):
+    """ref: generation_utils.py:163-178.  `temperature` None: greedy; otherwise the token is drawn at `input_pos` (sample)."""
     logits = model(x, input_pos, is_prefill=False, attn_top_k=attn_top_k)
-    return greedy(logits, next_token)
+    if temperature is None:
+        return greedy(logits, next_token)
+    return sample(logits, next_token, temperature, top_k, seed, input_pos)
 
 
 class GraphedDecoder:
     """One decode step captured in a hipGraph (HIP-native replacement for the reference's
     `torch.compile(mode="reduce-overhead")`, generation_utils.py:581-587).  The token and position live in
-    static device tensors; every HIP entry point reads `input_pos` from device memory, so replays advance."""
+    static device tensors; every HIP entry point reads `input_pos` from device memory, so replays advance.
+    The sampling settings (temperature, top_k, seed; None: greedy) are carried by the captured step BY VALUE — the draw itself reads
+    the position from device memory — so a call with other settings than the step was captured with captures again."""
 
-    def __init__(self, model, warmup=2):
+    def __init__(self, model, warmup=2, temperature=None, top_k=None, seed=0):
         self.model = model
+        self.sampling = (temperature, top_k, seed)
         dev = model.output.weight.device
         self.tok = torch.zeros((1, 1), dtype=torch.int32, device=dev)
         self.pos = torch.zeros((1,), dtype=torch.int32, device=dev)
@@ -139,17 +205,18 @@ class GraphedDecoder:
         snap = [{k: v.clone() for k, v in c._buffers.items()} for c in caches]
         flags = [(getattr(c, "_next_valid", None), getattr(c, "_quant_pending", False)) for c in caches]
         pos0 = self.pos.clone()
+        kw = dict(zip(("temperature", "top_k", "seed"), self.sampling))
         try:
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
                 for _ in range(self.warmup):  # positions advance like a real decode (the pipeline assumes +1 steps)
-                    decode_one_token(self.model, self.tok, self.pos)
+                    decode_one_token(self.model, self.tok, self.pos, **kw)
                     self.pos += 1
             torch.cuda.current_stream().wait_stream(s)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                self.out_tok, self.out_probs = decode_one_token(self.model, self.tok, self.pos)
+                self.out_tok, self.out_probs = decode_one_token(self.model, self.tok, self.pos, **kw)
             self.graph = graph
             self._epoch = self._cache_epoch()
         finally:  # also when capture is refused (e.g. a collective that cannot be captured): the caller falls back to
@@ -167,7 +234,11 @@ class GraphedDecoder:
         """Moves when a cache changed something the captured steps carry by value (KVCacheRandom's per-generation seed)."""
         return sum(int(getattr(l.attention.kv_cache, "_graph_epoch", 0)) for l in self.model.layers)
 
-    def __call__(self, model, x, input_pos, next_token=None, **_):
+    def __call__(self, model, x, input_pos, next_token=None, **kw):
+        sampling = tuple(kw.get(k, d) for k, d in zip(("temperature", "top_k", "seed"), self.sampling))
+        if sampling != self.sampling:  # (carried by value, like what _cache_epoch watches: capture again)
+            self.sampling = sampling
+            self.graph = None
         if self.graph is not None:
             # A decoder reused across reset() / generations: prepare_decode sits OUTSIDE the captured step, so EVERY cache whose fused
             # pipeline was invalidated since (reset, a prefill) is re-seeded here, at the position the replay is about to run — the

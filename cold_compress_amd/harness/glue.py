@@ -3,7 +3,7 @@
 These are NOT part of the cache/attention hot path — they are the model-side code around it
 (ref: model.py:317-327, 375-387, 442-443, 452-457, 507-519), which the reference leaves to ~45 eager elementwise
 launches per layer or to torch.compile.  On device tensors they call the C ABI (`cc_add_rmsnorm`, `cc_qkv_rope`,
-`cc_silu_mul`, `cc_gemv_fused`, `cc_softmax_argmax`); CPU tensors raise — there is no host path in the package (the
+`cc_silu_mul`, `cc_gemv_fused`, `cc_softmax_argmax`, `cc_sample_topk`); CPU tensors raise — there is no host path in the package (the
 CPU model-wiring test brings its own eager twins: tests/host_glue.py).
 """
 import ctypes as C
@@ -161,3 +161,29 @@ def softmax_argmax(logits):
 
 
 _SM_WS = {}
+
+
+def sample_topk(logits, temperature, top_k, seed, input_pos):
+    """probs = the reference's logits_to_probs(logits, temperature, top_k) in the model dtype and one token drawn from it by the
+    stateless Gumbel-max rule of (seed, *input_pos) (cc_sample_topk; include/coldcompress.h has the contract).  logits: [V];
+    input_pos: a one-element int32 DEVICE tensor, read by the kernels (a captured step advances through it).  -> (probs, idx)."""
+    if not logits.is_cuda:
+        _host(logits, "sample_topk logits")
+    if not (input_pos.is_cuda and input_pos.dtype == torch.int32 and input_pos.numel() == 1):
+        raise _abi.ColdCompressError(f"sample_topk: input_pos must be a one-element int32 device tensor, got {input_pos.dtype} "
+                                     f"{tuple(input_pos.shape)} on {input_pos.device}")
+    if not float(temperature) > 0:
+        raise _abi.ColdCompressError(f"sample_topk: temperature must be > 0, got {temperature}")
+    lc = logits.contiguous()
+    probs = torch.empty_like(lc)
+    idx = torch.empty((1,), dtype=torch.int32, device=lc.device)
+    ws = _SP_WS.get(lc.device)
+    if ws is None:
+        ws = _SP_WS[lc.device] = torch.empty(int(_abi.lib()["cc_sample_topk_workspace_bytes"]()), dtype=torch.uint8, device=lc.device)
+    k = 0 if top_k is None else max(0, min(int(top_k), 2 ** 31 - 1))
+    _abi.call("cc_sample_topk", _p(lc), lc.numel(), _DT[lc.dtype], float(temperature), k, int(seed) & (2 ** 64 - 1), _p(input_pos),
+              _p(probs), _p(idx), _p(ws), ws.numel(), _stream())
+    return probs, idx
+
+
+_SP_WS = {}

@@ -847,6 +847,36 @@ size_t cc_softmax_argmax_workspace_bytes(void);
 int cc_softmax_argmax(const void* logits, int32_t V, int32_t dtype, void* probs, int32_t* idx_out, void* workspace,
                       size_t workspace_bytes, cc_stream_t stream);
 
+/* Seeded temperature / top-k sampling tail, ref: generation_utils.py:125-133 (logits_to_probs) followed by a STATELESS draw: one
+ * answer per (logits, temperature, top_k, seed, *input_pos), the same in eager launches, under hipGraph replay (a replay advances
+ * through *input_pos, which is read from DEVICE memory) and on every tensor-parallel rank (replicated logits: no communication).
+ * logits[V] and probs[V] in the model dtype T (`dtype`); temperature > 0; top_k <= 0: none; input_pos: the position of the step
+ * whose logits these are.
+ *   1. scaling   x[i] = T(float(logits[i]) / max(temperature, 1e-5f)): ONE IEEE fp32 division, then rounded to T (the reference's
+ *                `logits / temperature` in the model dtype).
+ *   2. top-k     k = min(top_k, V); pivot = the k-th largest x counted with multiplicity; kept = {i : x[i] >= pivot} — ties at the
+ *                pivot are ALL kept (the reference's torch.where(logits < pivot, -inf, logits)).  No top_k: everything is kept.
+ *   3. probs     m = the largest kept x.  Kept i: probs[i] = T(exp(x[i] - m) / sum over kept j of exp(x[j] - m)), in fp32, the exp
+ *                and the summation order in cc_softmax_argmax's accuracy class; every other probs[i] is exactly 0.
+ *   4. draw      h_i = mix64(mix64((seed ^ 0x53414D504C45) + p * 0x9E3779B97F4A7C15 + i)) in uint64 arithmetic, p = *input_pos and i
+ *                widened from unsigned 32 bits, mix64 = the murmur3 finaliser (x ^= x >> 33; x *= 0xff51afd7ed558ccd; x ^= x >> 33;
+ *                x *= 0xc4ceb9fe1a85ec53; x ^= x >> 33), applied twice as KVCacheRandom's generator does.
+ *                u_i = (2 * (h_i >> 41) + 1) * 2^-24: exact in fp32, never 0 or 1.
+ *   5. token     *idx_out = the kept i that maximises key_i = (x[i] - m) - log(-log(u_i)) in fp32 (the Gumbel-max rule: i wins with
+ *                probability probs[i]); the smallest index wins a tie.  Both logarithms are libm-grade (<= 2 ulp), -log(u) as
+ *                -log1pf(u - 1) for u > 1/2, where u - 1 is exact.  When top_k keeps one element the token is that element.
+ *   6. NaN       if any x is NaN, *idx_out is the first NaN's index (cc_softmax_argmax's rule: inside the vocabulary).  Nothing else
+ *                is promised then, nor for infinite x.
+ * The answer does not depend on the grid or on any reduction order: the pivot is an exact radix select over the orderable bit
+ * pattern of x (8 bits per launch: two launches for the 16-bit dtypes, four for fp32, none without top_k), the token an arg-min
+ * over 64-bit keys (~orderable(key_i) << 32 | i), the sum a fixed-order fold of per-workgroup partials.  Never synchronises, never
+ * allocates, stream-capturable; `workspace` (cc_sample_topk_workspace_bytes, 8-byte aligned) needs no initialisation.
+ * temperature <= 0 or NaN, V <= 0, a null pointer: CC_ERR_BAD_ARG before any launch. */
+size_t cc_sample_topk_workspace_bytes(void);
+int cc_sample_topk(const void* logits, int32_t V, int32_t dtype, float temperature, int32_t top_k, uint64_t seed,
+                   const int32_t* input_pos, void* probs, int32_t* idx_out, void* workspace, size_t workspace_bytes,
+                   cc_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * One-shot sum all-reduce over the GPUs of ONE node, for the decode-size messages of tensor parallelism.
  * ref: tp.py:134-138, 156-160 (`all_reduce(sum)` of the wo and FFN outputs: 2 * dim bytes, 8-16 KiB, twice per layer).
