@@ -286,7 +286,322 @@ static int launch_gemv(const GemvArgs& a, hipStream_t st) {
   return CC_OK;
 }
 
+// ---- the same product for NT input vectors from ONE pass over the weights (cc_gemv_fused_multi): blocks of decode steps whose
+//      input tokens are known (teacher forcing, the tail of a long prompt) need not stream W once per token.  Row t of y / h_out is
+//      BIT-IDENTICAL to gemv_kernel on row t of x / delta / freqs: the lane that owns a 16-byte chunk, the order of a lane's Dot16
+//      chain, gv_wave_sum, the four-wave meet (p0 + p1) + (p2 + p3) and every rounding point of the prologue and the epilogue are
+//      gemv_kernel's, kept per token — a weight register loaded once feeds NT accumulator chains instead of one.  None of that
+//      depends on RB, CU or the grid, so the launcher is free to choose them by the register budget (NT * XS input chunks per lane).
+//      x, delta, h_out: [NT, K]; y: [NT, N]; freqs: [NT, head_dim / 2, 2].  A plain grid: no workgroup waits for another.
+template <typename T, bool SWIGLU, int RB, int CU, int XS, int NT>
+__global__ __launch_bounds__(kGvThreads) void gemv_multi_kernel(GemvArgs a) {
+  constexpr int VEC = 16 / (int)sizeof(T);
+  static_assert(NT * RB <= 64, "wave 0 finishes one (token, row) per lane");
+  __shared__ float sm_red[NT][kGvWaves];
+  __shared__ float sm_part[NT][kGvWaves][2][RB];
+  const int K = a.K, N = a.N;
+  const int nch = K / VEC;
+  const T* xg = reinterpret_cast<const T*>(a.x);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+
+  // ---- work decomposition and the weight tile: gemv_kernel's (the first tile is requested before the inputs are touched)
+  const int nseg = (nch + 63) / 64;
+  const int nstep = (nseg + kGvWaves - 1) / kGvWaves;
+  const uint4* Wv = reinterpret_cast<const uint4*>(a.W);
+  const uint4* W3v = reinterpret_cast<const uint4*>(a.W3);
+  uint4 w[RB][CU], w3[RB][CU];
+  auto issue = [&](int r0, int s0) {
+#pragma unroll
+    for (int u = 0; u < CU; u++) {
+      const int c = ((s0 + u) * kGvWaves + wave) * 64 + lane;
+      const bool cin = (s0 + u < nstep) && c < nch;
+#pragma unroll
+      for (int r = 0; r < RB; r++) {
+        const bool in = cin && (r0 + r < N);
+        const size_t off = (size_t)(r0 + r) * nch + c;
+        w[r][u] = in ? nt_load(Wv + off) : make_uint4(0, 0, 0, 0);
+        if (SWIGLU) w3[r][u] = in ? nt_load(W3v + off) : make_uint4(0, 0, 0, 0);
+      }
+    }
+  };
+  const int row_first = blockIdx.x * RB;
+  if (row_first < N) issue(row_first, 0);
+
+  // ---- the NT input vectors: every lane keeps the chunks it will multiply, of every token (NT * XS uint4).  The norm prologue
+  //      runs per token (NT sums of squares, ONE barrier); chunk by chunk, so that only one chunk's x / delta of every token is
+  //      live beside the kept registers.  A token's sum of squares still runs over its chunks in gemv_kernel's order.
+  uint4 xr[NT][XS];
+  if (a.norm_w != nullptr) {
+    const T* dg = reinterpret_cast<const T*>(a.delta);
+    const T* wg = reinterpret_cast<const T*>(a.norm_w);
+    // (fp32 at 16 chunks and 3 or 4 tokens: the norm weight's chunks are read again behind the barrier instead of being kept — the
+    //  64 registers they would take are what that instantiation lacks)
+    constexpr bool KEEP_NV = !(sizeof(T) == 4 && XS == 16 && NT >= 3);
+    Vec16<T> nv[KEEP_NV ? XS : 1];
+    float ss[NT];
+#pragma unroll
+    for (int t = 0; t < NT; t++) ss[t] = 0.f;
+#pragma unroll
+    for (int j = 0; j < XS; j++) {
+      const int c = (j * kGvWaves + wave) * 64 + lane;
+      const bool in = j < nstep && c < nch;
+      if (KEEP_NV && in) nv[KEEP_NV ? j : 0].load(wg + (size_t)c * VEC);
+#pragma unroll
+      for (int t = 0; t < NT; t++) {
+        xr[t][j] = make_uint4(0, 0, 0, 0);
+        if (in) {
+          const size_t at = (size_t)t * K + (size_t)c * VEC;
+          Vec16<T> xv, dv;
+          xv.load(xg + at);
+          if (dg != nullptr) dv.load(dg + at);
+          float h[VEC];
+          xv.unpack(h);
+          if (dg != nullptr) {
+            float d[VEC];
+            dv.unpack(d);
+#pragma unroll
+            for (int e = 0; e < VEC; e++) h[e] = ElemTraits<T>::rnd(__fadd_rn(h[e], d[e]));  // model-dtype residual add
+          }
+#pragma unroll
+          for (int e = 0; e < VEC; e++) ss[t] = fmaf(h[e], h[e], ss[t]);
+          xr[t][j] = pack16<T>(h);
+          if (a.h_out != nullptr && blockIdx.x == 0) reinterpret_cast<uint4*>(a.h_out)[(size_t)t * nch + c] = xr[t][j];
+        }
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < NT; t++) {
+      const float s = gv_wave_sum(ss[t]);
+      if (lane == 0) sm_red[t][wave] = s;
+    }
+    __syncthreads();
+    float rs[NT];
+#pragma unroll
+    for (int t = 0; t < NT; t++) {
+      const float tot = (sm_red[t][0] + sm_red[t][1]) + (sm_red[t][2] + sm_red[t][3]);
+      rs[t] = rsqrtf(tot / (float)K + a.eps);
+    }
+#pragma unroll
+    for (int j = 0; j < XS; j++) {
+      const int c = (j * kGvWaves + wave) * 64 + lane;
+      if (j < nstep && c < nch) {
+        float wf[VEC];
+        if (KEEP_NV) {
+          nv[KEEP_NV ? j : 0].unpack(wf);
+        } else {
+          Vec16<T> n;
+          n.load(wg + (size_t)c * VEC);
+          n.unpack(wf);
+        }
+#pragma unroll
+        for (int t = 0; t < NT; t++) {
+          Vec16<T> hv;
+          float h[VEC], o[VEC];
+          hv.raw = xr[t][j];
+          hv.unpack(h);
+#pragma unroll
+          for (int e = 0; e < VEC; e++) o[e] = ElemTraits<T>::rnd(__fmul_rn(ElemTraits<T>::rnd(cc_opaque_f32(__fmul_rn(h[e], rs[t]))), wf[e]));
+          xr[t][j] = pack16<T>(o);
+        }
+      }
+    }
+  } else {
+#pragma unroll
+    for (int t = 0; t < NT; t++) {
+#pragma unroll
+      for (int j = 0; j < XS; j++) {
+        const int c = (j * kGvWaves + wave) * 64 + lane;
+        xr[t][j] = (j < nstep && c < nch) ? reinterpret_cast<const uint4*>(xg)[(size_t)t * nch + c] : make_uint4(0, 0, 0, 0);
+      }
+    }
+  }
+
+  T* yo = reinterpret_cast<T*>(a.y);
+  bool first = true;
+  for (int r0 = row_first; r0 < N; r0 += gridDim.x * RB) {
+    float acc[NT][RB], acc3[NT][RB];
+#pragma unroll
+    for (int t = 0; t < NT; t++) {
+#pragma unroll
+      for (int r = 0; r < RB; r++) acc[t][r] = acc3[t][r] = 0.f;
+    }
+#pragma unroll
+    for (int s0 = 0; s0 < XS; s0 += CU) {
+      if (s0 < nstep) {
+        if (!first) issue(r0, s0);
+        first = false;
+#pragma unroll
+        for (int u = 0; u < CU; u++) {
+#pragma unroll
+          for (int t = 0; t < NT; t++) {
+            const uint4 xv = xr[t][s0 + u < XS ? s0 + u : XS - 1];  // beyond nstep the weights are zero-filled
+#pragma unroll
+            for (int r = 0; r < RB; r++) {
+              acc[t][r] = Dot16<T>::run(w[r][u], xv, acc[t][r]);
+              if (SWIGLU) acc3[t][r] = Dot16<T>::run(w3[r][u], xv, acc3[t][r]);
+            }
+          }
+        }
+      }
+    }
+    // ---- the four K-quarters of every (token, row) meet in LDS (fixed order: deterministic)
+#pragma unroll
+    for (int t = 0; t < NT; t++) {
+#pragma unroll
+      for (int r = 0; r < RB; r++) {
+        const float s = gv_wave_sum(acc[t][r]);
+        float s3 = 0.f;
+        if (SWIGLU) s3 = gv_wave_sum(acc3[t][r]);
+        if (lane == 0) {
+          sm_part[t][wave][0][r] = s;
+          if (SWIGLU) sm_part[t][wave][1][r] = s3;
+        }
+      }
+    }
+    __syncthreads();
+    if (wave == 0) {
+      float out = 0.f;  // lane t * RB + r finishes row r0 + r of token t (RB is even: a RoPE pair stays in lanes l, l ^ 1)
+      const bool mine = lane < NT * RB;
+      const int t = mine ? lane / RB : 0;
+      const int r = mine ? lane % RB : 0;
+      float s = (sm_part[t][0][0][r] + sm_part[t][1][0][r]) + (sm_part[t][2][0][r] + sm_part[t][3][0][r]);
+      const int row = r0 + r;
+      if (a.bias != nullptr && row < N) s += ElemTraits<T>::load(reinterpret_cast<const T*>(a.bias), (size_t)row);
+      s = ElemTraits<T>::rnd(cc_opaque_f32(s));  // (opaque, here and below: gemv_kernel's rounding points)
+      if (SWIGLU) {
+        const float s3 = ElemTraits<T>::rnd((sm_part[t][0][1][r] + sm_part[t][1][1][r]) + (sm_part[t][2][1][r] + sm_part[t][3][1][r]));
+        const float sl = ElemTraits<T>::rnd(__fdiv_rn(s, 1.0f + expf(-s)));
+        s = __fmul_rn(sl, s3);
+      }
+      out = s;
+      if (a.freqs != nullptr) {
+        const float other = gv_dpp<0xB1>(out);
+        if (row < a.rope_rows) {
+          const T* fq = reinterpret_cast<const T*>(a.freqs) + (size_t)t * a.head_dim;  // token t's (cos, sin) rows
+          const int pr = (row % a.head_dim) >> 1;
+          const float c = ElemTraits<T>::load(fq, (size_t)pr * 2);
+          const float sn = ElemTraits<T>::load(fq, (size_t)pr * 2 + 1);
+          out = (row & 1) ? __fadd_rn(__fmul_rn(out, c), __fmul_rn(other, sn)) : __fsub_rn(__fmul_rn(out, c), __fmul_rn(other, sn));
+        }
+      }
+      if (mine && row < N) ElemTraits<T>::store(yo, (size_t)t * N + row, cc_opaque_f32(out));
+    }
+    __syncthreads();  // sm_part is reused by the next row group
+  }
+}
+
+// The geometry of a multi launch: pick_cfg's choice for the shape, with fewer rows / column steps in flight where NT * XS input
+// chunks per lane leave no room for it (results do not depend on either number).  Only fp32 needs it (DESIGN.md §2.10 has the
+// register figures of every instantiation): 16 chunks x 3 tokens fit at 2 x 2, and 4 x 8 at 8 chunks x 4 tokens becomes 4 x 4.
+static GvCfg pick_multi_cfg(const GemvArgs& a, int vec, int xs, int nt) {
+  GvCfg c = pick_cfg(a, vec);
+  if (vec == 4 && xs == 16 && nt >= 3) c.rb = c.cu = 2;
+  if (vec == 4 && xs == 8 && nt == 4 && c.rb == 4 && c.cu == 8) c.cu = 4;
+  return c;
+}
+
+template <typename T, bool SWIGLU, int RB, int CU, int XS, int NT>
+static void launch_multi_cfg(const GemvArgs& a, hipStream_t st, int cap) {
+  int blocks = (a.N + RB - 1) / RB;
+  if (blocks > cap) blocks = cap;
+  hipLaunchKernelGGL((gemv_multi_kernel<T, SWIGLU, RB, CU, XS, NT>), dim3(blocks), dim3(kGvThreads), 0, st, a);
+}
+
+template <typename T, int NT>
+static int launch_gemv_multi(const GemvArgs& a, hipStream_t st) {
+  const int vec = 16 / (int)sizeof(T);
+  const int nseg = (a.K / vec + 63) / 64, nstep = (nseg + kGvWaves - 1) / kGvWaves;
+  const int xs = nstep <= 2 ? 2 : nstep <= 8 ? 8 : 16;
+  const GvCfg c = pick_multi_cfg(a, vec, xs, NT);
+  if (nstep > 16 || c.cu > xs) return CC_ERR_UNSUPPORTED;
+  const int key = (a.W3 ? 100000 : 0) + xs * 1000 + c.rb * 10 + c.cu;
+  // (instantiations that would spill are not built: pick_multi_cfg never selects them)
+  constexpr bool kF32 = sizeof(T) == 4;
+  constexpr bool kWide16 = !(kF32 && NT >= 3), kNarrow16 = kF32 && NT == 3, kWide8 = !(kF32 && NT == 4);
+  switch (key) {
+    case 2022: launch_multi_cfg<T, false, 2, 2, 2, NT>(a, st, c.cap); break;
+    case 2042: launch_multi_cfg<T, false, 4, 2, 2, NT>(a, st, c.cap); break;
+    case 2082: launch_multi_cfg<T, false, 8, 2, 2, NT>(a, st, c.cap); break;
+    case 8022: launch_multi_cfg<T, false, 2, 2, 8, NT>(a, st, c.cap); break;
+    case 8024: launch_multi_cfg<T, false, 2, 4, 8, NT>(a, st, c.cap); break;
+    case 8044: launch_multi_cfg<T, false, 4, 4, 8, NT>(a, st, c.cap); break;
+    case 8028: launch_multi_cfg<T, false, 2, 8, 8, NT>(a, st, c.cap); break;
+    case 8048:
+      if constexpr (kWide8) launch_multi_cfg<T, false, 4, 8, 8, NT>(a, st, c.cap); else return CC_ERR_UNSUPPORTED;
+      break;
+    case 16044:
+      if constexpr (kWide16) launch_multi_cfg<T, false, 4, 4, 16, NT>(a, st, c.cap); else return CC_ERR_UNSUPPORTED;
+      break;
+    case 16028:
+      if constexpr (kWide16) launch_multi_cfg<T, false, 2, 8, 16, NT>(a, st, c.cap); else return CC_ERR_UNSUPPORTED;
+      break;
+    case 16022:
+      if constexpr (kNarrow16) launch_multi_cfg<T, false, 2, 2, 16, NT>(a, st, c.cap); else return CC_ERR_UNSUPPORTED;
+      break;
+    case 102022: launch_multi_cfg<T, true, 2, 2, 2, NT>(a, st, c.cap); break;
+    case 102042: launch_multi_cfg<T, true, 4, 2, 2, NT>(a, st, c.cap); break;
+    case 108022: launch_multi_cfg<T, true, 2, 2, 8, NT>(a, st, c.cap); break;
+    case 108024: launch_multi_cfg<T, true, 2, 4, 8, NT>(a, st, c.cap); break;
+    case 108028: launch_multi_cfg<T, true, 2, 8, 8, NT>(a, st, c.cap); break;
+    case 116024:
+      if constexpr (kWide16) launch_multi_cfg<T, true, 2, 4, 16, NT>(a, st, c.cap); else return CC_ERR_UNSUPPORTED;
+      break;
+    case 116022:
+      if constexpr (kNarrow16) launch_multi_cfg<T, true, 2, 2, 16, NT>(a, st, c.cap); else return CC_ERR_UNSUPPORTED;
+      break;
+    default: return CC_ERR_UNSUPPORTED;
+  }
+  CC_LAUNCH_CHECK();
+  return CC_OK;
+}
+
+template <typename T>
+static int launch_gemv_multi_t(const GemvArgs& a, int nt, hipStream_t st) {
+  switch (nt) {
+    case 1: return launch_gemv<T>(a, st);  // one token: the single-vector kernel itself
+    case 2: return launch_gemv_multi<T, 2>(a, st);
+    case 3: return launch_gemv_multi<T, 3>(a, st);
+    default: break;
+  }
+  if (sizeof(T) == 4 && (size_t)a.K * sizeof(T) > 32 * 1024) {
+    // fp32 rows beyond 32 KiB (16 chunks per lane): four tokens' inputs are the whole register file (256 + 256), and every
+    // geometry of that instantiation spills to scratch.  Two launches of two tokens each instead: the one shape class whose
+    // weights pass twice (same bits: a row's arithmetic does not depend on its neighbours)
+    GemvArgs b = a;
+    const size_t es = sizeof(T);
+    b.x = (const char*)a.x + 2 * (size_t)a.K * es;
+    if (a.delta) b.delta = (const char*)a.delta + 2 * (size_t)a.K * es;
+    if (a.h_out) b.h_out = (char*)a.h_out + 2 * (size_t)a.K * es;
+    if (a.freqs) b.freqs = (const char*)a.freqs + 2 * (size_t)a.head_dim * es;
+    b.y = (char*)a.y + 2 * (size_t)a.N * es;
+    const int rc = launch_gemv_multi<T, 2>(a, st);
+    return rc != CC_OK ? rc : launch_gemv_multi<T, 2>(b, st);
+  }
+  return launch_gemv_multi<T, 4>(a, st);
+}
+
 }  // namespace
+
+extern "C" int cc_gemv_fused_multi(const void* W, const void* W3, const void* x, const void* delta, const void* norm_w, float eps,
+                                   void* h_out, const void* bias, const void* freqs, int32_t rope_rows, int32_t head_dim, void* y,
+                                   int32_t N, int32_t K, int32_t T, int32_t dtype, cc_stream_t stream) {
+  CC_ENTRY();
+  if (!W || !x || !y || N <= 0 || K <= 0 || !cc_dt_ok(dtype)) return CC_ERR_BAD_ARG;
+  if (T < 1 || T > CC_GEMV_MULTI_MAX_T) return CC_ERR_BAD_ARG;
+  if ((delta || h_out) && !norm_w) return CC_ERR_BAD_ARG;
+  if (freqs && (W3 || rope_rows < 0 || rope_rows > N || head_dim <= 0 || (head_dim & 1) || (rope_rows % head_dim))) return CC_ERR_BAD_ARG;
+  if (W3 && bias) return CC_ERR_BAD_ARG;
+  const int vec = 16 / (int)cc_dt_size(dtype);
+  if (K % vec) return CC_ERR_UNSUPPORTED;
+  if ((size_t)K * cc_dt_size(dtype) > 64 * 1024) return CC_ERR_UNSUPPORTED;
+  GemvArgs a{W, W3, x, delta, norm_w, bias, freqs, h_out, y, eps, N, K, freqs ? rope_rows : 0, freqs ? head_dim : 2};
+  hipStream_t st = (hipStream_t)stream;
+  switch (dtype) {
+    case CC_DT_F32: return launch_gemv_multi_t<float>(a, T, st);
+    case CC_DT_BF16: return launch_gemv_multi_t<bf16_t>(a, T, st);
+    default: return launch_gemv_multi_t<f16_t>(a, T, st);
+  }
+}
 
 extern "C" int cc_gemv_fused(const void* W, const void* W3, const void* x, const void* delta, const void* norm_w, float eps,
                              void* h_out, const void* bias, const void* freqs, int32_t rope_rows, int32_t head_dim, void* y,

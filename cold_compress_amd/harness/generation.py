@@ -357,6 +357,8 @@ def _recover_token(model, cur_token, input_pos, decode_fn, nt, npb, forced, attn
     return nt, npb
 
 
+_MAX_BLOCK = 4  # glue.GEMV_MULTI_MAX_T: the most input vectors cc_gemv_fused_multi takes
+
 _L2_HANDOFF_DEMOTED = set()  # device indices on which the recovery path demoted the L2-resident hand-off: generate() restores them
 
 
@@ -465,9 +467,20 @@ def decode_n_tokens(model, cur_token, input_pos, decode_one_token, num_new_token
     at when that copy has completed — possibly a few tokens late: the loop then rewinds to the failed token (everything launched
     behind it did nothing).  The loop itself never synchronises the device ONLY without `terminator_ids`: with them, `nt in
     terminator_ids` reads the sampled token on the host every step (the reference's loop does the same, generation_utils.py:207-210),
-    and the status copy is then always complete one token later."""
+    and the status copy is then always complete one token later.
+    `forced_block` (ours; default 1: this loop as it was): with B > 1 on a model whose `block_eligible(attn_top_k)` holds, steps whose
+    INPUT tokens are known run in blocks of up to min(B, 4): steps i .. i+T-1 go through `model.forward_block` when steps i .. i+T-2
+    are forced (their outputs, the inputs of i+1 .. i+T-1, are then known) — every dense product of a layer is one pass over its
+    weights for the T tokens, the layer's T cache steps run in order, and the T results are committed in order exactly as the single
+    steps commit them (the last step of a block may be a free one: its token is drawn from its own row at its own position).
+    Blocks are eager launches; everything else — free steps, fewer than two known inputs, an ineligible model — runs through
+    `decode_one_token` as before.  A single-launch step that fails INSIDE a block cannot be rewound token-wise (earlier layers have
+    committed all T tokens): with `recover` the status word is read once behind each block, and a set word raises."""
     new_tokens, new_probs, incs = [], [], []
     recover = kw.pop("recover", None)
+    block = kw.pop("forced_block", 1)
+    block = 1 if block is None else max(1, min(int(block), _MAX_BLOCK))
+    use_blocks = block > 1 and prefix is not None and len(prefix) > 0 and bool(getattr(model, "block_eligible", lambda *_: False)(attn_top_k))
     tp = _tp_world() > 1
     recover = (cur_token.is_cuda and not tp) if recover is None else bool(recover)
     watch = _StatusWatch(cur_token.device) if recover and not tp else None
@@ -489,9 +502,42 @@ def decode_n_tokens(model, cur_token, input_pos, decode_one_token, num_new_token
         incs.append(1)
         cur = nt.view(1, -1)
 
+    def block_len(k):
+        """how many steps from k on run as one block: all but the last must be forced; 0: step k runs on its own."""
+        if not use_blocks:
+            return 0
+        T = min(block, num_new_tokens - k, len(prefix) - k + 1)
+        return T if T >= 2 else 0
+
+    def run_block(k, T):
+        """steps k .. k+T-1 through model.forward_block; commits T results in order."""
+        idx = torch.cat([cur.view(1, 1), prefix[k:k + T - 1].view(1, -1).to(cur.dtype)], 1)
+        pos = input_pos + torch.arange(T, device=input_pos.device, dtype=input_pos.dtype)
+        logits = model.forward_block(idx, pos, attn_top_k=attn_top_k)
+        if recover and cur_token.is_cuda and _collective_status(cur_token.device):
+            from ..attention_utils import raise_single_launch_failure
+
+            try:
+                raise_single_launch_failure(cur_token.device)  # (clears the word)
+            except Exception as e:
+                raise type(e)(f"in the block of {T} forced decode steps starting at position {int(pos[0])}: {e}") from None
+        for t in range(T):
+            row = logits[:, t:t + 1]
+            if kw.get("temperature") is None:
+                nt, npb = greedy(row, forced_at(k + t))
+            else:
+                nt, npb = sample(row, forced_at(k + t), kw["temperature"], kw.get("top_k"), kw.get("seed", 0), pos[t:t + 1])
+            commit(k + t, nt, npb)
+
     while True:
         running = i < num_new_tokens and not stopped
-        if running:
+        T = block_len(i) if running else 0
+        drain = T > 0 and watch is not None and watch.outstanding()  # (single steps still unjudged: their verdicts first)
+        if T > 0 and not drain:
+            run_block(i, T)
+            i += T
+            running = i < num_new_tokens and not stopped
+        elif running and not drain:
             nt, npb = decode_one_token(model, cur, input_pos, next_token=forced_at(i), attn_top_k=attn_top_k, **kw)
             if recover and tp:  # collective and synchronous (opt-in): every rank takes the same branch
                 nt, npb = _recover_token(model, cur, input_pos, decode_one_token, nt, npb, forced_at(i), attn_top_k, kw)
@@ -505,7 +551,7 @@ def decode_n_tokens(model, cur_token, input_pos, decode_one_token, num_new_token
                 break
             continue
         while watch.outstanding():
-            r = watch.ready() if running else watch.wait_oldest()
+            r = watch.ready() if (running and not drain) else watch.wait_oldest()
             if r is None:
                 break
             f, st = r

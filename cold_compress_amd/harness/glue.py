@@ -3,7 +3,7 @@
 These are NOT part of the cache/attention hot path — they are the model-side code around it
 (ref: model.py:317-327, 375-387, 442-443, 452-457, 507-519), which the reference leaves to ~45 eager elementwise
 launches per layer or to torch.compile.  On device tensors they call the C ABI (`cc_add_rmsnorm`, `cc_qkv_rope`,
-`cc_silu_mul`, `cc_gemv_fused`, `cc_softmax_argmax`, `cc_sample_topk`); CPU tensors raise — there is no host path in the package (the
+`cc_silu_mul`, `cc_gemv_fused`, `cc_gemv_fused_multi`, `cc_softmax_argmax`, `cc_sample_topk`); CPU tensors raise — there is no host path in the package (the
 CPU model-wiring test brings its own eager twins: tests/host_glue.py).
 """
 import ctypes as C
@@ -144,6 +144,36 @@ def gemv_fused(weight, x, w3=None, delta=None, norm_weight=None, eps=1e-5, h_out
     _abi.call("cc_gemv_fused", _p(weight), _p(w3), _p(xc), _p(dc), _p(norm_weight),
               float(eps), _p(h_out), _p(bias), _p(fc), int(rope_rows), int(head_dim),
               _p(y), N, K, _DT[weight.dtype], _stream())
+    return y
+
+
+GEMV_MULTI_MAX_T = 4  # CC_GEMV_MULTI_MAX_T (include/coldcompress.h)
+
+
+def gemv_fused_multi(weight, x, w3=None, delta=None, norm_weight=None, eps=1e-5, h_out=None, bias=None, freqs=None, rope_rows=0,
+                     head_dim=0):
+    """gemv_fused for T input vectors from ONE pass over the weights (cc_gemv_fused_multi), 1 <= T <= 4: x [T, K] (delta, h_out
+    likewise), freqs [T, head_dim / 2, 2] -> [T, N].  Row t is bit-identical to gemv_fused on row t.  Dense weights only: the int8,
+    int4 and MXFP4 GEMVs have no multi form (an error, not a fallback — callers ask Transformer.block_eligible first)."""
+    if weight.dtype not in _DT:
+        raise _abi.ColdCompressError(f"gemv_fused_multi: dense weights only, got {weight.dtype}")
+    if not x.is_cuda:
+        _host(x, "gemv_fused_multi input")
+    N, K = weight.shape
+    if x.dim() != 2 or x.shape[1] != K:
+        raise _abi.ColdCompressError(f"gemv_fused_multi: x must be [T, {K}], got {tuple(x.shape)}")
+    T = x.shape[0]
+    for name, t, shape in (("delta", delta, (T, K)), ("h_out", h_out, (T, K)), ("freqs", freqs, (T, head_dim // 2, 2))):
+        if t is not None and tuple(t.shape) != shape:
+            raise _abi.ColdCompressError(f"gemv_fused_multi: {name} must be {list(shape)}, got {tuple(t.shape)}")
+    if h_out is not None and not h_out.is_contiguous():
+        raise _abi.ColdCompressError("gemv_fused_multi: h_out must be contiguous")
+    xc = x.contiguous()
+    dc = delta.contiguous() if delta is not None else None
+    fc = freqs.contiguous() if freqs is not None else None
+    y = torch.empty((T, N), dtype=weight.dtype, device=weight.device)
+    _abi.call("cc_gemv_fused_multi", _p(weight), _p(w3), _p(xc), _p(dc), _p(norm_weight), float(eps), _p(h_out), _p(bias), _p(fc),
+              int(rope_rows), int(head_dim), _p(y), N, K, T, _DT[weight.dtype], _stream())
     return y
 
 

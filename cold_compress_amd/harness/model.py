@@ -163,6 +163,29 @@ class Attention(nn.Module):
             return self.prompt_compressor(input_pos, k_val, v_val, attn=attn)
         return input_pos, k_val, v_val, attn
 
+    def decode_attend(self, q, k, v, input_ids, input_pos, attn_top_k=1.0):
+        """One decode token's insert + attention + state update on q [1,HQ,1,D], k / v [1,H,1,D] -> y [1,HQ,1,D].  The ONE place
+        this sequence lives: forward() runs it for its token, TransformerBlock.forward_block for each token of a block in turn."""
+        cache = self.kv_cache
+        ck = {"input_ids": input_ids}
+        if (self.fuse_decode_step and type(cache) in (KVCacheHeavyHitter, KVCacheRecentGlobal, KVCacheFull, KVCacheRandom, KVCacheL2,
+                                                      KVCacheHybrid)
+                and cache.supports_fused_step() and attn_top_k == 1.0):
+            # one or two launches per layer: insert folded into the K/V streaming pass, history update + next eviction
+            # scoring folded into the combine pass (bit-identical to the three-call sequence below)
+            return cache.decode_step(q, k, v, input_pos, input_ids=input_ids) if type(cache) is KVCacheHybrid else cache.decode_step(q, k, v, input_pos)
+        kc, vc, kv_mask = cache.update_kv(input_pos, k, v, False, **ck)  # insert first, then attend
+        hist = cache.fused_history() if (self.fuse_state_update and type(cache) in (KVCacheHeavyHitter, KVCacheHybrid)
+                                         and attn_top_k == 1.0) else None
+        fuse = hist is not None
+        y, attn = scaled_dot_product_attention(
+            q, kc, vc, attn_mask=kv_mask, attn_top_k=attn_top_k, return_attn=cache.return_attn() and not fuse,
+            group_mean=True, history=hist)
+        if fuse:
+            cache._state_fused = True
+        cache.update_state(input_pos, k, v, False, attn, **ck)
+        return y
+
     def forward(self, x, input_ids, freqs_cis, mask, is_prefill, input_pos=None, attn_top_k=1.0, fused=None):
         """The glue of ref: model.py:363-432, GQA-aware (no repeat_interleave).
         `fused = (delta, norm, h_out)`: single-token decode on the device — x is the un-normalised residual stream,
@@ -188,31 +211,15 @@ class Attention(nn.Module):
             # split + RoPE(q, k) + head-major layout in one launch (ref: model.py:375-387)
             q, k, v = glue.qkv_rope(self.wqkv(x), freqs_cis, self.n_head, self.n_local_heads, self.head_dim)
         cache = self.kv_cache
-        ck = {"input_ids": input_ids}
-        if (not is_prefill and self.fuse_decode_step and type(cache) in (KVCacheHeavyHitter, KVCacheRecentGlobal, KVCacheFull, KVCacheRandom, KVCacheL2,
-                                                                          KVCacheHybrid)
-                and cache.supports_fused_step() and attn_top_k == 1.0):
-            # one or two launches per layer: insert folded into the K/V streaming pass, history update + next eviction
-            # scoring folded into the combine pass (bit-identical to the three-call sequence below)
-            y = cache.decode_step(q, k, v, input_pos, input_ids=input_ids) if type(cache) is KVCacheHybrid else cache.decode_step(q, k, v, input_pos)
-        elif not is_prefill:
-            kc, vc, kv_mask = cache.update_kv(input_pos, k, v, False, **ck)  # insert first, then attend
-            hist = cache.fused_history() if (self.fuse_state_update and type(cache) in (KVCacheHeavyHitter, KVCacheHybrid)
-                                             and attn_top_k == 1.0) else None
-            fuse = hist is not None
-            y, attn = scaled_dot_product_attention(
-                q, kc, vc, attn_mask=kv_mask, attn_top_k=attn_top_k, return_attn=cache.return_attn() and not fuse,
-                group_mean=True, history=hist)
-            if fuse:
-                cache._state_fused = True
-            cache.update_state(input_pos, k, v, False, attn, **ck)
+        if not is_prefill:
+            y = self.decode_attend(q, k, v, input_ids, input_pos, attn_top_k)
         else:
             bands = cache.attn_bands(seqlen) if hasattr(cache, "attn_bands") else ()  # hybrid profiling side outputs
             y, attn = scaled_dot_product_attention(q, k, v, attn_mask=mask, return_attn=cache.return_attn(),
                                                    is_causal=True, bands=bands)
             input_pos, k, v, attn = self.compress_prompt(input_pos, k, v, attn)
-            cache.update_kv(input_pos, k, v, True, **ck)
-            cache.update_state(input_pos, k, v, True, attn, **ck)
+            cache.update_kv(input_pos, k, v, True, input_ids=input_ids)
+            cache.update_state(input_pos, k, v, True, attn, input_ids=input_ids)
         if fused is not None:
             return glue.gemv_fused(self.wo.weight, y, **_quant(self.wo)).view(1, 1, -1)
         y = y.transpose(1, 2).contiguous().view(bsz, seqlen, self.dim)
@@ -244,6 +251,45 @@ class TransformerBlock(nn.Module):
         a = att(n1, input_ids, freqs_cis, mask, is_prefill, input_pos, attn_top_k=attn_top_k)
         h, n2 = self.ffn_norm(x, a)  # h = x + attn
         return h, ffn(n2)
+
+
+    def device_fused(self, x):
+        """forward()'s condition for the six-launch decode branch, for a tensor like `x`."""
+        att, ffn = self.attention, self.feed_forward
+        return bool(self.fuse_gemv and x.is_cuda
+                    and glue.gemv_supported(att.wqkv.weight, att.wo.weight, ffn.w1.weight, ffn.w3.weight, ffn.w2.weight))
+
+    def forward_block(self, x, delta, input_ids, input_pos, freqs_cis, attn_top_k=1.0):
+        """forward() for T decode tokens whose inputs are all known: x, delta [1, T, dim], input_ids [1, T], input_pos [T],
+        freqs_cis [T, D/2, 2] -> (h, f) like forward().  Every dense product is ONE pass over its weights for the T tokens
+        (cc_gemv_fused_multi: row t bit-identical to the single-token launch); the T cache steps run one after the other through
+        Attention.decode_attend, as the token-by-token loop runs them — layer l at token t needs layer l - 1 at token t and this
+        layer's cache behind tokens < t, both of which exist in this order.  CPU tensors (tests/cpu_twin.py): forward() row by
+        row, a correctness twin."""
+        att, ffn = self.attention, self.feed_forward
+        T = x.shape[1]
+        if not x.is_cuda:
+            outs = [self.forward(x[:, t:t + 1], None if delta is None else delta[:, t:t + 1], input_ids[:, t:t + 1], input_pos[t:t + 1],
+                                 False, freqs_cis[t:t + 1], None, attn_top_k=attn_top_k) for t in range(T)]
+            return torch.cat([o[0] for o in outs], 1), torch.cat([o[1] for o in outs], 1)
+        if not self.device_fused(x):
+            raise ColdCompressError("forward_block needs the device-fused decode branch (Transformer.block_eligible)")
+        HQ, H, D = att.n_head, att.n_local_heads, att.head_dim
+        x2 = x.view(T, -1)
+        h1 = torch.empty_like(x2)
+        qkv = glue.gemv_fused_multi(att.wqkv.weight, x2, delta=None if delta is None else delta.view(T, -1),
+                                    norm_weight=self.attention_norm.weight, eps=self.attention_norm.eps, h_out=h1, bias=att.wqkv.bias,
+                                    freqs=freqs_cis, rope_rows=(HQ + H) * D, head_dim=D)
+        ys = []
+        for t in range(T):
+            row = qkv[t]
+            ys.append(att.decode_attend(row[: HQ * D].view(1, HQ, 1, D), row[HQ * D: (HQ + H) * D].view(1, H, 1, D),
+                                        row[(HQ + H) * D:].view(1, H, 1, D), input_ids[:, t:t + 1], input_pos[t:t + 1], attn_top_k).view(1, -1))
+        a = glue.gemv_fused_multi(att.wo.weight, torch.cat(ys))
+        h2 = torch.empty_like(x2)
+        g = glue.gemv_fused_multi(ffn.w1.weight, h1, w3=ffn.w3.weight, delta=a, norm_weight=self.ffn_norm.weight, eps=self.ffn_norm.eps,
+                                  h_out=h2)
+        return h2.view(1, T, -1), glue.gemv_fused_multi(ffn.w2.weight, g).view(1, T, -1)
 
 
 class Transformer(nn.Module):
@@ -324,3 +370,47 @@ class Transformer(nn.Module):
             return glue.gemv_fused(self.output.weight, x, delta=delta, norm_weight=self.norm.weight, eps=self.norm.eps,
                                    **_quant(self.output)).view(1, 1, -1)
         return self.output(self.norm(x, delta)[1])
+
+    def block_eligible(self, attn_top_k=1.0):
+        """True when forward_block computes what the token-by-token decode computes, from one pass over the weights per block:
+        every layer on the device-fused decode branch over dense weights, no single-launch QKV step, full attention, no analysis
+        cache, no cache that quantises in reference mode (its batched round trip behind the last layer, flush_quantized, would
+        run after later tokens have read the layer's cache; the fused quantised modes are fine), one rank."""
+        from ..cache import KVCacheAnalysis
+        from .generation import _tp_world
+
+        if attn_top_k != 1.0 or _tp_world() > 1 or self.freqs_cis is None:
+            return False
+        dense = (torch.float32, torch.bfloat16, torch.float16)
+        probe = self.tok_embeddings.weight
+        on_device = probe.is_cuda  # (CPU tensors exist under tests/cpu_twin.py only: forward_block's row-by-row twin serves them)
+        if self.output.weight.dtype not in dense or (on_device and not (self.output.bias is None and glue.gemv_supported(self.output.weight))):
+            return False
+        for layer in self.layers:
+            att, ffn, cache = layer.attention, layer.feed_forward, layer.attention.kv_cache
+            if any(w.dtype not in dense for w in (att.wqkv.weight, att.wo.weight, ffn.w1.weight, ffn.w3.weight, ffn.w2.weight)):
+                return False
+            if (on_device and not layer.device_fused(probe)) or att.fuse_qkv_step or cache is None or isinstance(cache, KVCacheAnalysis):
+                return False
+            if cache.quantize and not cache.fused_quant:
+                return False
+        return True
+
+    def forward_block(self, idx, input_pos, attn_top_k=1.0) -> Tensor:
+        """T decode steps whose input tokens are known, layer by layer: idx [1, T], input_pos [T] (consecutive positions) ->
+        logits [1, T, V], row t equal to forward(idx[:, t:t+1], input_pos[t:t+1], is_prefill=False)'s, and every cache left as the
+        T calls leave it.  Device tensors need block_eligible(); CPU tensors (tests/cpu_twin.py) run the same order row by row."""
+        assert self.freqs_cis is not None, "Caches must be initialized first"
+        T = idx.shape[1]
+        if idx.is_cuda and not (1 <= T <= glue.GEMV_MULTI_MAX_T and self.block_eligible(attn_top_k)):
+            raise ColdCompressError(f"forward_block: {T} tokens on a model that is not block_eligible (or more than {glue.GEMV_MULTI_MAX_T})")
+        freqs_cis = self.freqs_cis[input_pos]
+        x, delta = self.tok_embeddings(idx), None
+        for layer in self.layers:
+            x, delta = layer.forward_block(x, delta, idx, input_pos, freqs_cis, attn_top_k=attn_top_k)
+        if not x.is_cuda:
+            if self.batch_quant_flush:
+                flush_quantized([layer.attention.kv_cache for layer in self.layers])
+            return torch.cat([self.output(self.norm(x[:, t:t + 1], delta[:, t:t + 1])[1]) for t in range(T)], 1)
+        return glue.gemv_fused_multi(self.output.weight, x.view(T, -1), delta=delta.view(T, -1), norm_weight=self.norm.weight,
+                                     eps=self.norm.eps).view(1, T, -1)

@@ -777,6 +777,20 @@ int cc_gemv_fused(const void* W, const void* W3, const void* x, const void* delt
                   void* h_out, const void* bias, const void* freqs, int32_t rope_rows, int32_t head_dim, void* y,
                   int32_t N, int32_t K, int32_t dtype, cc_stream_t stream);
 
+/* cc_gemv_fused for T input vectors from ONE pass over the weights, 1 <= T <= CC_GEMV_MULTI_MAX_T: a block of decode steps whose
+ * input tokens are known (teacher forcing, the tail of a long prompt) streams W once instead of T times.
+ *   x, delta (or NULL), h_out (or NULL): [T, K];  freqs (or NULL): [T, head_dim / 2, 2], row t the (cos, sin) of token t's position;
+ *   y: [T, N];  W, W3, norm_w, bias: as cc_gemv_fused, shared by the T rows.
+ * Row t of y and of h_out is BIT-IDENTICAL to cc_gemv_fused called with row t of x, delta and freqs, for every dtype, form and
+ * shape cc_gemv_fused serves (a row's arithmetic there depends neither on the rows and column steps in flight nor on the grid, and
+ * is kept per token here).  Same argument checks and CC_ERR_UNSUPPORTED cases; T outside 1 .. CC_GEMV_MULTI_MAX_T:
+ * CC_ERR_BAD_ARG.  Dense weights only.  A plain grid: no workgroup waits for another.  Arguments are validated before any launch:
+ * an error writes nothing. */
+#define CC_GEMV_MULTI_MAX_T 4
+int cc_gemv_fused_multi(const void* W, const void* W3, const void* x, const void* delta, const void* norm_w, float eps,
+                        void* h_out, const void* bias, const void* freqs, int32_t rope_rows, int32_t head_dim, void* y,
+                        int32_t N, int32_t K, int32_t T, int32_t dtype, cc_stream_t stream);
+
 /* The same decode-time dense layer over INT8 WEIGHT-ONLY matrices (the weight-only int8 checkpoint format, ref: quantize.py
  * WeightOnlyInt8QuantHandler / WeightOnlyInt8Linear): W, W3 int8 [N, K] row major, one scale per output row, scales / scales3 [N]
  * in `dtype`, which is also the activation, bias, freqs and output dtype.
