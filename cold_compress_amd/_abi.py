@@ -73,6 +73,8 @@ SIGNATURES = {
     "cc_gemv_fused_w8": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
     "cc_gemv_fused_w4": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     "cc_gemv_fused_mx4": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
+    "cc_gemv_fused_w8_multi": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "cc_gemv_fused_mx4_multi": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     "cc_kv_requant": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "cc_kv_requant_pair": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
     "cc_kv_requant_batch": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
@@ -185,6 +187,8 @@ DEVICE_ONLY = {"cc_error_string", "cc_device_info", "cc_decode_step_single_launc
                "cc_gemv_fused_w8",  # int8 weight-only GEMV: its checker is the fp32 torch composition of the reference's formula
                "cc_gemv_fused_w4",  # int4 group-wise weight-only GEMV: likewise
                "cc_gemv_fused_mx4",  # MXFP4 weight-only GEMV: likewise (and bit-exact known-answer cases)
+               # the two for up to 4 input vectors: their checkers are cc_gemv_fused_w8 / cc_gemv_fused_mx4 themselves, row by row, bit for bit
+               "cc_gemv_fused_w8_multi", "cc_gemv_fused_mx4_multi",
                "cc_sample_topk_workspace_bytes", "cc_sample_topk",  # sampling tail: its checker is the numpy twin of the contract (tests/sample_twin.py)
                # the fused quantised cache's ring and hybrid steps: their checker is the same policy's 16-bit step on the dequantised values
                "cc_decode_step_heavy_hitter_ring_quant", "cc_decode_step_hybrid_quant_rc", "cc_decode_step_hybrid_quant_single_launch",

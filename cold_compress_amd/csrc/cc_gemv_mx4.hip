@@ -18,6 +18,10 @@
 // The RMSNorm prologue runs in the 16-bit kernel's layout (8 elements per lane and chunk, the same chunk order, the same fp32
 // chains and the same LDS reduction): h_out and the normalised input are bit-identical to cc_gemv_fused's.  The normalised vector
 // is passed to the lanes that multiply it through LDS (K * 2 bytes, norm forms only).
+//
+// TWO COPIES: gemv_mx4_multi_kernel at the end of this file (the same product for up to four input vectors) repeats gemv_mx4_kernel's weight tile,
+// prologue, row loop and epilogue, token by token, and promises the same bits.  A change to the chunk ownership, a chain's order, a
+// reduction or a rounding point here has to be made there too (tests/test_gpu_gemv_wo_multi.py compares the two bit for bit).
 #include <cstdio>
 #include <cstdlib>
 
@@ -326,4 +330,351 @@ extern "C" int cc_gemv_fused_mx4(const uint8_t* W, const uint8_t* scales, const 
   if ((size_t)K * sizeof(bf16_t) > 64 * 1024) return CC_ERR_UNSUPPORTED;
   GemvMx4Args a{W, W3, scales, scales3, x, delta, norm_w, bias, freqs, h_out, y, eps, N, K, freqs ? rope_rows : 0, freqs ? head_dim : 2};
   return launch_gemv_mx4(a, (hipStream_t)stream);
+}
+
+// ---- the same product for NT input vectors from ONE pass over the MXFP4 weights (cc_gemv_fused_mx4_multi): cc_gemv.hip's
+//      gemv_multi_kernel for this file's kernel.  Row t of y / h_out is BIT-IDENTICAL to gemv_mx4_kernel on row t of x / delta / freqs:
+//      the lane that owns a 16-byte code chunk, the order of that lane's dot2 chain, gv_wave_sum, the meet of a row's WS waves (WS
+//      is launch_gemv_mx4's function of K) and every rounding point of the prologue and the epilogue are gemv_mx4_kernel's, kept per
+//      token.  A code register and its scale byte are loaded once and DECODED once (the sixteen v_cvt_scalef32_pk_bf16_fp4 of a chunk,
+//      exact) and then feed NT accumulator chains, so the conversion cost per token falls with NT.  None of that depends on RB, CU or
+//      the grid.  x, delta, h_out: [NT, K]; y: [NT, N]; freqs: [NT, head_dim / 2, 2].  A plain grid: no workgroup waits for another.
+//
+//      The RMSNorm prologue keeps ONE staging buffer (the single kernel's K * 2 bytes of dynamic LDS): every token's h = x + delta and
+//      sum of squares are formed first, in the 16-bit kernel's chunk layout, with h parked in the registers that will hold the token's
+//      input (4 * XS uint4: a lane never owns more 8-element chunks than that); then the tokens pass through the buffer one after the
+//      other — normalise token t into it, barrier, every lane picks up the 64-byte pieces it multiplies, barrier, the next token.
+namespace {
+
+__device__ __forceinline__ void deq_mx4_word(uint32_t w, float scale, uint32_t* p) {
+  p[0] = cc_mx4_dequant2<bf16_t, 0>(w, scale);
+  p[1] = cc_mx4_dequant2<bf16_t, 1>(w, scale);
+  p[2] = cc_mx4_dequant2<bf16_t, 2>(w, scale);
+  p[3] = cc_mx4_dequant2<bf16_t, 3>(w, scale);
+}
+// one chunk's 32 scaled weights as 16 bf16 pairs in column order (chunk_mx4's conversions, done once for the NT tokens)
+__device__ __forceinline__ void deq_mx4(uint4 w, uint32_t sb, uint32_t (&p)[16]) {
+  const float scale = __uint_as_float(sb << 23);
+  deq_mx4_word(w.x, scale, p);
+  deq_mx4_word(w.y, scale, p + 4);
+  deq_mx4_word(w.z, scale, p + 8);
+  deq_mx4_word(w.w, scale, p + 12);
+}
+__device__ __forceinline__ float dot_mx4_deq(const uint32_t (&p)[16], const uint4* xv, float acc) {  // chunk_mx4's chain
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    acc = dot2_bf16(p[4 * i], xv[i].x, acc);
+    acc = dot2_bf16(p[4 * i + 1], xv[i].y, acc);
+    acc = dot2_bf16(p[4 * i + 2], xv[i].z, acc);
+    acc = dot2_bf16(p[4 * i + 3], xv[i].w, acc);
+  }
+  return acc;
+}
+
+template <bool SWIGLU, int RB, int CU, int XS, int WS, int NT>
+__global__ __launch_bounds__(kMx4Threads) void gemv_mx4_multi_kernel(GemvMx4Args a) {
+  typedef bf16_t T;
+  constexpr int VEC = 8;
+  constexpr int RG = kMx4Waves / WS;
+  constexpr int RW = RB * RG;
+  static_assert(NT * RW <= 64 && RW % 2 == 0, "wave 0 finishes one (token, row) per lane; a RoPE pair stays in lanes l, l ^ 1");
+  extern __shared__ uint4 sm_in[];  // ONE token's normalised input at a time, norm forms only (K / 8 chunks)
+  __shared__ float sm_red[NT][kMx4Waves];
+  __shared__ float sm_part[NT][kMx4Waves][2][RB];
+  const int K = a.K, N = a.N;
+  const int nch = K / 32;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int ws = wave % WS, rg = wave / WS;
+  const int nseg = (nch + 63) / 64;
+  const int nstep = (nseg + WS - 1) / WS;
+
+  // ---- work decomposition and the code / scale-byte tile: gemv_mx4_kernel's (requested before the inputs are touched)
+  const uint4* Wv = reinterpret_cast<const uint4*>(a.W);
+  const uint4* W3v = reinterpret_cast<const uint4*>(a.W3);
+  uint4 w[RB][CU], w3[RB][CU];
+  uint32_t q[RB][CU], q3[RB][CU];
+  auto issue = [&](int r0, int s0) {  // r0: this wave's first row
+#pragma unroll
+    for (int u = 0; u < CU; u++) {
+      const int c = ((s0 + u) * WS + ws) * 64 + lane;
+      const bool cin = (s0 + u < nstep) && c < nch;
+#pragma unroll
+      for (int r = 0; r < RB; r++) {
+        const bool in = cin && (r0 + r < N);
+        const size_t off = (size_t)(r0 + r) * nch + c;
+        w[r][u] = in ? nt_load(Wv + off) : make_uint4(0, 0, 0, 0);
+        q[r][u] = in ? nt_load_u8(a.sc + off) : 127u;
+        if (SWIGLU) {
+          w3[r][u] = in ? nt_load(W3v + off) : make_uint4(0, 0, 0, 0);
+          q3[r][u] = in ? nt_load_u8(a.sc3 + off) : 127u;
+        }
+      }
+    }
+  };
+  const int row_first = blockIdx.x * RW;  // < N (the launcher sizes the grid)
+  issue(row_first + rg * RB, 0);
+
+  // ---- the NT input vectors: xin[t][4 j + i] is gemv_mx4_kernel's xv[j][i] of token t
+  uint4 xin[NT][4 * XS];
+  if (a.norm_w != nullptr) {
+    constexpr int XP = 4 * XS;
+    const int nch8 = K / VEC;
+    const int nstep8 = ((nch8 + 63) / 64 + kMx4Waves - 1) / kMx4Waves;  // <= nseg <= WS * nstep <= XP
+    const T* xg = reinterpret_cast<const T*>(a.x);
+    const T* dg = reinterpret_cast<const T*>(a.delta);
+    const T* wg = reinterpret_cast<const T*>(a.norm_w);
+    float ss[NT];
+#pragma unroll
+    for (int t = 0; t < NT; t++) ss[t] = 0.f;
+#pragma unroll
+    for (int j = 0; j < XP; j++) {
+      const int c = (j * kMx4Waves + wave) * 64 + lane;
+      const bool in = j < nstep8 && c < nch8;
+#pragma unroll
+      for (int t = 0; t < NT; t++) {
+        xin[t][j] = make_uint4(0, 0, 0, 0);
+        if (in) {
+          const size_t at = (size_t)t * K + (size_t)c * VEC;
+          Vec16<T> xl, dv;
+          float h[VEC];
+          xl.load(xg + at);
+          xl.unpack(h);
+          if (dg != nullptr) {
+            float d[VEC];
+            dv.load(dg + at);
+            dv.unpack(d);
+#pragma unroll
+            for (int e = 0; e < VEC; e++) h[e] = ElemTraits<T>::rnd(__fadd_rn(h[e], d[e]));  // model-dtype residual add
+          }
+#pragma unroll
+          for (int e = 0; e < VEC; e++) ss[t] = fmaf(h[e], h[e], ss[t]);
+          xin[t][j] = pack16<T>(h);  // (parked: the 8-element chunk c of token t's h)
+          if (a.h_out != nullptr && blockIdx.x == 0) reinterpret_cast<uint4*>(a.h_out)[(size_t)t * nch8 + c] = xin[t][j];
+        }
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < NT; t++) {
+      const float s = gv_wave_sum(ss[t]);
+      if (lane == 0) sm_red[t][wave] = s;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < NT; t++) {
+      const float tot = (sm_red[t][0] + sm_red[t][1]) + (sm_red[t][2] + sm_red[t][3]);
+      const float rs = rsqrtf(tot / (float)K + a.eps);
+#pragma unroll
+      for (int j = 0; j < XP; j++) {
+        const int c = (j * kMx4Waves + wave) * 64 + lane;
+        if (j < nstep8 && c < nch8) {
+          Vec16<T> hv, nv;
+          float h[VEC], wf[VEC], o[VEC];
+          hv.raw = xin[t][j];
+          nv.load(wg + (size_t)c * VEC);
+          hv.unpack(h);
+          nv.unpack(wf);
+#pragma unroll
+          for (int e = 0; e < VEC; e++) o[e] = ElemTraits<T>::rnd(__fmul_rn(ElemTraits<T>::rnd(cc_opaque_f32(__fmul_rn(h[e], rs))), wf[e]));
+          sm_in[c] = pack16<T>(o);
+        }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int j = 0; j < XS; j++) {
+        const int c = (j * WS + ws) * 64 + lane;
+        const bool in = j < nstep && c < nch;
+#pragma unroll
+        for (int i = 0; i < 4; i++) xin[t][4 * j + i] = in ? sm_in[4 * c + i] : make_uint4(0, 0, 0, 0);
+      }
+      if (t + 1 < NT) __syncthreads();  // the buffer is the next token's
+    }
+  } else {
+    const uint4* xg = reinterpret_cast<const uint4*>(a.x);
+#pragma unroll
+    for (int t = 0; t < NT; t++) {
+#pragma unroll
+      for (int j = 0; j < XS; j++) {
+        const int c = (j * WS + ws) * 64 + lane;
+        const bool in = j < nstep && c < nch;
+#pragma unroll
+        for (int i = 0; i < 4; i++) xin[t][4 * j + i] = in ? xg[((size_t)t * nch + c) * 4 + i] : make_uint4(0, 0, 0, 0);
+      }
+    }
+  }
+
+  T* yo = reinterpret_cast<T*>(a.y);
+  bool first = true;
+  for (int r0 = row_first; r0 < N; r0 += gridDim.x * RW) {
+    const int rw0 = r0 + rg * RB;
+    float acc[NT][RB], acc3[NT][RB];
+#pragma unroll
+    for (int t = 0; t < NT; t++) {
+#pragma unroll
+      for (int r = 0; r < RB; r++) acc[t][r] = acc3[t][r] = 0.f;
+    }
+#pragma unroll
+    for (int s0 = 0; s0 < XS; s0 += CU) {
+      if (s0 < nstep) {
+        if (!first) issue(rw0, s0);
+        first = false;
+#pragma unroll
+        for (int u = 0; u < CU; u++) {
+          const int j = s0 + u < XS ? s0 + u : XS - 1;  // beyond nstep the codes are zero-filled
+#pragma unroll
+          for (int r = 0; r < RB; r++) {
+            uint32_t p[16];
+            deq_mx4(w[r][u], q[r][u], p);  // decoded once, multiplied NT times
+#pragma unroll
+            for (int t = 0; t < NT; t++) acc[t][r] = dot_mx4_deq(p, &xin[t][4 * j], acc[t][r]);
+            if (SWIGLU) {
+              deq_mx4(w3[r][u], q3[r][u], p);
+#pragma unroll
+              for (int t = 0; t < NT; t++) acc3[t][r] = dot_mx4_deq(p, &xin[t][4 * j], acc3[t][r]);
+            }
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < NT; t++) {
+#pragma unroll
+      for (int r = 0; r < RB; r++) {
+        const float s = gv_wave_sum(acc[t][r]);
+        float s3 = 0.f;
+        if (SWIGLU) s3 = gv_wave_sum(acc3[t][r]);
+        if (lane == 0) {
+          sm_part[t][wave][0][r] = s;
+          if (SWIGLU) sm_part[t][wave][1][r] = s3;
+        }
+      }
+    }
+    __syncthreads();
+    if (wave == 0) {  // lane t * RW + l finishes row r0 + l of token t
+      const bool mine = lane < NT * RW;
+      const int t = mine ? lane / RW : 0;
+      const int l = mine ? lane % RW : 0;
+      const int g = l / RB, r = l % RB;
+      const int row = r0 + l;
+      const int rowc = row < N ? row : N - 1;
+      auto part = [&](int m) {  // the WS waves of row group g, in gemv_mx4_kernel's order
+        if (WS == 1) return sm_part[t][g][m][r];
+        if (WS == 2) return sm_part[t][2 * g][m][r] + sm_part[t][2 * g + 1][m][r];
+        return (sm_part[t][0][m][r] + sm_part[t][1][m][r]) + (sm_part[t][2][m][r] + sm_part[t][3][m][r]);
+      };
+      float s = ElemTraits<T>::rnd(cc_opaque_f32(part(0)));
+      if (a.bias != nullptr) s = ElemTraits<T>::rnd(cc_opaque_f32(__fadd_rn(s, ElemTraits<T>::load(reinterpret_cast<const T*>(a.bias), (size_t)rowc))));
+      if (SWIGLU) {
+        const float s3 = ElemTraits<T>::rnd(cc_opaque_f32(part(1)));
+        const float sl = ElemTraits<T>::rnd(__fdiv_rn(s, 1.0f + expf(-s)));  // F.silu -> dtype
+        s = __fmul_rn(sl, s3);
+      }
+      float out = s;
+      if (a.freqs != nullptr) {
+        const float other = gv_dpp<0xB1>(out);  // the pair partner lives in lane ^ 1 (r0 and RW are even)
+        if (row < a.rope_rows) {
+          const T* fq = reinterpret_cast<const T*>(a.freqs) + (size_t)t * a.head_dim;  // token t's (cos, sin) rows
+          const int pr = (row % a.head_dim) >> 1;
+          const float c = ElemTraits<T>::load(fq, (size_t)pr * 2);
+          const float sn = ElemTraits<T>::load(fq, (size_t)pr * 2 + 1);
+          out = (row & 1) ? __fadd_rn(__fmul_rn(out, c), __fmul_rn(other, sn)) : __fsub_rn(__fmul_rn(out, c), __fmul_rn(other, sn));
+        }
+      }
+      if (mine && row < N) ElemTraits<T>::store(yo, (size_t)t * N + row, cc_opaque_f32(out));
+    }
+    __syncthreads();  // sm_part is reused by the next row group
+  }
+}
+
+template <bool SWIGLU, int RB, int CU, int XS, int WS, int NT>
+static void launch_mx4_multi_cfg(const GemvMx4Args& a, hipStream_t st, int cap) {
+  constexpr int RWm = RB * (kMx4Waves / WS);
+  int blocks = (a.N + RWm - 1) / RWm;
+  if (blocks > cap) blocks = cap;
+  const size_t lds = a.norm_w != nullptr ? (size_t)a.K * sizeof(bf16_t) : 0;  // the single kernel's: one staging buffer for the NT tokens
+  hipLaunchKernelGGL((gemv_mx4_multi_kernel<SWIGLU, RB, CU, XS, WS, NT>), dim3(blocks), dim3(kMx4Threads), lds, st, a);
+}
+
+// true for the switch keys launch_gemv_mx4 serves (its MX4_CASE list): what a CC_GEMV_MX4_CFG may name
+static bool mx4_single_serves(int key) {
+#define MX4_KEY(SW, WS_, XS_, RB_, CU_) case (SW ? 100000 : 0) + WS_ * 10000 + XS_ * 1000 + RB_ * 10 + CU_:
+  switch (key) {
+    MX4_KEY(false, 1, 1, 2, 1) MX4_KEY(false, 1, 1, 4, 1) MX4_KEY(false, 1, 1, 8, 1)
+    MX4_KEY(false, 2, 1, 2, 1) MX4_KEY(false, 2, 1, 4, 1) MX4_KEY(false, 2, 1, 8, 1)
+    MX4_KEY(false, 4, 1, 2, 1) MX4_KEY(false, 4, 1, 4, 1) MX4_KEY(false, 4, 1, 8, 1)
+    MX4_KEY(false, 4, 2, 4, 1) MX4_KEY(false, 4, 2, 8, 1) MX4_KEY(false, 4, 2, 2, 2) MX4_KEY(false, 4, 2, 4, 2) MX4_KEY(false, 4, 2, 8, 2)
+    MX4_KEY(false, 4, 4, 2, 4) MX4_KEY(false, 4, 4, 4, 2) MX4_KEY(false, 4, 4, 8, 2) MX4_KEY(false, 4, 4, 4, 4)
+    MX4_KEY(true, 1, 1, 2, 1) MX4_KEY(true, 1, 1, 4, 1) MX4_KEY(true, 1, 1, 8, 1)
+    MX4_KEY(true, 2, 1, 2, 1) MX4_KEY(true, 2, 1, 4, 1) MX4_KEY(true, 2, 1, 8, 1)
+    MX4_KEY(true, 4, 1, 2, 1) MX4_KEY(true, 4, 1, 4, 1) MX4_KEY(true, 4, 1, 8, 1)
+    MX4_KEY(true, 4, 2, 2, 1) MX4_KEY(true, 4, 2, 4, 1) MX4_KEY(true, 4, 2, 2, 2) MX4_KEY(true, 4, 2, 4, 2)
+    MX4_KEY(true, 4, 4, 2, 2) MX4_KEY(true, 4, 4, 4, 2) MX4_KEY(true, 4, 4, 2, 4)
+      return true;
+    default: return false;
+  }
+#undef MX4_KEY
+}
+
+// The geometry of a multi launch: pick_mx4_cfg's choice for the shape (results do not depend on it); WS stays launch_gemv_mx4's
+// function of K, which the order of a row's sum does depend on.  Only the ten instantiations a default launch selects are built
+// (DESIGN.md §2.12 has their register figures; 8 rows per wave at WS = 1 would need more than wave 0's 64 finishing lanes).  A
+// CC_GEMV_MX4_CFG that names another geometry launch_gemv_mx4 serves runs the shape's DEFAULT geometry here, with the hook's cap on
+// the grid: the same bits, and the same CC_ERR_UNSUPPORTED cases as the single-vector entry point under that setting.
+template <int NT>
+static int launch_gemv_mx4_multi(const GemvMx4Args& a, hipStream_t st) {
+  const int nseg = (a.K / 32 + 63) / 64;
+  const int ws = nseg >= 3 ? 4 : nseg;
+  const int nstep = (nseg + ws - 1) / ws;
+  Mx4Cfg c = pick_mx4_cfg(a, nstep);
+  const int xs = nstep <= 1 ? 1 : nstep <= 2 ? 2 : 4;
+  if (nstep > 4 || c.cu > xs || c.cap <= 0) return CC_ERR_UNSUPPORTED;
+  if (!mx4_single_serves((a.W3 ? 100000 : 0) + ws * 10000 + xs * 1000 + c.rb * 10 + c.cu)) return CC_ERR_UNSUPPORTED;
+  if (nstep <= 1) {  // the default geometry of the shape class (pick_mx4_cfg without the tuning hook)
+    c.rb = 4; c.cu = 1;
+  } else {
+    c.rb = a.W3 != nullptr ? 2 : 4; c.cu = 2;
+  }
+  const int key = (a.W3 ? 100000 : 0) + ws * 10000 + xs * 1000 + c.rb * 10 + c.cu;
+#define MX4M_CASE(SW, WS_, XS_, RB_, CU_) \
+  case (SW ? 100000 : 0) + WS_ * 10000 + XS_ * 1000 + RB_ * 10 + CU_: launch_mx4_multi_cfg<SW, RB_, CU_, XS_, WS_, NT>(a, st, c.cap); break;
+  switch (key) {
+    MX4M_CASE(false, 1, 1, 4, 1) MX4M_CASE(false, 2, 1, 4, 1) MX4M_CASE(false, 4, 1, 4, 1) MX4M_CASE(false, 4, 2, 4, 2) MX4M_CASE(false, 4, 4, 4, 2)
+    MX4M_CASE(true, 1, 1, 4, 1) MX4M_CASE(true, 2, 1, 4, 1) MX4M_CASE(true, 4, 1, 4, 1) MX4M_CASE(true, 4, 2, 2, 2) MX4M_CASE(true, 4, 4, 2, 2)
+    default: return CC_ERR_UNSUPPORTED;
+  }
+#undef MX4M_CASE
+  CC_LAUNCH_CHECK();
+  return CC_OK;
+}
+
+static int launch_gemv_mx4_multi_t(const GemvMx4Args& a, int nt, hipStream_t st) {
+  switch (nt) {
+    case 1: return launch_gemv_mx4(a, st);  // one token: the single-vector kernel itself
+    case 2: return launch_gemv_mx4_multi<2>(a, st);
+    case 3: return launch_gemv_mx4_multi<3>(a, st);
+    default: return launch_gemv_mx4_multi<4>(a, st);
+  }
+}
+
+}  // namespace
+
+extern "C" int cc_gemv_fused_mx4_multi(const uint8_t* W, const uint8_t* scales, const uint8_t* W3, const uint8_t* scales3, const void* x,
+                                       const void* delta, const void* norm_w, float eps, void* h_out, const void* bias, const void* freqs,
+                                       int32_t rope_rows, int32_t head_dim, void* y, int32_t N, int32_t K, int32_t T, int32_t dtype,
+                                       cc_stream_t stream) {
+  CC_ENTRY();
+  if (!W || !scales || !x || !y || N <= 0 || K <= 0 || !cc_dt_ok(dtype)) return CC_ERR_BAD_ARG;
+  if (T < 1 || T > CC_GEMV_MULTI_MAX_T) return CC_ERR_BAD_ARG;
+  if ((W3 != nullptr) != (scales3 != nullptr)) return CC_ERR_BAD_ARG;
+  if ((delta || h_out) && !norm_w) return CC_ERR_BAD_ARG;
+  if (freqs && (W3 || rope_rows < 0 || rope_rows > N || head_dim <= 0 || (head_dim & 1) || (rope_rows % head_dim))) return CC_ERR_BAD_ARG;
+  if (W3 && bias) return CC_ERR_BAD_ARG;
+  // (row t of x / delta / h_out starts K * 2 bytes behind row t - 1: K % 32 == 0 keeps every row as aligned as the first)
+  if (!mx4_aligned(W, 16) || !mx4_aligned(W3, 16) || !mx4_aligned(x, 16) || !mx4_aligned(delta, 16) || !mx4_aligned(norm_w, 16) ||
+      !mx4_aligned(h_out, 16) || !mx4_aligned(bias, 2) || !mx4_aligned(freqs, 2) || !mx4_aligned(y, 2))
+    return CC_ERR_BAD_ARG;
+  if (dtype != CC_DT_BF16) return CC_ERR_UNSUPPORTED;  // bf16 models only
+  if (K % 32) return CC_ERR_UNSUPPORTED;               // whole MX blocks
+  if ((size_t)K * sizeof(bf16_t) > 64 * 1024) return CC_ERR_UNSUPPORTED;
+  GemvMx4Args a{W, W3, scales, scales3, x, delta, norm_w, bias, freqs, h_out, y, eps, N, K, freqs ? rope_rows : 0, freqs ? head_dim : 2};
+  return launch_gemv_mx4_multi_t(a, T, (hipStream_t)stream);
 }

@@ -3,7 +3,7 @@
 These are NOT part of the cache/attention hot path — they are the model-side code around it
 (ref: model.py:317-327, 375-387, 442-443, 452-457, 507-519), which the reference leaves to ~45 eager elementwise
 launches per layer or to torch.compile.  On device tensors they call the C ABI (`cc_add_rmsnorm`, `cc_qkv_rope`,
-`cc_silu_mul`, `cc_gemv_fused`, `cc_gemv_fused_multi`, `cc_softmax_argmax`, `cc_sample_topk`); CPU tensors raise — there is no host path in the package (the
+`cc_silu_mul`, `cc_gemv_fused`, `cc_gemv_fused_multi` and its int8 / MXFP4 forms, `cc_softmax_argmax`, `cc_sample_topk`); CPU tensors raise — there is no host path in the package (the
 CPU model-wiring test brings its own eager twins: tests/host_glue.py).
 """
 import ctypes as C
@@ -151,15 +151,43 @@ GEMV_MULTI_MAX_T = 4  # CC_GEMV_MULTI_MAX_T (include/coldcompress.h)
 
 
 def gemv_fused_multi(weight, x, w3=None, delta=None, norm_weight=None, eps=1e-5, h_out=None, bias=None, freqs=None, rope_rows=0,
-                     head_dim=0):
+                     head_dim=0, scales=None, scales3=None):
     """gemv_fused for T input vectors from ONE pass over the weights (cc_gemv_fused_multi), 1 <= T <= 4: x [T, K] (delta, h_out
-    likewise), freqs [T, head_dim / 2, 2] -> [T, N].  Row t is bit-identical to gemv_fused on row t.  Dense weights only: the int8,
-    int4 and MXFP4 GEMVs have no multi form (an error, not a fallback — callers ask Transformer.block_eligible first)."""
-    if weight.dtype not in _DT:
-        raise _abi.ColdCompressError(f"gemv_fused_multi: dense weights only, got {weight.dtype}")
+    likewise), freqs [T, head_dim / 2, 2] -> [T, N].  Row t is bit-identical to gemv_fused on row t.
+    int8 `weight` (and `w3`) with per-row `scales` (`scales3`): cc_gemv_fused_w8_multi, bf16 or f16 activations.
+    uint8 `weight` (and `w3`) with uint8 `scales` (`scales3`), the e8m0 block bytes [N, K / 32]: cc_gemv_fused_mx4_multi, bf16
+    activations.  The int4 GEMV (uint8 codes with bf16 (scale, zero) pairs) has no multi form: an error, not a fallback — callers
+    ask Transformer.block_eligible first."""
+    if weight.dtype == torch.int8:
+        if scales is None or (w3 is not None and (w3.dtype != torch.int8 or scales3 is None)):
+            raise _abi.ColdCompressError("gemv_fused_multi: int8 weights need their per-row scales (and w3 int8 with scales3)")
+        if x.dtype not in (torch.bfloat16, torch.float16):
+            raise _abi.ColdCompressError(f"gemv_fused_multi: int8 weights need 16-bit activations, got {x.dtype}")
+        N, K = weight.shape
+        for t in (scales, scales3):
+            if t is not None and t.numel() != N:
+                raise _abi.ColdCompressError(f"gemv_fused_multi: int8 scales must hold one value per row ({N}), got {tuple(t.shape)}")
+    elif weight.dtype == torch.uint8:
+        if scales is None or scales.dtype != torch.uint8 or (w3 is not None and (w3.dtype != torch.uint8 or scales3 is None)):
+            raise _abi.ColdCompressError("gemv_fused_multi: uint8 weights need MXFP4's uint8 block scales (and w3 uint8 with scales3); the "
+                                         "int4 GEMV has no multi form")
+        if x.dtype != torch.bfloat16:
+            raise _abi.ColdCompressError(f"gemv_fused_multi: MXFP4 weights need bf16 activations, got {x.dtype}")
+        N, K = weight.shape[0], 2 * weight.shape[1]
+        for t in (scales, scales3):
+            if t is not None and (t.dtype != torch.uint8 or not t.is_contiguous() or tuple(t.shape) != (N, K // 32)):
+                raise _abi.ColdCompressError(f"gemv_fused_multi: MXFP4 block scales must be contiguous uint8 [{N}, K / 32] (K = {K}), got "
+                                             f"{t.dtype} {tuple(t.shape)}")
+    elif weight.dtype in _DT:
+        if scales is not None or scales3 is not None:
+            raise _abi.ColdCompressError("gemv_fused_multi: dense weights take no scales")
+        N, K = weight.shape
+    else:
+        raise _abi.ColdCompressError(f"gemv_fused_multi: dense, int8 or MXFP4 weights, got {weight.dtype}")
+    if weight.dtype not in _DT and w3 is not None and tuple(w3.shape) != tuple(weight.shape):
+        raise _abi.ColdCompressError(f"gemv_fused_multi: w3 must have the shape of weight {tuple(weight.shape)}, got {tuple(w3.shape)}")
     if not x.is_cuda:
         _host(x, "gemv_fused_multi input")
-    N, K = weight.shape
     if x.dim() != 2 or x.shape[1] != K:
         raise _abi.ColdCompressError(f"gemv_fused_multi: x must be [T, {K}], got {tuple(x.shape)}")
     T = x.shape[0]
@@ -171,6 +199,19 @@ def gemv_fused_multi(weight, x, w3=None, delta=None, norm_weight=None, eps=1e-5,
     xc = x.contiguous()
     dc = delta.contiguous() if delta is not None else None
     fc = freqs.contiguous() if freqs is not None else None
+    if weight.dtype == torch.int8:
+        dt = x.dtype
+        sc = scales.to(dt).contiguous()
+        sc3 = scales3.to(dt).contiguous() if w3 is not None else None
+        y = torch.empty((T, N), dtype=dt, device=weight.device)
+        _abi.call("cc_gemv_fused_w8_multi", _p(weight), _p(sc), _p(w3), _p(sc3), _p(xc), _p(dc), _p(norm_weight), float(eps), _p(h_out),
+                  _p(bias), _p(fc), int(rope_rows), int(head_dim), _p(y), N, K, T, _DT[dt], _stream())
+        return y
+    if weight.dtype == torch.uint8:
+        y = torch.empty((T, N), dtype=torch.bfloat16, device=weight.device)
+        _abi.call("cc_gemv_fused_mx4_multi", _p(weight), _p(scales), _p(w3), _p(scales3), _p(xc), _p(dc), _p(norm_weight), float(eps),
+                  _p(h_out), _p(bias), _p(fc), int(rope_rows), int(head_dim), _p(y), N, K, T, _DT[torch.bfloat16], _stream())
+        return y
     y = torch.empty((T, N), dtype=weight.dtype, device=weight.device)
     _abi.call("cc_gemv_fused_multi", _p(weight), _p(w3), _p(xc), _p(dc), _p(norm_weight), float(eps), _p(h_out), _p(bias), _p(fc),
               int(rope_rows), int(head_dim), _p(y), N, K, T, _DT[weight.dtype], _stream())

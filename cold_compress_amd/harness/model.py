@@ -101,7 +101,8 @@ def precompute_freqs_cis(seq_len, n_elem, base=10000, dtype=torch.bfloat16, rope
 def _quant(linear, suffix=""):
     """glue.gemv_fused's quantisation arguments for a weight-only linear (harness/quantize.py), none for a dense one: int8 its
     per-row scales, int4 its per-row (scale, zero) pairs and groupsize, MXFP4 its e8m0 block-scale bytes (uint8 codes like int4's:
-    told apart by the module's buffer, before the int4 branch).  suffix "3": the w3 of a SwiGLU pair."""
+    told apart by the module's buffer, before the int4 branch).  suffix "3": the w3 of a SwiGLU pair.  glue.gemv_fused_multi takes
+    the same arguments except int4's `groupsize` (it has no int4 form): Transformer.block_eligible keeps int4 linears away from it."""
     if linear.weight.dtype == torch.uint8 and hasattr(linear, "block_scales"):
         return {"scales" + suffix: linear.block_scales}
     if linear.weight.dtype == torch.int8:
@@ -262,7 +263,7 @@ class TransformerBlock(nn.Module):
     def forward_block(self, x, delta, input_ids, input_pos, freqs_cis, attn_top_k=1.0):
         """forward() for T decode tokens whose inputs are all known: x, delta [1, T, dim], input_ids [1, T], input_pos [T],
         freqs_cis [T, D/2, 2] -> (h, f) like forward().  Every dense product is ONE pass over its weights for the T tokens
-        (cc_gemv_fused_multi: row t bit-identical to the single-token launch); the T cache steps run one after the other through
+        (cc_gemv_fused_multi, or its int8 / MXFP4 form: row t bit-identical to the single-token launch); the T cache steps run one after the other through
         Attention.decode_attend, as the token-by-token loop runs them — layer l at token t needs layer l - 1 at token t and this
         layer's cache behind tokens < t, both of which exist in this order.  CPU tensors (tests/cpu_twin.py): forward() row by
         row, a correctness twin."""
@@ -279,17 +280,17 @@ class TransformerBlock(nn.Module):
         h1 = torch.empty_like(x2)
         qkv = glue.gemv_fused_multi(att.wqkv.weight, x2, delta=None if delta is None else delta.view(T, -1),
                                     norm_weight=self.attention_norm.weight, eps=self.attention_norm.eps, h_out=h1, bias=att.wqkv.bias,
-                                    freqs=freqs_cis, rope_rows=(HQ + H) * D, head_dim=D)
+                                    freqs=freqs_cis, rope_rows=(HQ + H) * D, head_dim=D, **_quant(att.wqkv))
         ys = []
         for t in range(T):
             row = qkv[t]
             ys.append(att.decode_attend(row[: HQ * D].view(1, HQ, 1, D), row[HQ * D: (HQ + H) * D].view(1, H, 1, D),
                                         row[(HQ + H) * D:].view(1, H, 1, D), input_ids[:, t:t + 1], input_pos[t:t + 1], attn_top_k).view(1, -1))
-        a = glue.gemv_fused_multi(att.wo.weight, torch.cat(ys))
+        a = glue.gemv_fused_multi(att.wo.weight, torch.cat(ys), **_quant(att.wo))
         h2 = torch.empty_like(x2)
         g = glue.gemv_fused_multi(ffn.w1.weight, h1, w3=ffn.w3.weight, delta=a, norm_weight=self.ffn_norm.weight, eps=self.ffn_norm.eps,
-                                  h_out=h2)
-        return h2.view(1, T, -1), glue.gemv_fused_multi(ffn.w2.weight, g).view(1, T, -1)
+                                  h_out=h2, **{**_quant(ffn.w1), **_quant(ffn.w3, "3")})
+        return h2.view(1, T, -1), glue.gemv_fused_multi(ffn.w2.weight, g, **_quant(ffn.w2)).view(1, T, -1)
 
 
 class Transformer(nn.Module):
@@ -303,6 +304,9 @@ class Transformer(nn.Module):
         self.freqs_cis: Optional[Tensor] = None
         self.max_batch_size = 1
         self.batch_quant_flush = True  # False: one round-trip launch per layer, at the start of its next update
+        # True: block_eligible also accepts weight-only int8 and MXFP4 linears (cc_gemv_fused_w8_multi / cc_gemv_fused_mx4_multi: the
+        # same bits as the token-by-token route).  OPT-IN: DESIGN.md §2.12 has what blocks are worth for quantised weights
+        self.block_weight_only = False
 
     @classmethod
     def from_name(cls, name: str):
@@ -375,20 +379,33 @@ class Transformer(nn.Module):
         """True when forward_block computes what the token-by-token decode computes, from one pass over the weights per block:
         every layer on the device-fused decode branch over dense weights, no single-launch QKV step, full attention, no analysis
         cache, no cache that quantises in reference mode (its batched round trip behind the last layer, flush_quantized, would
-        run after later tokens have read the layer's cache; the fused quantised modes are fine), one rank."""
+        run after later tokens have read the layer's cache; the fused quantised modes are fine), one rank.
+        With `block_weight_only` set, each of the five linears of a layer and the LM head may also be a WeightOnlyInt8Linear (bf16 or
+        f16 activations) or a WeightOnlyMxfp4Linear (bf16 activations) — recognised as the module with its scale buffer, not by the
+        weight's dtype — with w1 and w3 of the same kind.  Int4 linears have no multi GEMV: not eligible either way."""
         from ..cache import KVCacheAnalysis
         from .generation import _tp_world
+        from .quantize import is_int8_linear, is_mxfp4_linear
 
         if attn_top_k != 1.0 or _tp_world() > 1 or self.freqs_cis is None:
             return False
         dense = (torch.float32, torch.bfloat16, torch.float16)
         probe = self.tok_embeddings.weight
         on_device = probe.is_cuda  # (CPU tensors exist under tests/cpu_twin.py only: forward_block's row-by-row twin serves them)
-        if self.output.weight.dtype not in dense or (on_device and not (self.output.bias is None and glue.gemv_supported(self.output.weight))):
+
+        def kind(linear):
+            """'dense', 'int8' or 'mxfp4' for a linear the multi GEMVs serve at this model's activation dtype, else None."""
+            if self.block_weight_only and is_int8_linear(linear):
+                return "int8" if probe.dtype in (torch.bfloat16, torch.float16) else None
+            if self.block_weight_only and is_mxfp4_linear(linear):
+                return "mxfp4" if probe.dtype == torch.bfloat16 else None
+            return "dense" if linear.weight.dtype in dense else None
+
+        if kind(self.output) is None or (on_device and not (self.output.bias is None and glue.gemv_supported(self.output.weight))):
             return False
         for layer in self.layers:
             att, ffn, cache = layer.attention, layer.feed_forward, layer.attention.kv_cache
-            if any(w.dtype not in dense for w in (att.wqkv.weight, att.wo.weight, ffn.w1.weight, ffn.w3.weight, ffn.w2.weight)):
+            if any(kind(m) is None for m in (att.wqkv, att.wo, ffn.w1, ffn.w3, ffn.w2)) or kind(ffn.w1) != kind(ffn.w3):
                 return False
             if (on_device and not layer.device_fused(probe)) or att.fuse_qkv_step or cache is None or isinstance(cache, KVCacheAnalysis):
                 return False
@@ -413,4 +430,4 @@ class Transformer(nn.Module):
                 flush_quantized([layer.attention.kv_cache for layer in self.layers])
             return torch.cat([self.output(self.norm(x[:, t:t + 1], delta[:, t:t + 1])[1]) for t in range(T)], 1)
         return glue.gemv_fused_multi(self.output.weight, x.view(T, -1), delta=delta.view(T, -1), norm_weight=self.norm.weight,
-                                     eps=self.norm.eps).view(1, T, -1)
+                                     eps=self.norm.eps, **_quant(self.output)).view(1, T, -1)

@@ -784,7 +784,7 @@ int cc_gemv_fused(const void* W, const void* W3, const void* x, const void* delt
  * Row t of y and of h_out is BIT-IDENTICAL to cc_gemv_fused called with row t of x, delta and freqs, for every dtype, form and
  * shape cc_gemv_fused serves (a row's arithmetic there depends neither on the rows and column steps in flight nor on the grid, and
  * is kept per token here).  Same argument checks and CC_ERR_UNSUPPORTED cases; T outside 1 .. CC_GEMV_MULTI_MAX_T:
- * CC_ERR_BAD_ARG.  Dense weights only.  A plain grid: no workgroup waits for another.  Arguments are validated before any launch:
+ * CC_ERR_BAD_ARG.  Dense weights only (int8 / MXFP4: cc_gemv_fused_w8_multi / cc_gemv_fused_mx4_multi).  A plain grid: no workgroup waits for another.  Arguments are validated before any launch:
  * an error writes nothing. */
 #define CC_GEMV_MULTI_MAX_T 4
 int cc_gemv_fused_multi(const void* W, const void* W3, const void* x, const void* delta, const void* norm_w, float eps,
@@ -853,6 +853,31 @@ int cc_gemv_fused_w4(const uint8_t* W, const void* qparams, const uint8_t* W3, c
 int cc_gemv_fused_mx4(const uint8_t* W, const uint8_t* scales, const uint8_t* W3, const uint8_t* scales3, const void* x,
                       const void* delta, const void* norm_w, float eps, void* h_out, const void* bias, const void* freqs,
                       int32_t rope_rows, int32_t head_dim, void* y, int32_t N, int32_t K, int32_t dtype, cc_stream_t stream);
+
+/* cc_gemv_fused_w8 and cc_gemv_fused_mx4 for T input vectors from ONE pass over the weights, 1 <= T <= CC_GEMV_MULTI_MAX_T: what
+ * cc_gemv_fused_multi is to cc_gemv_fused, for weight-only int8 and MXFP4 models.
+ *   x, delta (or NULL), h_out (or NULL): [T, K];  freqs (or NULL): [T, head_dim / 2, 2], row t the (cos, sin) of token t's position;
+ *   y: [T, N];  W, W3, scales, scales3 (int8: per row, in `dtype`; MXFP4: the e8m0 block bytes), norm_w, bias: as the single-vector
+ *   entry point, shared by the T rows.
+ * Row t of y and of h_out is BIT-IDENTICAL to the single-vector entry point (cc_gemv_fused_w8 / cc_gemv_fused_mx4) called with row t
+ * of x, delta and freqs, for every dtype, form and shape that entry point serves, K * 2 = 64 KiB with the norm prologue included: the
+ * lane that owns a weight chunk, the order of its dot chain, the wave and workgroup reductions (MXFP4: the waves per row, a function
+ * of K) and every rounding point are kept per token; a weight register is loaded and decoded once and feeds T accumulator chains.
+ * The norm prologue passes the T tokens one after the other through ONE staging buffer: the dynamic LDS of a workgroup is the
+ * single-vector kernel's.  Same argument checks and CC_ERR_UNSUPPORTED cases as the single-vector entry point; T outside
+ * 1 .. CC_GEMV_MULTI_MAX_T: CC_ERR_BAD_ARG.  T = 1 launches the single-vector kernel itself.  A plain grid: no workgroup waits for
+ * another.  Arguments are validated before any launch: an error writes nothing.  (Int4 group-wise weights have no multi form.)
+ * Under the tuning hooks (CC_GEMV_W8_CFG / CC_GEMV_MX4_CFG) the refusals are the single-vector entry point's too; the MXFP4 form
+ * builds the default geometries only and runs the shape's default one where the hook names another that cc_gemv_fused_mx4 serves
+ * (results do not depend on the geometry). */
+int cc_gemv_fused_w8_multi(const int8_t* W, const void* scales, const int8_t* W3, const void* scales3, const void* x,
+                           const void* delta, const void* norm_w, float eps, void* h_out, const void* bias, const void* freqs,
+                           int32_t rope_rows, int32_t head_dim, void* y, int32_t N, int32_t K, int32_t T, int32_t dtype,
+                           cc_stream_t stream);
+int cc_gemv_fused_mx4_multi(const uint8_t* W, const uint8_t* scales, const uint8_t* W3, const uint8_t* scales3, const void* x,
+                            const void* delta, const void* norm_w, float eps, void* h_out, const void* bias, const void* freqs,
+                            int32_t rope_rows, int32_t head_dim, void* y, int32_t N, int32_t K, int32_t T, int32_t dtype,
+                            cc_stream_t stream);
 
 /* Greedy sampling tail, ref: generation_utils.py:136-142: probs[V] = dtype(softmax_fp32(logits[V])),
  * *idx_out = first index of the largest rounded probability (torch.argmax semantics).  Two small launches; `workspace`
