@@ -9,6 +9,10 @@
 //             largest element.  The first of them also leaves the per-workgroup maxima (the largest kept value IS the global maximum).
 //   draw      folds the last histogram into the pivot; per workgroup the sum of exp(x - m) over the kept set and the best Gumbel key.
 //   write     folds the sums, writes the probabilities (exactly 0 outside the kept set); workgroup 0 folds the keys into the token.
+// cc_sample_nucleus (top-p, min-p) adds, between select and draw:
+//   mass      one launch per digit again, over the top-k kept set: 256 bins of 64-bit INTEGER masses floor(exp(x - m) * 2^40) per
+//             workgroup (LDS atomics; integer sums do not depend on their order), folded and walked by the next launch to the digit at
+//             which the running mass reaches ceil(top_p * Z); the first pass's histogram sums to Z.  min-p is a compare in draw and write.
 #include "cc_common.h"
 
 namespace {
@@ -258,6 +262,248 @@ void sp_launch(const void* logits_, int V, float tmax, int k, unsigned long long
   hipLaunchKernelGGL((sample_draw_kernel<T, NP>), grid, block, 0, st, logits, V, tmax, k, seed, input_pos, ws);
   hipLaunchKernelGGL((sample_write_kernel<T, NP>), grid, block, 0, st, logits, V, tmax, probs, idx_out, ws);
 }
+
+// ---- top-p / min-p (cc_sample_nucleus): a second radix select over the same key, after the top-k one, whose bins hold 64-bit masses
+struct SpNucWs {  // cc_sample_nucleus_workspace_bytes; as SpWs, nothing is read before a launch of the call wrote it
+  SpWs base;
+  unsigned long long mass[2][kSpBlocks][256];  // digit masses of nucleus pass Q in mass[Q & 1]
+  unsigned long long mrem[4];                  // after pass Q: the mass still to collect among the elements that match mprefix[Q]
+  unsigned int mprefix[4];
+  unsigned int cntpart[kSpBlocks];
+};
+
+// step 2a's integer mass of an element d = x - m below the maximum: floor(exp(d) * 2^40), the exp being the softmax's (sp_exp<T>)
+template <typename T>
+__device__ __forceinline__ unsigned long long sp_mass(float d) {
+  return (unsigned long long)(sp_exp<T>(d) * 1099511627776.0f);  // (the scaling by 2^40 is exact; the conversion truncates)
+}
+
+// sp_fold for masses: fold the 128 mass histograms of nucleus pass Q (thread t owns digit t) and walk them from digit 255 down to the
+// digit at which the running mass reaches what is still to collect; pass 0's histogram sums to Z, so the target is computed here.
+// Integer sums: the same in every workgroup whatever order the LDS atomics ran in.  s_m: kSpWaves + 1 words, s_w: 1 word.
+__device__ __forceinline__ uint32_t sp_fold_mass(SpNucWs* nws, int Q, float top_p, unsigned long long* s_m, unsigned int* s_w) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint32_t pfx = 0u;
+  unsigned long long rem = 0ull;
+  if (Q > 0) {
+    pfx = nws->mprefix[Q - 1];
+    rem = nws->mrem[Q - 1];
+  }
+  unsigned long long c = 0ull;
+  for (int g = 0; g < kSpBlocks; g++) c += nws->mass[Q & 1][g][threadIdx.x];
+  unsigned long long s = c;  // inclusive suffix sum over the wave's digits
+#pragma unroll
+  for (int off = 1; off < CC_WAVE; off <<= 1) {
+    const unsigned long long o = __shfl_down(s, off, CC_WAVE);
+    if (lane + off < CC_WAVE) s += o;
+  }
+  if (lane == 0) s_m[wave] = s;
+  if (threadIdx.x == 0) {  // (no digit reaches the target only when Z is 0: no finite element at all.  Digit 0: everything stays)
+    s_w[0] = pfx << 8;
+    s_m[kSpWaves] = 0ull;
+  }
+  __syncthreads();
+  if (Q == 0) {
+    const unsigned long long Z = (s_m[0] + s_m[1]) + (s_m[2] + s_m[3]);
+    rem = (unsigned long long)ceil(__dmul_rn((double)top_p, (double)Z));
+    rem = rem < Z ? rem : Z;
+  }
+  unsigned long long above = 0ull;
+  for (int w = wave + 1; w < kSpWaves; w++) above += s_m[w];
+  const unsigned long long incl = s + above, excl = incl - c;
+  if (excl < rem && rem <= incl) {  // exactly one digit (its own mass is not 0)
+    s_w[0] = (pfx << 8) | (uint32_t)threadIdx.x;
+    s_m[kSpWaves] = rem - excl;
+  }
+  __syncthreads();
+  const uint32_t prefix = s_w[0];
+  rem = s_m[kSpWaves];
+  __syncthreads();
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    nws->mprefix[Q] = prefix;
+    nws->mrem[Q] = rem;
+  }
+  return prefix;
+}
+
+// nucleus pass Q over K = the top-k kept set without NaNs (NPK: top-k select passes that ran; pass 0 folds the last of them)
+template <typename T, int NPK, int Q>
+__global__ __launch_bounds__(kSpThreads) void sample_mass_kernel(const T* logits, int V, float tmax, int k, float top_p, SpNucWs* nws) {
+  constexpr int NB = SpKey<T>::NB;
+  __shared__ unsigned long long shm[256];
+  __shared__ unsigned long long s_m[kSpWaves + 1];
+  __shared__ unsigned int s_w[kSpWaves + 2];
+  __shared__ float s_f[kSpWaves];
+  SpWs* ws = &nws->base;
+  int lo, hi;
+  sp_slice(V, lo, hi);
+  uint32_t kpivot = 0u, mprefix = 0u;
+  if constexpr (NPK > 0) {
+    if constexpr (Q == 0) {
+      uint32_t krem;
+      sp_fold(ws, NPK - 1, k, s_w, kpivot, krem);
+    } else {
+      kpivot = ws->prefix[NPK - 1];
+    }
+  }
+  if constexpr (Q > 0) mprefix = sp_fold_mass(nws, Q - 1, top_p, s_m, s_w);
+  const float m = sp_fold_max(ws, s_f);
+  shm[threadIdx.x] = 0ull;
+  __syncthreads();
+  for (int i = lo + threadIdx.x; i < hi; i += kSpThreads) {
+    const float x = sp_scaled<T>(logits, i, tmax);
+    if (x != x) continue;
+    const uint32_t key = SpKey<T>::key(x);
+    bool match = key >= kpivot;
+    if constexpr (Q > 0) match = match && (key >> (NB - 8 * Q)) == mprefix;
+    if (match) atomicAdd(&shm[(key >> (NB - 8 * (Q + 1))) & 0xffu], sp_mass<T>(__fsub_rn(x, m)));
+  }
+  __syncthreads();
+  nws->mass[Q & 1][blockIdx.x][threadIdx.x] = shm[threadIdx.x];
+}
+
+// the draw launch with the two filters (NPQ: nucleus passes that ran; 0: top-p is off) and the per-workgroup count of kept elements
+template <typename T, int NPK, int NPQ>
+__global__ __launch_bounds__(kSpThreads) void sample_draw_nucleus_kernel(const T* logits, int V, float tmax, int k, float top_p, float dmin,
+                                                                         unsigned long long seed, const int32_t* input_pos, SpNucWs* nws) {
+  __shared__ unsigned int s_w[kSpWaves + 2];
+  __shared__ float s_f[kSpWaves];
+  __shared__ unsigned long long s_k[kSpWaves + 1];
+  __shared__ unsigned int s_c[kSpWaves];
+  SpWs* ws = &nws->base;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int lo, hi;
+  sp_slice(V, lo, hi);
+  uint32_t pivot = 0u;
+  if constexpr (NPQ > 0) {  // (the nucleus pivot is a key of K: never below the top-k pivot)
+    pivot = sp_fold_mass(nws, NPQ - 1, top_p, s_k, s_w);
+  } else if constexpr (NPK > 0) {
+    uint32_t krem;
+    sp_fold(ws, NPK - 1, k, s_w, pivot, krem);
+  }
+  const float m = sp_fold_max(ws, s_f);
+  __syncthreads();
+  const int32_t pos = *input_pos;
+  float sum = 0.f;
+  unsigned int cnt = 0u;
+  unsigned long long best = ~0ull;
+  for (int i = lo + threadIdx.x; i < hi; i += kSpThreads) {
+    const float x = sp_scaled<T>(logits, i, tmax);
+    unsigned long long cand = ~0ull;
+    if (x != x) {
+      cand = (unsigned long long)(unsigned)i;
+    } else if (SpKey<T>::key(x) >= pivot) {
+      const float d = __fsub_rn(x, m);
+      if (d >= dmin) {
+        sum += sp_exp<T>(d);
+        cnt++;
+        cand = ((unsigned long long)(~orderable_f32(sp_gumbel_key(d, seed, pos, i))) << 32) | (unsigned)i;
+      }
+    }
+    best = cand < best ? cand : best;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    sum += __shfl_xor(sum, off, CC_WAVE);
+    cnt += __shfl_xor(cnt, off, CC_WAVE);
+  }
+  if (lane == 0) {
+    s_f[wave] = sum;
+    s_c[wave] = cnt;
+  }
+  best = block_min_u64(best, s_k);  // (its barriers also publish s_f and s_c)
+  if (threadIdx.x == 0) {
+    ws->sumpart[blockIdx.x] = (s_f[0] + s_f[1]) + (s_f[2] + s_f[3]);
+    ws->keypart[blockIdx.x] = best;
+    nws->cntpart[blockIdx.x] = (s_c[0] + s_c[1]) + (s_c[2] + s_c[3]);
+  }
+}
+
+template <typename T, int NPK, int NPQ>
+__global__ __launch_bounds__(kSpThreads) void sample_write_nucleus_kernel(const T* logits, int V, float tmax, float dmin, T* probs,
+                                                                          int32_t* idx_out, int32_t* n_kept_out, SpNucWs* nws) {
+  __shared__ float s_f[kSpWaves];
+  __shared__ float s_sum;
+  SpWs* ws = &nws->base;
+  int lo, hi;
+  sp_slice(V, lo, hi);
+  const float m = sp_fold_max(ws, s_f);
+  if (threadIdx.x < CC_WAVE) {  // one wave folds the sums in a fixed order
+    float s = 0.f;
+    for (int g = threadIdx.x; g < kSpBlocks; g += CC_WAVE) s += ws->sumpart[g];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, CC_WAVE);
+    if (threadIdx.x == 0) s_sum = s;
+  }
+  __syncthreads();
+  const float sum = s_sum;
+  uint32_t pivot = 0u;
+  if constexpr (NPQ > 0) pivot = nws->mprefix[NPQ - 1];
+  else if constexpr (NPK > 0) pivot = ws->prefix[NPK - 1];
+  for (int i = lo + threadIdx.x; i < hi; i += kSpThreads) {
+    const float x = sp_scaled<T>(logits, i, tmax);
+    const float d = __fsub_rn(x, m);
+    float p = 0.f;
+    if (x != x || (SpKey<T>::key(x) >= pivot && d >= dmin)) p = ElemTraits<T>::rnd(__fdiv_rn(sp_exp<T>(d), sum));
+    ElemTraits<T>::store(probs, (size_t)i, p);
+  }
+  if (blockIdx.x == 0 && threadIdx.x < CC_WAVE) {
+    unsigned long long b = ~0ull;
+    unsigned int n = 0u;
+    for (int g = threadIdx.x; g < kSpBlocks; g += CC_WAVE) {
+      const unsigned long long o = ws->keypart[g];
+      b = o < b ? o : b;
+      n += nws->cntpart[g];
+    }
+    b = wave_min_u64(b);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, CC_WAVE);
+    if (threadIdx.x == 0) {
+      *idx_out = b == ~0ull ? 0 : (int32_t)(b & 0xffffffffull);
+      if (n_kept_out) *n_kept_out = (int32_t)n;
+    }
+  }
+}
+
+template <typename T, int NPK>
+void spn_tail(const T* logits, int V, float tmax, int k, bool with_p, float top_p, float dmin, unsigned long long seed, const int32_t* input_pos,
+              T* probs, int32_t* idx_out, int32_t* n_kept_out, SpNucWs* nws, hipStream_t st) {
+  constexpr int NP = SpKey<T>::NB / 8;
+  dim3 grid(kSpBlocks), block(kSpThreads);
+  if (!with_p) {
+    hipLaunchKernelGGL((sample_draw_nucleus_kernel<T, NPK, 0>), grid, block, 0, st, logits, V, tmax, k, top_p, dmin, seed, input_pos, nws);
+    hipLaunchKernelGGL((sample_write_nucleus_kernel<T, NPK, 0>), grid, block, 0, st, logits, V, tmax, dmin, probs, idx_out, n_kept_out, nws);
+    return;
+  }
+  hipLaunchKernelGGL((sample_mass_kernel<T, NPK, 0>), grid, block, 0, st, logits, V, tmax, k, top_p, nws);
+  hipLaunchKernelGGL((sample_mass_kernel<T, NPK, 1>), grid, block, 0, st, logits, V, tmax, k, top_p, nws);
+  if constexpr (NP == 4) {
+    hipLaunchKernelGGL((sample_mass_kernel<T, NPK, 2>), grid, block, 0, st, logits, V, tmax, k, top_p, nws);
+    hipLaunchKernelGGL((sample_mass_kernel<T, NPK, 3>), grid, block, 0, st, logits, V, tmax, k, top_p, nws);
+  }
+  hipLaunchKernelGGL((sample_draw_nucleus_kernel<T, NPK, NP>), grid, block, 0, st, logits, V, tmax, k, top_p, dmin, seed, input_pos, nws);
+  hipLaunchKernelGGL((sample_write_nucleus_kernel<T, NPK, NP>), grid, block, 0, st, logits, V, tmax, dmin, probs, idx_out, n_kept_out, nws);
+}
+
+template <typename T>
+void spn_launch(const void* logits_, int V, float tmax, int k, bool with_p, float top_p, float dmin, unsigned long long seed,
+                const int32_t* input_pos, void* probs_, int32_t* idx_out, int32_t* n_kept_out, SpNucWs* nws, hipStream_t st) {
+  const T* logits = (const T*)logits_;
+  T* probs = (T*)probs_;
+  constexpr int NP = SpKey<T>::NB / 8;
+  dim3 grid(kSpBlocks), block(kSpThreads);
+  hipLaunchKernelGGL((sample_hist_kernel<T, 0>), grid, block, 0, st, logits, V, tmax, k, &nws->base);  // (k == 0: the maxima alone)
+  if (k <= 0) {
+    spn_tail<T, 0>(logits, V, tmax, k, with_p, top_p, dmin, seed, input_pos, probs, idx_out, n_kept_out, nws, st);
+    return;
+  }
+  hipLaunchKernelGGL((sample_hist_kernel<T, 1>), grid, block, 0, st, logits, V, tmax, k, &nws->base);
+  if constexpr (NP == 4) {
+    hipLaunchKernelGGL((sample_hist_kernel<T, 2>), grid, block, 0, st, logits, V, tmax, k, &nws->base);
+    hipLaunchKernelGGL((sample_hist_kernel<T, 3>), grid, block, 0, st, logits, V, tmax, k, &nws->base);
+  }
+  spn_tail<T, NP>(logits, V, tmax, k, with_p, top_p, dmin, seed, input_pos, probs, idx_out, n_kept_out, nws, st);
+}
 }  // namespace
 
 extern "C" size_t cc_sample_topk_workspace_bytes(void) { return sizeof(SpWs); }
@@ -277,6 +523,41 @@ extern "C" int cc_sample_topk(const void* logits, int32_t V, int32_t dtype, floa
     case CC_DT_F32: sp_launch<float>(logits, V, tmax, k, seed, input_pos, probs, idx_out, ws, st); break;
     case CC_DT_BF16: sp_launch<bf16_t>(logits, V, tmax, k, seed, input_pos, probs, idx_out, ws, st); break;
     default: sp_launch<f16_t>(logits, V, tmax, k, seed, input_pos, probs, idx_out, ws, st); break;
+  }
+  CC_LAUNCH_CHECK();
+  return CC_OK;
+}
+
+extern "C" size_t cc_sample_nucleus_workspace_bytes(void) { return sizeof(SpNucWs); }
+
+extern "C" int cc_sample_nucleus(const void* logits, int32_t V, int32_t dtype, float temperature, int32_t top_k, float top_p, float min_p,
+                                 uint64_t seed, const int32_t* input_pos, void* probs, int32_t* idx_out, int32_t* n_kept_out,
+                                 void* workspace, size_t workspace_bytes, cc_stream_t stream) {
+  CC_ENTRY();
+  if (!logits || !probs || !idx_out || !input_pos || !workspace || V <= 0 || !cc_dt_ok(dtype) || !(temperature > 0.f)) return CC_ERR_BAD_ARG;
+  if (!(top_p > 0.f) || !(min_p <= 1.f)) return CC_ERR_BAD_ARG;  // (NaN fails both comparisons)
+  const bool with_p = top_p < 1.f, with_min = min_p > 0.f;
+  if (with_p && V > CC_SAMPLE_NUCLEUS_MAX_V) return CC_ERR_BAD_ARG;
+  if (workspace_bytes < sizeof(SpNucWs)) return CC_ERR_WORKSPACE;
+  if (((uintptr_t)workspace & 7u) != 0) return CC_ERR_BAD_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  SpNucWs* nws = reinterpret_cast<SpNucWs*>(workspace);
+  const float tmax = temperature > 1e-5f ? temperature : 1e-5f;
+  const int k = (top_k <= 0 || top_k >= V) ? 0 : top_k;
+  if (!with_p && !with_min && !n_kept_out) {  // both filters off: cc_sample_topk's own launches
+    switch (dtype) {
+      case CC_DT_F32: sp_launch<float>(logits, V, tmax, k, seed, input_pos, probs, idx_out, &nws->base, st); break;
+      case CC_DT_BF16: sp_launch<bf16_t>(logits, V, tmax, k, seed, input_pos, probs, idx_out, &nws->base, st); break;
+      default: sp_launch<f16_t>(logits, V, tmax, k, seed, input_pos, probs, idx_out, &nws->base, st); break;
+    }
+    CC_LAUNCH_CHECK();
+    return CC_OK;
+  }
+  const float dmin = with_min ? (float)log((double)min_p) : -INFINITY;
+  switch (dtype) {
+    case CC_DT_F32: spn_launch<float>(logits, V, tmax, k, with_p, top_p, dmin, seed, input_pos, probs, idx_out, n_kept_out, nws, st); break;
+    case CC_DT_BF16: spn_launch<bf16_t>(logits, V, tmax, k, with_p, top_p, dmin, seed, input_pos, probs, idx_out, n_kept_out, nws, st); break;
+    default: spn_launch<f16_t>(logits, V, tmax, k, with_p, top_p, dmin, seed, input_pos, probs, idx_out, n_kept_out, nws, st); break;
   }
   CC_LAUNCH_CHECK();
   return CC_OK;

@@ -4,6 +4,7 @@ by torch.compile (generation_utils.py:578-594).
 
 Budget helpers are exact-integer restatements checked against tests/golden/f8_budgets.json.
 """
+import math
 import time
 
 import torch
@@ -123,8 +124,13 @@ def _mix64(x):
     return x ^ ((x >> 33) & lo31)
 
 
-def _sample_host(row, temperature, top_k, seed, pos):
-    """cc_sample_topk's contract (include/coldcompress.h) in torch on a CPU tensor: the same six steps, fp32 where the kernel is."""
+def _f32(v):
+    return float(torch.tensor(float(v), dtype=torch.float32))
+
+
+def _sample_host(row, temperature, top_k, seed, pos, top_p=None, min_p=None):
+    """cc_sample_topk's contract (include/coldcompress.h) in torch on a CPU tensor: the same six steps, fp32 where the kernel is, and
+    cc_sample_nucleus's two filters (steps 2a and 2b) when `top_p` / `min_p` are given.  -> (idx, probs, number of kept elements)."""
     V, dt = row.numel(), row.dtype
     tmax = torch.maximum(torch.tensor(float(temperature), dtype=torch.float32), torch.tensor(1e-5, dtype=torch.float32))
     x = (row.float() / tmax).to(dt).float()  # 1. one fp32 division, rounded to the model dtype
@@ -132,6 +138,17 @@ def _sample_host(row, temperature, top_k, seed, pos):
     if top_k is not None and top_k > 0:  # 2. ties at the pivot are all kept
         kept = x >= torch.topk(x, min(int(top_k), V)).values[-1]
     m = x[kept].max() if bool(kept.any()) else x.max()
+    if top_p is not None and _f32(top_p) < 1:  # 2a. the smallest level set of K whose integer mass reaches ceil(top_p * Z)
+        K = kept & ~torch.isnan(x)
+        w = torch.where(K, torch.floor(torch.exp(x - m) * 2.0 ** 40), torch.zeros_like(x)).to(torch.int64)
+        Z = int(w.sum())
+        if Z > 0:
+            target = min(Z, math.ceil(_f32(top_p) * float(Z)))
+            xs, order = torch.sort(torch.where(K, x, torch.full_like(x, -float("inf"))), descending=True, stable=True)
+            j = int(torch.searchsorted(torch.cumsum(w[order], 0), torch.tensor(target, dtype=torch.int64)))
+            kept = K & (x >= xs[min(j, V - 1)])  # ties at the level are all kept
+    if min_p is not None and _f32(min_p) > 0:  # 2b. p_i >= min_p * p_max in the logit domain
+        kept = kept & ((x - m) >= torch.tensor(math.log(_f32(min_p)), dtype=torch.float32))
     e = torch.where(kept, torch.exp(x - m), torch.zeros_like(x))  # 3.
     probs = (e / e.sum()).to(dt)
     i = torch.arange(V, dtype=torch.int64)  # 4. (p and i widened from unsigned 32 bits)
@@ -142,53 +159,70 @@ def _sample_host(row, temperature, top_k, seed, pos):
     key = torch.where(kept, key, torch.full_like(key, -float("inf")))
     nan = torch.isnan(x)
     idx = torch.argmax(nan.to(torch.int8)) if bool(nan.any()) else torch.argmax(key)  # 6. the first NaN's index
-    return idx.view(1).to(torch.int), probs
+    return idx.view(1).to(torch.int), probs, int((kept & ~nan).sum())
 
 
-def sample(logits, next_token, temperature, top_k, seed, input_pos):
+def sample(logits, next_token, temperature, top_k, seed, input_pos, top_p=None, min_p=None, return_n_kept=False):
     """The reference's logits_to_probs (generation_utils.py:125-133) and a stateless draw from it: one token per (logits,
     temperature, top_k, seed, position), whatever launches, replays or ranks computed it (include/coldcompress.h, cc_sample_topk).
     `input_pos`: one element, the position of the step whose logits these are.  Device tensors run the kernel; CPU tensors the same
-    contract in torch.  A forced `next_token` is returned as given, with the sampled distribution's probabilities."""
+    contract in torch.  A forced `next_token` is returned as given, with the sampled distribution's probabilities.
+    `top_p` (nucleus) and `min_p` (None: off) filter the top-k kept set before the softmax (cc_sample_nucleus); an invalid one raises
+    (ValueError here, ColdCompressError on the device path).  `return_n_kept`: the size of the kept set as a third result (a
+    one-element int32 tensor on the device path, an int on the CPU path)."""
     row = logits[0, -1]
     if row.is_cuda:
         from . import glue
 
-        probs, idx_next = glue.sample_topk(row, temperature, top_k, seed, input_pos.view(-1)[-1:].to(torch.int32))
+        pos = input_pos.view(-1)[-1:].to(torch.int32)
+        if top_p is None and min_p is None and not return_n_kept:
+            probs, idx_next = glue.sample_topk(row, temperature, top_k, seed, pos)
+        else:
+            probs, idx_next, *n_kept = glue.sample_nucleus(row, temperature, top_k, top_p, min_p, seed, pos, return_n_kept)
     else:
         if not float(temperature) > 0:
             raise ValueError(f"sample: temperature must be > 0, got {temperature}")
-        idx_next, probs = _sample_host(row, temperature, top_k, seed, int(input_pos.view(-1)[-1]))
-    return (idx_next if next_token is None else next_token), probs
+        if top_p is not None and not _f32(top_p) > 0:
+            raise ValueError(f"sample: top_p must be > 0 (>= 1: off), got {top_p}")
+        if min_p is not None and not _f32(min_p) <= 1:
+            raise ValueError(f"sample: min_p must be <= 1 (<= 0: off), got {min_p}")
+        idx_next, probs, n = _sample_host(row, temperature, top_k, seed, int(input_pos.view(-1)[-1]), top_p, min_p)
+        n_kept = [n]
+    idx_next = idx_next if next_token is None else next_token
+    return (idx_next, probs, n_kept[0]) if return_n_kept else (idx_next, probs)
 
 
-def prefill(model, x, input_pos, next_token=None, temperature=None, top_k=None, seed=0, **_):
+def prefill(model, x, input_pos, next_token=None, temperature=None, top_k=None, seed=0, top_p=None, min_p=None, **_):
     """ref: generation_utils.py:145-160 — the causal mask is implicit in the HIP prefill kernel.  `temperature` None: greedy;
-    otherwise the token is drawn at the last prompt position (sample)."""
+    otherwise the token is drawn at the last prompt position (sample), behind the top_k / top_p / min_p filters."""
     logits = model(x, input_pos, mask=None, is_prefill=True)
     if temperature is None:
         return greedy(logits, next_token)
-    return sample(logits, next_token, temperature, top_k, seed, input_pos[-1:])
+    return sample(logits, next_token, temperature, top_k, seed, input_pos[-1:], top_p=top_p, min_p=min_p)
 
 
-def decode_one_token(model, x, input_pos, next_token=None, attn_top_k=1.0, temperature=None, top_k=None, seed=0, **_):
+def decode_one_token(model, x, input_pos, next_token=None, attn_top_k=1.0, temperature=None, top_k=None, seed=0, top_p=None, min_p=None,
+                     **_):
     """ref: generation_utils.py:163-178.  `temperature` None: greedy; otherwise the token is drawn at `input_pos` (sample)."""
     logits = model(x, input_pos, is_prefill=False, attn_top_k=attn_top_k)
     if temperature is None:
         return greedy(logits, next_token)
-    return sample(logits, next_token, temperature, top_k, seed, input_pos)
+    return sample(logits, next_token, temperature, top_k, seed, input_pos, top_p=top_p, min_p=min_p)
 
 
 class GraphedDecoder:
     """One decode step captured in a hipGraph (HIP-native replacement for the reference's
     `torch.compile(mode="reduce-overhead")`, generation_utils.py:581-587).  The token and position live in
     static device tensors; every HIP entry point reads `input_pos` from device memory, so replays advance.
-    The sampling settings (temperature, top_k, seed; None: greedy) are carried by the captured step BY VALUE — the draw itself reads
-    the position from device memory — so a call with other settings than the step was captured with captures again."""
+    The sampling settings (temperature, top_k, seed, top_p, min_p; temperature None: greedy) are carried by the captured step BY
+    VALUE — the draw itself reads the position from device memory — so a call with other settings than the step was captured with
+    captures again."""
 
-    def __init__(self, model, warmup=2, temperature=None, top_k=None, seed=0):
+    _SETTINGS = ("temperature", "top_k", "seed", "top_p", "min_p")
+
+    def __init__(self, model, warmup=2, temperature=None, top_k=None, seed=0, top_p=None, min_p=None):
         self.model = model
-        self.sampling = (temperature, top_k, seed)
+        self.sampling = (temperature, top_k, seed, top_p, min_p)
         dev = model.output.weight.device
         self.tok = torch.zeros((1, 1), dtype=torch.int32, device=dev)
         self.pos = torch.zeros((1,), dtype=torch.int32, device=dev)
@@ -205,7 +239,7 @@ class GraphedDecoder:
         snap = [{k: v.clone() for k, v in c._buffers.items()} for c in caches]
         flags = [(getattr(c, "_next_valid", None), getattr(c, "_quant_pending", False)) for c in caches]
         pos0 = self.pos.clone()
-        kw = dict(zip(("temperature", "top_k", "seed"), self.sampling))
+        kw = dict(zip(self._SETTINGS, self.sampling))
         try:
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
@@ -235,7 +269,7 @@ class GraphedDecoder:
         return sum(int(getattr(l.attention.kv_cache, "_graph_epoch", 0)) for l in self.model.layers)
 
     def __call__(self, model, x, input_pos, next_token=None, **kw):
-        sampling = tuple(kw.get(k, d) for k, d in zip(("temperature", "top_k", "seed"), self.sampling))
+        sampling = tuple(kw.get(k, d) for k, d in zip(self._SETTINGS, self.sampling))
         if sampling != self.sampling:  # (carried by value, like what _cache_epoch watches: capture again)
             self.sampling = sampling
             self.graph = None
@@ -526,7 +560,8 @@ def decode_n_tokens(model, cur_token, input_pos, decode_one_token, num_new_token
             if kw.get("temperature") is None:
                 nt, npb = greedy(row, forced_at(k + t))
             else:
-                nt, npb = sample(row, forced_at(k + t), kw["temperature"], kw.get("top_k"), kw.get("seed", 0), pos[t:t + 1])
+                nt, npb = sample(row, forced_at(k + t), kw["temperature"], kw.get("top_k"), kw.get("seed", 0), pos[t:t + 1],
+                                 top_p=kw.get("top_p"), min_p=kw.get("min_p"))
             commit(k + t, nt, npb)
 
     while True:

@@ -3,7 +3,7 @@
 These are NOT part of the cache/attention hot path — they are the model-side code around it
 (ref: model.py:317-327, 375-387, 442-443, 452-457, 507-519), which the reference leaves to ~45 eager elementwise
 launches per layer or to torch.compile.  On device tensors they call the C ABI (`cc_add_rmsnorm`, `cc_qkv_rope`,
-`cc_silu_mul`, `cc_gemv_fused`, `cc_gemv_fused_multi` and its int8 / MXFP4 forms, `cc_softmax_argmax`, `cc_sample_topk`); CPU tensors raise — there is no host path in the package (the
+`cc_silu_mul`, `cc_gemv_fused`, `cc_gemv_fused_multi` and its int8 / MXFP4 forms, `cc_softmax_argmax`, `cc_sample_topk`, `cc_sample_nucleus`); CPU tensors raise — there is no host path in the package (the
 CPU model-wiring test brings its own eager twins: tests/host_glue.py).
 """
 import ctypes as C
@@ -258,3 +258,36 @@ def sample_topk(logits, temperature, top_k, seed, input_pos):
 
 
 _SP_WS = {}
+
+
+def sample_nucleus(logits, temperature, top_k, top_p, min_p, seed, input_pos, return_n_kept=False):
+    """sample_topk with the top-p (nucleus) and min-p filters of cc_sample_nucleus (include/coldcompress.h has the contract) between the
+    top-k cut and the softmax; `top_p` / `min_p` None: that filter is off (both off: sample_topk's launches and its answer, bit for
+    bit).  -> (probs, idx), and with `return_n_kept` a one-element int32 device tensor, the size of the kept set, as a third."""
+    if not logits.is_cuda:
+        _host(logits, "sample_nucleus logits")
+    if not (input_pos.is_cuda and input_pos.dtype == torch.int32 and input_pos.numel() == 1):
+        raise _abi.ColdCompressError(f"sample_nucleus: input_pos must be a one-element int32 device tensor, got {input_pos.dtype} "
+                                     f"{tuple(input_pos.shape)} on {input_pos.device}")
+    if not float(temperature) > 0:
+        raise _abi.ColdCompressError(f"sample_nucleus: temperature must be > 0, got {temperature}")
+    p = 1.0 if top_p is None else float(top_p)
+    mp = 0.0 if min_p is None else float(min_p)
+    if not p > 0:
+        raise _abi.ColdCompressError(f"sample_nucleus: top_p must be > 0 (>= 1: off), got {top_p}")
+    if not mp <= 1:
+        raise _abi.ColdCompressError(f"sample_nucleus: min_p must be <= 1 (<= 0: off), got {min_p}")
+    lc = logits.contiguous()
+    probs = torch.empty_like(lc)
+    idx = torch.empty((1,), dtype=torch.int32, device=lc.device)
+    n_kept = torch.empty((1,), dtype=torch.int32, device=lc.device) if return_n_kept else None
+    ws = _SN_WS.get(lc.device)
+    if ws is None:
+        ws = _SN_WS[lc.device] = torch.empty(int(_abi.lib()["cc_sample_nucleus_workspace_bytes"]()), dtype=torch.uint8, device=lc.device)
+    k = 0 if top_k is None else max(0, min(int(top_k), 2 ** 31 - 1))
+    _abi.call("cc_sample_nucleus", _p(lc), lc.numel(), _DT[lc.dtype], float(temperature), k, p, mp, int(seed) & (2 ** 64 - 1),
+              _p(input_pos), _p(probs), _p(idx), _p(n_kept), _p(ws), ws.numel(), _stream())
+    return (probs, idx, n_kept) if return_n_kept else (probs, idx)
+
+
+_SN_WS = {}

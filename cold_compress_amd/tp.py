@@ -15,8 +15,10 @@ Two sum all-reduces per layer (after attention, after the FFN), issued in place 
 Unlike the reference, a rank may own a single KV head (Llama-3 70B at TP=8): the reference's
 KVCacheHeavyHitter crashes there (cache.py:751/:480); ours does not.
 KVCacheL2's score uses the max key norm over the heads of THIS rank, like the reference under TP.
-Sampling (harness.sample, cc_sample_topk) needs no exchange either: the LM head is a replica, so the logits are bit-identical on
-every rank, and the draw is a stateless function of (logits, temperature, top_k, seed, position): every rank draws the same token.
+Sampling (harness.sample, cc_sample_topk / cc_sample_nucleus) needs no exchange either: the LM head is a replica, so the logits are
+bit-identical on every rank, and the draw is a stateless function of (logits, temperature, top_k, top_p, min_p, seed, position):
+every rank draws the same token.  The top-p and min-p filters need none for the same reason: their kept set is a function of the
+logits alone, computed with integer masses whose sums do not depend on any order.
 """
 import os
 from typing import List, Optional

@@ -916,6 +916,36 @@ int cc_sample_topk(const void* logits, int32_t V, int32_t dtype, float temperatu
                    const int32_t* input_pos, void* probs, int32_t* idx_out, void* workspace, size_t workspace_bytes,
                    cc_stream_t stream);
 
+/* cc_sample_topk with two more filters, top-p (nucleus) and min-p, between its step 2 and its softmax.  Steps 1 (scaling), 2 (top-k,
+ * ties at the pivot all kept), 4 and 5 (uniforms, Gumbel-max key) and 6 (NaN rule) are cc_sample_topk's, word for word; so are the
+ * launch properties (never synchronises, never allocates, stream-capturable, *input_pos read from device memory, one answer per
+ * (logits, settings, seed, *input_pos) whatever the grid, the launch mode or the rank).  Let K be the kept set of step 2 (NaNs
+ * excluded) and m the global maximum of x.  Both filters are level sets of x, so the final kept set is again {i : x[i] >= v}.
+ *   2a. top-p    e_i = exp(x[i] - m) in fp32, computed exactly as step 3 computes it; the MASS of i is the integer
+ *                w_i = floor(e_i * 2^40) (unsigned 64 bits; e_i <= 1), Z = sum over K of w_i, and the target is
+ *                t = min(Z, ceil((double)top_p * (double)Z)), one double-precision product of the two conversions.  The nucleus is the
+ *                smallest level set {i in K : x[i] >= v} whose mass is >= t; ties at v are ALL kept, as at the top-k pivot.  Integer
+ *                addition is associative, so Z and every partial sum are independent of the grid, the wave order and the order of
+ *                the LDS atomics that accumulate them.  V <= CC_SAMPLE_NUCLEUS_MAX_V = 2^24 - 1 keeps Z below 2^64 (each
+ *                w_i <= 2^40); for V < 2^17, Z < 2^57.  A larger V with the filter on: CC_ERR_BAD_ARG.
+ *                top_p >= 1: the filter is off.  top_p <= 0 or NaN: CC_ERR_BAD_ARG before any launch.
+ *   2b. min-p    i survives iff fp32(x[i] - m) >= dmin (one IEEE subtraction, rounded to nearest), dmin = the fp32 rounding of the
+ *                double-precision log((double)min_p), computed once on the host side of the call: p_i >= min_p * p_max in the logit
+ *                domain, exact and without an exponential.  It is relative to the global maximum and independent of top-p: the kept
+ *                set is the intersection of K, the nucleus and the min-p set.  min_p <= 0: off.  min_p > 1 or NaN: CC_ERR_BAD_ARG.
+ *                min_p == 1 keeps exactly the elements equal to the maximum.
+ *   3.  probs    as cc_sample_topk's step 3 over the final kept set (renormalised); exactly 0 elsewhere.
+ * *n_kept_out (may be NULL) receives the number of kept elements: the one observable that identifies the level set (f16
+ * probabilities below 2^-24 read as 0) and the nucleus size.  With both filters off, probs and token are cc_sample_topk's bit for bit
+ * (the same launches run).  The nucleus pivot is a second radix select over the same orderable pattern, after the top-k select, whose
+ * 256-bin histograms hold 64-bit masses: one more launch per 8-bit digit (the first also yields Z).  `workspace`
+ * (cc_sample_nucleus_workspace_bytes, 8-byte aligned) needs no initialisation.  Otherwise cc_sample_topk's refusals. */
+#define CC_SAMPLE_NUCLEUS_MAX_V ((1 << 24) - 1)
+size_t cc_sample_nucleus_workspace_bytes(void);
+int cc_sample_nucleus(const void* logits, int32_t V, int32_t dtype, float temperature, int32_t top_k, float top_p, float min_p,
+                      uint64_t seed, const int32_t* input_pos, void* probs, int32_t* idx_out, int32_t* n_kept_out,
+                      void* workspace, size_t workspace_bytes, cc_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * One-shot sum all-reduce over the GPUs of ONE node, for the decode-size messages of tensor parallelism.
  * ref: tp.py:134-138, 156-160 (`all_reduce(sum)` of the wo and FFN outputs: 2 * dim bytes, 8-16 KiB, twice per layer).

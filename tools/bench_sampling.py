@@ -1,7 +1,7 @@
 """Time of the sampling tail against the greedy tail and the torch composition, and tokens/s of a graphed generation with sampling on
 and off -> profiles/sampling_tail.jsonl (one JSON row per line).
 
-    python tools/bench_sampling.py                 # tails at V = 32000 and 128256 (bf16) + the 128-token generation
+    python tools/bench_sampling.py                 # tails at V = 32000 and 128256 (bf16), top_p / min_p rows included, + the 128-token generation
     python tools/bench_sampling.py --no_generate   # the tails alone (what a rocprofv3 --kernel-trace --stats run wraps)
 
 Tails: HIP events around `--launches` back-to-back calls on one stream, after a warm-up; the logits stay resident in L2 between the
@@ -49,7 +49,10 @@ def tails(dev, launches, out):
                 ("cc_sample_topk", None, lambda: glue.sample_topk(logits, 0.8, None, 1, pos)),
                 ("cc_sample_topk", 50, lambda: glue.sample_topk(logits, 0.8, 50, 1, pos)),
                 ("torch topk+softmax+multinomial", 50, torch_comp)]
-        for name, k, fn in rows:
+        # cc_sample_nucleus beside the cc_sample_topk rows of the same run (the only numbers its cost is compared against)
+        rows += [("cc_sample_nucleus", k, lambda k=k, p=p, mp=mp: glue.sample_nucleus(logits, 0.8, k, p, mp, 1, pos), p, mp)
+                 for k, p, mp in ((None, 0.9, None), (50, 0.9, None), (None, None, 0.05), (50, 0.9, 0.05))]
+        for name, k, fn, *filters in rows:
             # under hipGraph replay as well: what the decode step pays (no per-launch host work)
             us = timed(fn, launches)
             try:
@@ -59,8 +62,10 @@ def tails(dev, launches, out):
                 us_graph = round(timed(g.replay, launches), 2)
             except RuntimeError:  # (a composition this runtime cannot capture)
                 us_graph = None
-            out({"what": "tail", "V": V, "dtype": "bf16", "path": name, "top_k": k, "launches": launches, "us_per_call_eager": round(us, 2),
-                 "us_per_call_graph": us_graph})
+            row = {"what": "tail", "V": V, "dtype": "bf16", "path": name, "top_k": k}
+            if filters:
+                row.update(top_p=filters[0], min_p=filters[1])
+            out({**row, "launches": launches, "us_per_call_eager": round(us, 2), "us_per_call_graph": us_graph})
 
 
 def generation(dev, out):
@@ -79,7 +84,8 @@ def generation(dev, out):
               recent_window=10, history_window_size=1, attn_thresholding=False)
     setup_caches(model, None, dev, 4096, dict(kw))
     prompt = torch.randint(0, cfg["vocab_size"], (512,), generator=torch.Generator().manual_seed(1), dtype=torch.int32).to(dev)
-    for name, skw in (("greedy", {}), ("sampling", dict(temperature=0.8, top_k=50, seed=1))):
+    for name, skw in (("greedy", {}), ("sampling", dict(temperature=0.8, top_k=50, seed=1)),
+                      ("sampling top_p", dict(temperature=0.8, top_k=50, top_p=0.9, seed=1))):
         dec = GraphedDecoder(model, **skw)
         best = None
         for r in range(3):  # the first run captures; best of the next two
