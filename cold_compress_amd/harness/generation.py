@@ -6,6 +6,7 @@ Budget helpers are exact-integer restatements checked against tests/golden/f8_bu
 """
 import math
 import time
+from typing import NamedTuple
 
 import torch
 
@@ -192,19 +193,87 @@ def sample(logits, next_token, temperature, top_k, seed, input_pos, top_p=None, 
     return (idx_next, probs, n_kept[0]) if return_n_kept else (idx_next, probs)
 
 
-def prefill(model, x, input_pos, next_token=None, temperature=None, top_k=None, seed=0, top_p=None, min_p=None, **_):
+class TokenScores(NamedTuple):
+    """What `generate(..., logprobs=True)` returns in place of the probability rows: the committed tokens' log-probabilities under the
+    model's own distribution (fp32) and their ranks (int32: how many logits were strictly larger), in commit order."""
+
+    logprob: torch.Tensor
+    rank: torch.Tensor
+
+
+def token_logprobs(logits, targets, fallback=None):
+    """Log-probability and rank of one token per row of logits [1, T, V] (include/coldcompress.h, cc_logprob_rows): row r is scored
+    against targets[r] where that is >= 0 and against fallback[r] otherwise (`targets` None: all rows against `fallback`); a token
+    outside the vocabulary gives NaN and -1.  -> (logprob [T] fp32, rank [T] int32).  Device tensors run the kernel (T <= 64); CPU tensors
+    the same contract in torch: an fp32 log_softmax and a compare-and-sum."""
+    rows = logits[0]
+    T, V = rows.shape
+    if rows.is_cuda:
+        from . import glue
+
+        tg = None if targets is None else targets.reshape(-1).to(torch.int32)
+        fb = None if fallback is None else fallback.reshape(-1).to(torch.int32)
+        logprob, _, rank = glue.logprob_rows(rows, tg, fb)
+        return logprob, rank
+    t = torch.full((T,), -1, dtype=torch.int64) if targets is None else targets.reshape(-1).to(torch.int64)
+    if fallback is not None:
+        t = torch.where(t >= 0, t, fallback.reshape(-1).to(torch.int64))
+    ok = (t >= 0) & (t < V)
+    tc = torch.where(ok, t, torch.zeros_like(t)).view(T, 1)
+    x = rows.float()
+    xt = x.gather(1, tc)
+    nan = torch.full((T,), float("nan"), dtype=torch.float32)
+    logprob = torch.where(ok, torch.log_softmax(x, dim=-1).gather(1, tc).view(T), nan)
+    rank = torch.where(ok & ~torch.isnan(xt.view(T)), (x > xt).sum(dim=1), torch.full((T,), -1, dtype=torch.int64))
+    return logprob, rank.to(torch.int32)
+
+
+def perplexity(logprob, every=500):
+    """The reference's perplexity arithmetic (eval.py:230-241) on a vector of per-token log-probabilities, in float64:
+    {"ppl": exp(mean(-logprob)), "ppl@500": the same over the first 500 tokens, "ppl@1000": ...}; `every` None: "ppl" alone."""
+    nll = -logprob.detach().to("cpu", torch.float64).view(-1)
+    out = {}
+    if every:
+        for k in range(int(every), len(nll), int(every)):
+            out[f"ppl@{k}"] = float(torch.exp(torch.mean(nll[:k])))
+    out["ppl"] = float(torch.exp(torch.mean(nll)))
+    return out
+
+
+def _scored(logits, next_token, temperature, top_k, seed, input_pos, top_p, min_p, score_target=None):
+    """One step's token and its TokenScores (logprobs=True).  A forced step runs no softmax and keeps no row: it is scored against its
+    forced token.  A free step chooses its token exactly as greedy / sample do and scores it through `fallback`; so does a captured
+    step (`score_target`: a one-element int32 device tensor the replay reads — the forced token, or -1 for what the step chose)."""
+    row = logits[:, -1:]
+    if next_token is not None and score_target is None:
+        return next_token, TokenScores(*token_logprobs(row, next_token.view(1)))
+    if temperature is None:
+        idx_next, _ = greedy(row, None)
+    else:
+        idx_next, _ = sample(row, None, temperature, top_k, seed, input_pos, top_p=top_p, min_p=min_p)
+    scores = TokenScores(*token_logprobs(row, score_target, fallback=idx_next.view(1)))
+    return (idx_next if next_token is None else next_token), scores
+
+
+def prefill(model, x, input_pos, next_token=None, temperature=None, top_k=None, seed=0, top_p=None, min_p=None, logprobs=False, **_):
     """ref: generation_utils.py:145-160 — the causal mask is implicit in the HIP prefill kernel.  `temperature` None: greedy;
-    otherwise the token is drawn at the last prompt position (sample), behind the top_k / top_p / min_p filters."""
+    otherwise the token is drawn at the last prompt position (sample), behind the top_k / top_p / min_p filters.  `logprobs`: the
+    second result is the token's TokenScores, taken from the last row, instead of that row's probabilities."""
     logits = model(x, input_pos, mask=None, is_prefill=True)
+    if logprobs:
+        return _scored(logits, next_token, temperature, top_k, seed, input_pos[-1:], top_p, min_p)
     if temperature is None:
         return greedy(logits, next_token)
     return sample(logits, next_token, temperature, top_k, seed, input_pos[-1:], top_p=top_p, min_p=min_p)
 
 
 def decode_one_token(model, x, input_pos, next_token=None, attn_top_k=1.0, temperature=None, top_k=None, seed=0, top_p=None, min_p=None,
-                     **_):
-    """ref: generation_utils.py:163-178.  `temperature` None: greedy; otherwise the token is drawn at `input_pos` (sample)."""
+                     logprobs=False, score_target=None, **_):
+    """ref: generation_utils.py:163-178.  `temperature` None: greedy; otherwise the token is drawn at `input_pos` (sample).
+    `logprobs`: the second result is the token's TokenScores instead of the row's probabilities (_scored)."""
     logits = model(x, input_pos, is_prefill=False, attn_top_k=attn_top_k)
+    if logprobs:
+        return _scored(logits, next_token, temperature, top_k, seed, input_pos, top_p, min_p, score_target)
     if temperature is None:
         return greedy(logits, next_token)
     return sample(logits, next_token, temperature, top_k, seed, input_pos, top_p=top_p, min_p=min_p)
@@ -216,16 +285,19 @@ class GraphedDecoder:
     static device tensors; every HIP entry point reads `input_pos` from device memory, so replays advance.
     The sampling settings (temperature, top_k, seed, top_p, min_p; temperature None: greedy) are carried by the captured step BY
     VALUE — the draw itself reads the position from device memory — so a call with other settings than the step was captured with
-    captures again."""
+    captures again.  `logprobs` is one more such setting: the captured step then ends with cc_logprob_rows on its row, scoring
+    `self.target` (the forced token, copied in before the replay; -1 for a free step) or else the token the step just wrote, into
+    static tensors that the caller clones as it clones the token."""
 
-    _SETTINGS = ("temperature", "top_k", "seed", "top_p", "min_p")
+    _SETTINGS = ("temperature", "top_k", "seed", "top_p", "min_p", "logprobs")
 
-    def __init__(self, model, warmup=2, temperature=None, top_k=None, seed=0, top_p=None, min_p=None):
+    def __init__(self, model, warmup=2, temperature=None, top_k=None, seed=0, top_p=None, min_p=None, logprobs=False):
         self.model = model
-        self.sampling = (temperature, top_k, seed, top_p, min_p)
+        self.sampling = (temperature, top_k, seed, top_p, min_p, logprobs)
         dev = model.output.weight.device
         self.tok = torch.zeros((1, 1), dtype=torch.int32, device=dev)
         self.pos = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self.target = torch.full((1,), -1, dtype=torch.int32, device=dev)
         self.graph = None
         self.out_tok = self.out_probs = None
         self.warmup = warmup
@@ -240,6 +312,8 @@ class GraphedDecoder:
         flags = [(getattr(c, "_next_valid", None), getattr(c, "_quant_pending", False)) for c in caches]
         pos0 = self.pos.clone()
         kw = dict(zip(self._SETTINGS, self.sampling))
+        if kw["logprobs"]:
+            kw["score_target"] = self.target
         try:
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
@@ -251,6 +325,8 @@ class GraphedDecoder:
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
                 self.out_tok, self.out_probs = decode_one_token(self.model, self.tok, self.pos, **kw)
+            if kw["logprobs"]:
+                self.out_logprob, self.out_rank = self.out_probs
             self.graph = graph
             self._epoch = self._cache_epoch()
         finally:  # also when capture is refused (e.g. a collective that cannot be captured): the caller falls back to
@@ -291,6 +367,11 @@ class GraphedDecoder:
             self.capture()
         self.tok.copy_(x)
         self.pos.copy_(input_pos)
+        if self.sampling[-1]:
+            if next_token is None:
+                self.target.fill_(-1)
+            else:
+                self.target.copy_(next_token.view(1))
         self.graph.replay()
         if next_token is not None:
             return next_token, self.out_probs
@@ -509,8 +590,13 @@ def decode_n_tokens(model, cur_token, input_pos, decode_one_token, num_new_token
     steps commit them (the last step of a block may be a free one: its token is drawn from its own row at its own position).
     Blocks are eager launches; everything else — free steps, fewer than two known inputs, an ineligible model — runs through
     `decode_one_token` as before.  A single-launch step that fails INSIDE a block cannot be rewound token-wise (earlier layers have
-    committed all T tokens): with `recover` the status word is read once behind each block, and a set word raises."""
+    committed all T tokens): with `recover` the status word is read once behind each block, and a set word raises.
+    `logprobs` (ours; default False: this loop as it was): the second result is not the list of V-sized probability rows but
+    TokenScores(logprob, rank), one element per committed token in commit order (trimmed with the tokens when the loop rewinds).  A
+    forced step runs no softmax and is scored against its forced token; a free step draws its token as before and scores it; a block
+    scores its T rows in one call."""
     new_tokens, new_probs, incs = [], [], []
+    logprobs = bool(kw.get("logprobs", False))
     recover = kw.pop("recover", None)
     block = kw.pop("forced_block", 1)
     block = 1 if block is None else max(1, min(int(block), _MAX_BLOCK))
@@ -526,7 +612,7 @@ def decode_n_tokens(model, cur_token, input_pos, decode_one_token, num_new_token
     def commit(k, nt, npb):
         nonlocal cur, stopped
         new_tokens.append(nt.clone())
-        new_probs.append(npb.clone())
+        new_probs.append(TokenScores(npb.logprob.clone(), npb.rank.clone()) if logprobs else npb.clone())
         teacher_force = prefix is not None and k < len(prefix)
         if terminator_ids and nt in terminator_ids and not teacher_force:
             stopped = True
@@ -555,6 +641,24 @@ def decode_n_tokens(model, cur_token, input_pos, decode_one_token, num_new_token
                 raise_single_launch_failure(cur_token.device)  # (clears the word)
             except Exception as e:
                 raise type(e)(f"in the block of {T} forced decode steps starting at position {int(pos[0])}: {e}") from None
+        if logprobs:
+            n_forced = min(T, len(prefix) - k)  # T or T - 1: only the last step of a block may be a free one
+            targets = torch.full((T,), -1, dtype=torch.int32, device=logits.device)
+            targets[:n_forced] = prefix[k:k + n_forced]
+            fallback = last = None
+            if n_forced < T:
+                row = logits[:, T - 1:T]
+                if kw.get("temperature") is None:
+                    last, _ = greedy(row, None)
+                else:
+                    last, _ = sample(row, None, kw["temperature"], kw.get("top_k"), kw.get("seed", 0), pos[T - 1:T], top_p=kw.get("top_p"),
+                                     min_p=kw.get("min_p"))
+                fallback = torch.zeros((T,), dtype=torch.int32, device=logits.device)
+                fallback[T - 1:] = last.view(1)
+            lp, rk = token_logprobs(logits, targets, fallback)
+            for t in range(T):
+                commit(k + t, forced_at(k + t) if t < n_forced else last, TokenScores(lp[t:t + 1], rk[t:t + 1]))
+            return
         for t in range(T):
             row = logits[:, t:t + 1]
             if kw.get("temperature") is None:
@@ -603,6 +707,10 @@ def decode_n_tokens(model, cur_token, input_pos, decode_one_token, num_new_token
                 break
         if not running and not watch.outstanding():
             break
+    if logprobs:
+        dev = cur_token.device
+        return new_tokens, TokenScores(torch.cat([p.logprob for p in new_probs]) if new_probs else torch.empty(0, dtype=torch.float32, device=dev),
+                                       torch.cat([p.rank for p in new_probs]) if new_probs else torch.empty(0, dtype=torch.int32, device=dev))
     return new_tokens, new_probs
 
 
@@ -610,7 +718,9 @@ def decode_n_tokens(model, cur_token, input_pos, decode_one_token, num_new_token
 def generate(model, prompt, prefill, decode_one_token, max_new_tokens, next_tokens=None, terminator_ids=None,
              feed_long_prompts=False, decode_first_token=False, attn_top_k=1.0, **kw):
     """ref: generation_utils.py:399-531 (prompt-splitting rules, teacher forcing, perf stats).  Unlike the
-    reference, the prefill timer is closed after a device sync (SURVEY §5 note)."""
+    reference, the prefill timer is closed after a device sync (SURVEY §5 note).  `logprobs=True` (ours): the second result is
+    TokenScores(logprob, rank) of `decode_tokens` elements — the committed tokens' fp32 log-probabilities and ranks — instead of the
+    list of probability rows (perplexity() turns the first into the reference's ppl figures)."""
     prompt_length = prompt.size(0)
     device, dtype = prompt.device, prompt.dtype
     _restore_l2_handoff()
@@ -645,7 +755,9 @@ def generate(model, prompt, prefill, decode_one_token, max_new_tokens, next_toke
     ret = prefill(model, prompt.view(1, -1), input_pos, next_token=next_token, **kw)
     sync()
     t1 = time.perf_counter()
-    next_token, next_tok_probs = ret[0].clone(), ret[1].clone()
+    logprobs = bool(kw.get("logprobs", False))
+    next_token = ret[0].clone()
+    next_tok_probs = TokenScores(ret[1].logprob.clone(), ret[1].rank.clone()) if logprobs else ret[1].clone()
     seq[prompt_length] = next_token
     input_pos = torch.tensor([prompt_length], device=device, dtype=torch.int)
     toks, tok_probs = decode_n_tokens(model, next_token.view(1, -1), input_pos, decode_one_token, max_new_tokens - 1,
@@ -673,6 +785,8 @@ def generate(model, prompt, prefill, decode_one_token, max_new_tokens, next_toke
         seq[prompt_length + 1: prompt_length + 1 + len(toks)] = torch.cat(toks)
     if -1 in seq:
         seq = seq[: torch.where(seq == -1)[0][0]]
+    if logprobs:  # (element 0: the token behind the prefill, scored from the prefill's last row)
+        return seq, TokenScores(torch.cat([next_tok_probs.logprob, tok_probs.logprob]), torch.cat([next_tok_probs.rank, tok_probs.rank])), stats
     return seq, [next_tok_probs] + tok_probs, stats
 
 

@@ -3,7 +3,7 @@
 These are NOT part of the cache/attention hot path — they are the model-side code around it
 (ref: model.py:317-327, 375-387, 442-443, 452-457, 507-519), which the reference leaves to ~45 eager elementwise
 launches per layer or to torch.compile.  On device tensors they call the C ABI (`cc_add_rmsnorm`, `cc_qkv_rope`,
-`cc_silu_mul`, `cc_gemv_fused`, `cc_gemv_fused_multi` and its int8 / MXFP4 forms, `cc_softmax_argmax`, `cc_sample_topk`, `cc_sample_nucleus`); CPU tensors raise — there is no host path in the package (the
+`cc_silu_mul`, `cc_gemv_fused`, `cc_gemv_fused_multi` and its int8 / MXFP4 forms, `cc_softmax_argmax`, `cc_sample_topk`, `cc_sample_nucleus`, `cc_logprob_rows`); CPU tensors raise — there is no host path in the package (the
 CPU model-wiring test brings its own eager twins: tests/host_glue.py).
 """
 import ctypes as C
@@ -291,3 +291,36 @@ def sample_nucleus(logits, temperature, top_k, top_p, min_p, seed, input_pos, re
 
 
 _SN_WS = {}
+
+
+def logprob_rows(logits_2d, targets=None, fallback=None, want_rank=True):
+    """Per-row log-probability of a target token, the row's log-sum-exp and the target's rank, in fp32 from the logits themselves
+    (cc_logprob_rows; include/coldcompress.h has the contract).  logits_2d: [T, V] (or one row [V]) on the device, T <= 64; a view
+    with a row stride is passed as it is, without a copy.  targets / fallback: int32 DEVICE tensors of T elements or None; row r is
+    scored against targets[r] where that is >= 0 and against fallback[r] otherwise — both are read by the kernels, so a captured
+    step scores the token of each replay.  -> (logprob [T] fp32, lse [T] fp32, rank [T] int32, or None without `want_rank`)."""
+    if not logits_2d.is_cuda:
+        _host(logits_2d, "logprob_rows logits")
+    x = logits_2d.view(1, -1) if logits_2d.dim() == 1 else logits_2d
+    if x.dim() != 2 or x.dtype not in _DT:
+        raise _abi.ColdCompressError(f"logprob_rows: logits must be [T, V] in float32 / bfloat16 / float16, got {x.dtype} {tuple(x.shape)}")
+    T, V = x.shape
+    if V > 1 and x.stride(1) != 1 or (T > 1 and x.stride(0) < V):
+        x = x.contiguous()
+    stride = x.stride(0) if T > 1 else V
+    for name, t in (("targets", targets), ("fallback", fallback)):
+        if t is not None and not (t.is_cuda and t.dtype == torch.int32 and t.numel() == T and t.is_contiguous()):
+            raise _abi.ColdCompressError(f"logprob_rows: {name} must be a contiguous int32 device tensor of {T} elements, got {t.dtype} "
+                                         f"{tuple(t.shape)} on {t.device}")
+    logprob = torch.empty((T,), dtype=torch.float32, device=x.device)
+    lse = torch.empty((T,), dtype=torch.float32, device=x.device)
+    rank = torch.empty((T,), dtype=torch.int32, device=x.device) if want_rank else None
+    ws = _LP_WS.get(x.device)
+    if ws is None:
+        ws = _LP_WS[x.device] = torch.empty(int(_abi.lib()["cc_logprob_rows_workspace_bytes"]()), dtype=torch.uint8, device=x.device)
+    _abi.call("cc_logprob_rows", _p(x), T, V, int(stride), _DT[x.dtype], _p(targets), _p(fallback), _p(logprob), _p(lse), _p(rank), _p(ws),
+              ws.numel(), _stream())
+    return logprob, lse, rank
+
+
+_LP_WS = {}

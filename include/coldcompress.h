@@ -946,6 +946,41 @@ int cc_sample_nucleus(const void* logits, int32_t V, int32_t dtype, float temper
                       uint64_t seed, const int32_t* input_pos, void* probs, int32_t* idx_out, int32_t* n_kept_out,
                       void* workspace, size_t workspace_bytes, cc_stream_t stream);
 
+/* Per-token log-probabilities: what a perplexity evaluation reads from the logits (ref: eval.py:230-241 takes the log of a probability
+ * row that generate() returned; this entry point returns the one number per token instead of the row).  logits: T rows of V elements
+ * of the model dtype (`dtype`), row r at logits + r * row_stride elements, row_stride >= V — a [1, T, V] block of logits, a single row,
+ * or a strided view of either.  EVERY pointer is a device pointer, targets and fallback included: nothing is read on the host, so a
+ * captured step advances through them.  logprob[T] (fp32), lse[T] (fp32, may be NULL), rank[T] (int32, may be NULL).
+ *   1. values    x_i = float(logits[r][i]), exact.  No temperature and no filters: the model's own distribution, whatever the sampler
+ *                of the step was asked to do.
+ *   2. target    t = targets[r] if targets is non-NULL and targets[r] >= 0, else fallback[r] (a captured step scores either the forced
+ *                token or the token its sampler just wrote).  A t outside [0, V), or no pointer to take it from: logprob[r] = NaN and
+ *                rank[r] = -1; lse[r] is still written.  No address outside the row is ever formed from t.
+ *   3. lse       in fp32.  The vocabulary is cut into the launch's fixed number of slices (128, slice starts at multiples of 8
+ *                elements); slice g leaves (m_g, s_g = sum of exp(x_i - m_g)) in the workspace, and ONE fold in a fixed order gives
+ *                M = max m_g and S = sum of s_g * exp(m_g - M); empty slices contribute nothing.  lse = M + log S and
+ *                logprob = (x_t - M) - log S.  exp and log are libm-grade (<= 2 ulp) for every dtype: the result is fp32, so the
+ *                greedy tail's v_exp_f32 shortcut for 16-bit outputs does not apply.  exp(x - m) is taken as exactly 1 where x == m.
+ *   4. rank      rank[r] = the number of i with x_i > x_t, exact: 0 means the target is the top logit or tied for it.  NaN elements
+ *                never count; rank[r] = -1 when x_t is NaN.
+ *   5. classes   the class of logprob[r] and lse[r] (finite, -inf, NaN) is that of float64 torch.log_softmax / torch.logsumexp on the
+ *                same row, rounded to fp32: a NaN anywhere gives NaN for both; a +inf gives lse = +inf and logprob = NaN; a row of
+ *                -inf alone gives lse = -inf and logprob = NaN; a -inf target under a finite maximum gives logprob = -inf.
+ *   6. determinism  a row's three results are a pure function of that row's values and its target: bit-identical from run to run, in
+ *                eager launches and under hipGraph replay, and whether the row is scored alone or as row r of T with any rows around
+ *                it and at any alignment (an element's place in the summation order depends on its index alone, not on how it was
+ *                loaded: 16 bytes per lane where the row's base is 16-byte aligned, element-wise otherwise).  No atomics on global
+ *                memory and no tickets: per-slice partials folded in a fixed order, as cc_sample_topk's.
+ * Two launches: a (128, T) grid for the partials, with the target compare counted in the same pass, and T workgroups for the fold.
+ * Never synchronises, never allocates, stream-capturable; `workspace` (cc_logprob_rows_workspace_bytes, 16-byte aligned) needs no
+ * initialisation.  CC_ERR_BAD_ARG before any launch: a NULL logits / logprob / workspace, T < 1, T > CC_LOGPROB_MAX_ROWS, V < 1,
+ * row_stride < V, a dtype that is none of the three.  CC_ERR_WORKSPACE: a workspace shorter than cc_logprob_rows_workspace_bytes(). */
+#define CC_LOGPROB_MAX_ROWS 64
+size_t cc_logprob_rows_workspace_bytes(void);
+int cc_logprob_rows(const void* logits, int32_t T, int32_t V, int64_t row_stride, int32_t dtype, const int32_t* targets,
+                    const int32_t* fallback, float* logprob, float* lse, int32_t* rank, void* workspace, size_t workspace_bytes,
+                    cc_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * One-shot sum all-reduce over the GPUs of ONE node, for the decode-size messages of tensor parallelism.
  * ref: tp.py:134-138, 156-160 (`all_reduce(sum)` of the wo and FFN outputs: 2 * dim bytes, 8-16 KiB, twice per layer).
