@@ -11,6 +11,7 @@ from typing import NamedTuple
 import torch
 
 from .model import Transformer, find_multiple
+from .penalties import LogitPenalties, active as _active_penalties  # noqa: F401
 
 
 # ------------------------------------------------------------------------------ budgets (ref: :224-321)
@@ -240,40 +241,56 @@ def perplexity(logprob, every=500):
     return out
 
 
-def _scored(logits, next_token, temperature, top_k, seed, input_pos, top_p, min_p, score_target=None):
+def _scored(logits, next_token, temperature, top_k, seed, input_pos, top_p, min_p, score_target=None, chosen_from=None):
     """One step's token and its TokenScores (logprobs=True).  A forced step runs no softmax and keeps no row: it is scored against its
     forced token.  A free step chooses its token exactly as greedy / sample do and scores it through `fallback`; so does a captured
-    step (`score_target`: a one-element int32 device tensor the replay reads — the forced token, or -1 for what the step chose)."""
+    step (`score_target`: a one-element int32 device tensor the replay reads — the forced token, or -1 for what the step chose).
+    `chosen_from`: the penalised logits the token is chosen from (LogitPenalties); the scores stay the model's own row's."""
     row = logits[:, -1:]
     if next_token is not None and score_target is None:
         return next_token, TokenScores(*token_logprobs(row, next_token.view(1)))
+    pick = row if chosen_from is None else chosen_from[:, -1:]
     if temperature is None:
-        idx_next, _ = greedy(row, None)
+        idx_next, _ = greedy(pick, None)
     else:
-        idx_next, _ = sample(row, None, temperature, top_k, seed, input_pos, top_p=top_p, min_p=min_p)
+        idx_next, _ = sample(pick, None, temperature, top_k, seed, input_pos, top_p=top_p, min_p=min_p)
     scores = TokenScores(*token_logprobs(row, score_target, fallback=idx_next.view(1)))
     return (idx_next if next_token is None else next_token), scores
 
 
-def prefill(model, x, input_pos, next_token=None, temperature=None, top_k=None, seed=0, top_p=None, min_p=None, logprobs=False, **_):
+def prefill(model, x, input_pos, next_token=None, temperature=None, top_k=None, seed=0, top_p=None, min_p=None, logprobs=False,
+            penalties=None, **_):
     """ref: generation_utils.py:145-160 — the causal mask is implicit in the HIP prefill kernel.  `temperature` None: greedy;
     otherwise the token is drawn at the last prompt position (sample), behind the top_k / top_p / min_p filters.  `logprobs`: the
-    second result is the token's TokenScores, taken from the last row, instead of that row's probabilities."""
+    second result is the token's TokenScores, taken from the last row, instead of that row's probabilities.  `penalties` (a
+    LogitPenalties whose `reset` has counted this prompt): the token is chosen from the penalised last row and the probabilities are
+    that row's; the scores stay the model's own."""
     logits = model(x, input_pos, mask=None, is_prefill=True)
+    pen = _active_penalties(penalties)
+    chosen_from = None
+    if pen is not None:  # (the prompt is already counted: this row adds nothing)
+        chosen_from = pen.apply(logits[:, -1:])
     if logprobs:
-        return _scored(logits, next_token, temperature, top_k, seed, input_pos[-1:], top_p, min_p)
+        return _scored(logits, next_token, temperature, top_k, seed, input_pos[-1:], top_p, min_p, chosen_from=chosen_from)
+    if chosen_from is not None:
+        logits = chosen_from
     if temperature is None:
         return greedy(logits, next_token)
     return sample(logits, next_token, temperature, top_k, seed, input_pos[-1:], top_p=top_p, min_p=min_p)
 
 
 def decode_one_token(model, x, input_pos, next_token=None, attn_top_k=1.0, temperature=None, top_k=None, seed=0, top_p=None, min_p=None,
-                     logprobs=False, score_target=None, **_):
+                     logprobs=False, score_target=None, penalties=None, **_):
     """ref: generation_utils.py:163-178.  `temperature` None: greedy; otherwise the token is drawn at `input_pos` (sample).
-    `logprobs`: the second result is the token's TokenScores instead of the row's probabilities (_scored)."""
+    `logprobs`: the second result is the token's TokenScores instead of the row's probabilities (_scored).  `penalties`: the step's
+    input `x` at `input_pos` is counted (both read from device memory) and the token is chosen from the penalised row."""
     logits = model(x, input_pos, is_prefill=False, attn_top_k=attn_top_k)
+    pen = _active_penalties(penalties)
+    chosen_from = pen.apply(logits[:, -1:], x, input_pos) if pen is not None else None
     if logprobs:
-        return _scored(logits, next_token, temperature, top_k, seed, input_pos, top_p, min_p, score_target)
+        return _scored(logits, next_token, temperature, top_k, seed, input_pos, top_p, min_p, score_target, chosen_from=chosen_from)
+    if chosen_from is not None:
+        logits = chosen_from
     if temperature is None:
         return greedy(logits, next_token)
     return sample(logits, next_token, temperature, top_k, seed, input_pos, top_p=top_p, min_p=min_p)
@@ -287,13 +304,16 @@ class GraphedDecoder:
     VALUE — the draw itself reads the position from device memory — so a call with other settings than the step was captured with
     captures again.  `logprobs` is one more such setting: the captured step then ends with cc_logprob_rows on its row, scoring
     `self.target` (the forced token, copied in before the replay; -1 for a free step) or else the token the step just wrote, into
-    static tensors that the caller clones as it clones the token."""
+    static tensors that the caller clones as it clones the token.  `penalties` (a LogitPenalties; None or a neutral one: none) is
+    one more: the captured step holds the addresses of its buffers and advances its counts from `self.tok` / `self.pos`; objects
+    compare by identity, so the same object reused across generations does not capture again."""
 
-    _SETTINGS = ("temperature", "top_k", "seed", "top_p", "min_p", "logprobs")
+    _SETTINGS = ("temperature", "top_k", "seed", "top_p", "min_p", "logprobs", "penalties")
+    _LOGPROBS = 5  # (index of `logprobs` in the settings)
 
-    def __init__(self, model, warmup=2, temperature=None, top_k=None, seed=0, top_p=None, min_p=None, logprobs=False):
+    def __init__(self, model, warmup=2, temperature=None, top_k=None, seed=0, top_p=None, min_p=None, logprobs=False, penalties=None):
         self.model = model
-        self.sampling = (temperature, top_k, seed, top_p, min_p, logprobs)
+        self.sampling = (temperature, top_k, seed, top_p, min_p, logprobs, _active_penalties(penalties))
         dev = model.output.weight.device
         self.tok = torch.zeros((1, 1), dtype=torch.int32, device=dev)
         self.pos = torch.zeros((1,), dtype=torch.int32, device=dev)
@@ -312,6 +332,8 @@ class GraphedDecoder:
         flags = [(getattr(c, "_next_valid", None), getattr(c, "_quant_pending", False)) for c in caches]
         pos0 = self.pos.clone()
         kw = dict(zip(self._SETTINGS, self.sampling))
+        pen = kw["penalties"]
+        pen_snap = pen.snapshot() if pen is not None else None  # (the warm-up steps and the captured step would be counted)
         if kw["logprobs"]:
             kw["score_target"] = self.target
         try:
@@ -331,6 +353,8 @@ class GraphedDecoder:
             self._epoch = self._cache_epoch()
         finally:  # also when capture is refused (e.g. a collective that cannot be captured): the caller falls back to
             self.pos.copy_(pos0)  # eager launches and must find the state it handed in
+            if pen is not None:
+                pen.restore(pen_snap)
             for c, sn, fl in zip(caches, snap, flags):
                 for k, v in sn.items():
                     c._buffers[k].copy_(v)
@@ -346,6 +370,7 @@ class GraphedDecoder:
 
     def __call__(self, model, x, input_pos, next_token=None, **kw):
         sampling = tuple(kw.get(k, d) for k, d in zip(self._SETTINGS, self.sampling))
+        sampling = sampling[:-1] + (_active_penalties(sampling[-1]),)
         if sampling != self.sampling:  # (carried by value, like what _cache_epoch watches: capture again)
             self.sampling = sampling
             self.graph = None
@@ -367,7 +392,7 @@ class GraphedDecoder:
             self.capture()
         self.tok.copy_(x)
         self.pos.copy_(input_pos)
-        if self.sampling[-1]:
+        if self.sampling[self._LOGPROBS]:
             if next_token is None:
                 self.target.fill_(-1)
             else:
@@ -429,7 +454,7 @@ def _collective_status(dev):
     return st
 
 
-def _recover_token(model, cur_token, input_pos, decode_fn, nt, npb, forced, attn_top_k, kw, max_retries=6):
+def _recover_token(model, cur_token, input_pos, decode_fn, nt, npb, forced, attn_top_k, kw, max_retries=6, rebuild=None):
     """In-band recovery from a single-launch hand-off that could not complete (a launch whose workgroups were not all resident: a
     co-tenant kernel on the device; or, with the L2-resident hand-off, a workgroup that found itself on an unexpected XCD).  Called
     when the status word of the decode workspace is known to be set: the failed step committed nothing of its kv head, every later
@@ -438,7 +463,9 @@ def _recover_token(model, cur_token, input_pos, decode_fn, nt, npb, forced, attn
     step.  From the FOURTH attempt on (three have failed) the L2-resident hand-off is demoted ON THIS DEVICE (memory hand-off; a
     captured graph is dropped and captured again) — until the next generate() call.
     Caches whose step carries no commit words (`recoverable()` False) and a failure that persists raise.  Under tensor parallelism
-    the status is the maximum over the ranks, so all ranks take every branch here together."""
+    the status is the maximum over the ranks, so all ranks take every branch here together.
+    `rebuild` (with LogitPenalties): called before every retry — the failed attempt's penalise launch counted its input all the same,
+    and it puts the counts back to the histogram of the inputs before this token."""
     from .. import _abi
     from ..attention_utils import raise_single_launch_failure, reset_single_launch_status
 
@@ -468,6 +495,8 @@ def _recover_token(model, cur_token, input_pos, decode_fn, nt, npb, forced, attn
             if hasattr(decode_fn, "graph"):
                 decode_fn.graph = None  # captured with the L2-resident form: capture again
         time.sleep(0.05 * tries)  # whatever shared the device gets a moment to leave
+        if rebuild is not None:
+            rebuild()
         nt, npb = decode_fn(model, cur_token, input_pos, next_token=forced, attn_top_k=attn_top_k, **kw)
     return nt, npb
 
@@ -594,8 +623,13 @@ def decode_n_tokens(model, cur_token, input_pos, decode_one_token, num_new_token
     `logprobs` (ours; default False: this loop as it was): the second result is not the list of V-sized probability rows but
     TokenScores(logprob, rank), one element per committed token in commit order (trimmed with the tokens when the loop rewinds).  A
     forced step runs no softmax and is scored against its forced token; a free step draws its token as before and scores it; a block
-    scores its T rows in one call."""
+    scores its T rows in one call.
+    `penalties` (ours; default None: this loop as it was): a LogitPenalties whose counts hold the prompt; every step counts its input
+    token and chooses from the penalised row (a block in one call over its T rows).  Launches behind a set status word do nothing to
+    the caches but their penalise launches still count their garbage inputs: a rewind rebuilds the counts from the inputs of the
+    steps that stay committed before the failed token runs again, and so does every retry."""
     new_tokens, new_probs, incs = [], [], []
+    pen = _active_penalties(kw.get("penalties"))
     logprobs = bool(kw.get("logprobs", False))
     recover = kw.pop("recover", None)
     block = kw.pop("forced_block", 1)
@@ -622,6 +656,14 @@ def decode_n_tokens(model, cur_token, input_pos, decode_one_token, num_new_token
         incs.append(1)
         cur = nt.view(1, -1)
 
+    def rebuild_before(k):
+        """the counts as step k must find them: prompt ‖ inputs of steps < k (tok0 and new_tokens[:k-1]); `input_pos` is step k's."""
+        inputs = torch.cat([tok0.view(-1)] + [t.view(-1) for t in new_tokens[:k - 1]]) if k > 0 else tok0.view(-1)[:0]
+        pen.rebuild(inputs, int(input_pos.view(-1)[0]) - k)
+
+    def recover_kw(k):
+        return {"rebuild": lambda: rebuild_before(k)} if pen is not None else {}
+
     def block_len(k):
         """how many steps from k on run as one block: all but the last must be forced; 0: step k runs on its own."""
         if not use_blocks:
@@ -641,6 +683,9 @@ def decode_n_tokens(model, cur_token, input_pos, decode_one_token, num_new_token
                 raise_single_launch_failure(cur_token.device)  # (clears the word)
             except Exception as e:
                 raise type(e)(f"in the block of {T} forced decode steps starting at position {int(pos[0])}: {e}") from None
+        own = logits  # (the model's own rows: what logprobs scores)
+        if pen is not None:
+            logits = pen.apply(logits, idx, pos)
         if logprobs:
             n_forced = min(T, len(prefix) - k)  # T or T - 1: only the last step of a block may be a free one
             targets = torch.full((T,), -1, dtype=torch.int32, device=logits.device)
@@ -655,7 +700,7 @@ def decode_n_tokens(model, cur_token, input_pos, decode_one_token, num_new_token
                                      min_p=kw.get("min_p"))
                 fallback = torch.zeros((T,), dtype=torch.int32, device=logits.device)
                 fallback[T - 1:] = last.view(1)
-            lp, rk = token_logprobs(logits, targets, fallback)
+            lp, rk = token_logprobs(own, targets, fallback)
             for t in range(T):
                 commit(k + t, forced_at(k + t) if t < n_forced else last, TokenScores(lp[t:t + 1], rk[t:t + 1]))
             return
@@ -679,7 +724,7 @@ def decode_n_tokens(model, cur_token, input_pos, decode_one_token, num_new_token
         elif running and not drain:
             nt, npb = decode_one_token(model, cur, input_pos, next_token=forced_at(i), attn_top_k=attn_top_k, **kw)
             if recover and tp:  # collective and synchronous (opt-in): every rank takes the same branch
-                nt, npb = _recover_token(model, cur, input_pos, decode_one_token, nt, npb, forced_at(i), attn_top_k, kw)
+                nt, npb = _recover_token(model, cur, input_pos, decode_one_token, nt, npb, forced_at(i), attn_top_k, kw, **recover_kw(i))
             if watch is not None:
                 watch.post(i)
             commit(i, nt, npb)
@@ -700,7 +745,9 @@ def decode_n_tokens(model, cur_token, input_pos, decode_one_token, num_new_token
                 cur = new_tokens[f - 1].view(1, -1) if f > 0 else tok0
                 stopped = False
                 watch.clear()
-                nt, npb = _recover_token(model, cur, input_pos, decode_one_token, None, None, forced_at(f), attn_top_k, kw)
+                if pen is not None:
+                    rebuild_before(f)
+                nt, npb = _recover_token(model, cur, input_pos, decode_one_token, None, None, forced_at(f), attn_top_k, kw, **recover_kw(f))
                 commit(f, nt, npb)
                 i = f + 1
                 running = i < num_new_tokens and not stopped
@@ -720,9 +767,14 @@ def generate(model, prompt, prefill, decode_one_token, max_new_tokens, next_toke
     """ref: generation_utils.py:399-531 (prompt-splitting rules, teacher forcing, perf stats).  Unlike the
     reference, the prefill timer is closed after a device sync (SURVEY §5 note).  `logprobs=True` (ours): the second result is
     TokenScores(logprob, rank) of `decode_tokens` elements — the committed tokens' fp32 log-probabilities and ranks — instead of the
-    list of probability rows (perplexity() turns the first into the reference's ppl figures)."""
+    list of probability rows (perplexity() turns the first into the reference's ppl figures).
+    `penalties=LogitPenalties(...)` (ours): repetition / frequency / presence penalties and a logit bias on every row a token is
+    chosen from, with the token history on the device; the object is reset with the tokens that are prefilled, and positions from the
+    ORIGINAL prompt length on count as generated (a teacher-forced continuation included).  The returned probability rows are the
+    penalised distribution's; `logprobs` keeps scoring under the model's own."""
     prompt_length = prompt.size(0)
     device, dtype = prompt.device, prompt.dtype
+    gen_start = prompt_length  # (penalties: a prompt tail that is fed through decode steps below still counts as prompt)
     _restore_l2_handoff()
     min_cache_length = model.min_cache_length()
     max_prompt_len = min_cache_length - 1
@@ -750,6 +802,9 @@ def generate(model, prompt, prefill, decode_one_token, max_new_tokens, next_toke
         if device.type == "cuda":
             torch.cuda.synchronize(device)
 
+    pen = _active_penalties(kw.get("penalties"))
+    if pen is not None:
+        pen.reset(prompt, gen_start)
     sync()
     t0 = time.perf_counter()
     ret = prefill(model, prompt.view(1, -1), input_pos, next_token=next_token, **kw)

@@ -3,7 +3,8 @@
 These are NOT part of the cache/attention hot path — they are the model-side code around it
 (ref: model.py:317-327, 375-387, 442-443, 452-457, 507-519), which the reference leaves to ~45 eager elementwise
 launches per layer or to torch.compile.  On device tensors they call the C ABI (`cc_add_rmsnorm`, `cc_qkv_rope`,
-`cc_silu_mul`, `cc_gemv_fused`, `cc_gemv_fused_multi` and its int8 / MXFP4 forms, `cc_softmax_argmax`, `cc_sample_topk`, `cc_sample_nucleus`, `cc_logprob_rows`); CPU tensors raise — there is no host path in the package (the
+`cc_silu_mul`, `cc_gemv_fused`, `cc_gemv_fused_multi` and its int8 / MXFP4 forms, `cc_softmax_argmax`, `cc_sample_topk`, `cc_sample_nucleus`, `cc_logprob_rows`,
+`cc_token_counts_add`, `cc_logits_penalize`); CPU tensors raise — there is no host path in the package (the
 CPU model-wiring test brings its own eager twins: tests/host_glue.py).
 """
 import ctypes as C
@@ -324,3 +325,60 @@ def logprob_rows(logits_2d, targets=None, fallback=None, want_rank=True):
 
 
 _LP_WS = {}
+
+
+def _counts_ok(what, V, prompt_count, gen_count, gen_start):
+    for name, t, n in (("prompt_count", prompt_count, V), ("gen_count", gen_count, V), ("gen_start", gen_start, 1)):
+        if not (t.is_cuda and t.dtype == torch.int32 and t.numel() == n and t.is_contiguous()):
+            raise _abi.ColdCompressError(f"{what}: {name} must be a contiguous int32 device tensor of {n} elements, got {t.dtype} "
+                                         f"{tuple(t.shape)} on {t.device}")
+
+
+def token_counts_add(prompt_count, gen_count, tokens, first_pos, gen_start):
+    """Add `tokens` (an int32 DEVICE tensor: the inputs at positions first_pos .. first_pos + n - 1, first_pos a host int) to the
+    token-history state of cc_logits_penalize, in place: each to `gen_count` where its position is >= *gen_start and to `prompt_count`
+    otherwise (cc_token_counts_add; include/coldcompress.h has the contract).  Tokens outside the vocabulary count nothing."""
+    V = prompt_count.numel()
+    _counts_ok("token_counts_add", V, prompt_count, gen_count, gen_start)
+    if not (tokens.is_cuda and tokens.dtype == torch.int32 and tokens.is_contiguous()):
+        raise _abi.ColdCompressError(f"token_counts_add: tokens must be a contiguous int32 device tensor, got {tokens.dtype} "
+                                     f"{tuple(tokens.shape)} on {tokens.device}")
+    _abi.call("cc_token_counts_add", _p(prompt_count), _p(gen_count), V, _p(tokens), tokens.numel(), int(first_pos), _p(gen_start),
+              _stream())
+
+
+def logits_penalize(logits_2d, prompt_count, gen_count, gen_start, tokens=None, pos=None, repetition_penalty=1.0, frequency_penalty=0.0,
+                    presence_penalty=0.0, bias=None, out=None):
+    """The repetition / frequency / presence penalties and the logit bias on T <= 4 rows of logits, and the rows' input tokens counted
+    into the state, in one launch (cc_logits_penalize; include/coldcompress.h has the contract).  logits_2d: [T, V] (or one row [V])
+    on the device; a view with a row stride is passed as it is.  tokens / pos: int32 DEVICE tensors of T elements — the inputs of the
+    T steps and their positions, read by the kernel, so a captured step counts the token of each replay — or None: count nothing.
+    bias: fp32 [V] on the device or None.  out: None (a new contiguous tensor) or `logits_2d` itself (in place).  -> out."""
+    if not logits_2d.is_cuda:
+        _host(logits_2d, "logits_penalize logits")
+    x = logits_2d.view(1, -1) if logits_2d.dim() == 1 else logits_2d
+    if x.dim() != 2 or x.dtype not in _DT:
+        raise _abi.ColdCompressError(f"logits_penalize: logits must be [T, V] in float32 / bfloat16 / float16, got {x.dtype} {tuple(x.shape)}")
+    T, V = x.shape
+    inplace = out is not None
+    if inplace and out is not logits_2d:
+        raise _abi.ColdCompressError("logits_penalize: out must be None or the logits tensor itself")
+    if V > 1 and x.stride(1) != 1 or (T > 1 and x.stride(0) < V):
+        if inplace:
+            raise _abi.ColdCompressError("logits_penalize: in place needs rows of unit element stride that do not overlap")
+        x = x.contiguous()
+    stride = x.stride(0) if T > 1 else V
+    _counts_ok("logits_penalize", V, prompt_count, gen_count, gen_start)
+    if (tokens is None) != (pos is None):
+        raise _abi.ColdCompressError("logits_penalize: tokens and pos come together")
+    for name, t in (("tokens", tokens), ("pos", pos)):
+        if t is not None and not (t.is_cuda and t.dtype == torch.int32 and t.numel() == T and t.is_contiguous()):
+            raise _abi.ColdCompressError(f"logits_penalize: {name} must be a contiguous int32 device tensor of {T} elements, got {t.dtype} "
+                                         f"{tuple(t.shape)} on {t.device}")
+    if bias is not None and not (bias.is_cuda and bias.dtype == torch.float32 and bias.numel() == V and bias.is_contiguous()):
+        raise _abi.ColdCompressError(f"logits_penalize: bias must be a contiguous float32 device tensor of {V} elements, got {bias.dtype} "
+                                     f"{tuple(bias.shape)} on {bias.device}")
+    y = x if inplace else torch.empty((T, stride), dtype=x.dtype, device=x.device)[:, :V]  # (one row stride serves both sides)
+    _abi.call("cc_logits_penalize", _p(x), _p(y), T, V, int(stride), _DT[x.dtype], _p(prompt_count), _p(gen_count), _p(tokens), _p(pos),
+              _p(gen_start), float(repetition_penalty), float(frequency_penalty), float(presence_penalty), _p(bias), _stream())
+    return logits_2d if inplace else y

@@ -981,6 +981,47 @@ int cc_logprob_rows(const void* logits, int32_t T, int32_t V, int64_t row_stride
                     const int32_t* fallback, float* logprob, float* lse, int32_t* rank, void* workspace, size_t workspace_bytes,
                     cc_stream_t stream);
 
+/* Token-history penalties and a logit bias in FRONT of the sampling tail: HF / vLLM's repetition_penalty, the OpenAI API's
+ * frequency_penalty / presence_penalty / logit_bias.  Unlike every other stage of the tail they depend on what has been fed so far, so
+ * the history lives on the DEVICE: prompt_count[V] and gen_count[V] (int32: how often each token has been an input) and gen_start[1]
+ * (int32, a position).  An input token at position p counts as GENERATED when p >= *gen_start and as PROMPT otherwise.  The same answer
+ * in eager launches, under hipGraph replay (the step's input token and position are read from device memory, and the counts advance
+ * in place), in blocks of T known steps and on every tensor-parallel rank (replicated logits: identical counts, no communication).
+ *
+ * cc_token_counts_add: tokens[n] (device int32) are the inputs at positions first_pos .. first_pos + n - 1 (first_pos: a host int);
+ * each is added to the array its position selects, by integer atomicAdd — exact in any order.  A token outside [0, V) counts nothing
+ * and no address is formed from it.  n == 0: CC_OK without a launch.  For the prefill (the whole prompt in one launch) and for
+ * rebuilding the state after a rewind.  A NULL array / gen_start, V <= 0, n < 0, NULL tokens with n > 0: CC_ERR_BAD_ARG.
+ *
+ * cc_logits_penalize: logits and out are T rows of V elements of the model dtype (`dtype`), row t at + t * row_stride elements,
+ * 1 <= T <= CC_GEMV_MULTI_MAX_T; out may be logits itself (in place) but must not overlap it otherwise.  tokens[T] / pos[T] (device
+ * int32): the input tokens of the T steps whose rows these are and their positions; tokens NULL: count nothing (the prefill's row:
+ * its prompt was added by cc_token_counts_add).  bias: float[V] or NULL.  Element v of all T rows has ONE owner:
+ *     cp = prompt_count[v]; cg = gen_count[v]
+ *     for t in 0 .. T-1:                                  row t sees the inputs of steps <= t
+ *         if tokens and tokens[t] == v: (pos[t] >= *gen_start ? cg : cp) += 1
+ *         x = float(logits[t][v])                                           exact
+ *         if cp + cg > 0: x = x > 0 ? x / r : x * r       repetition (HF / vLLM: prompt and generated); one IEEE fp32 operation
+ *         x = x - f * float(cg)                           frequency (OpenAI / vLLM: generated only); two roundings, no fma
+ *         if cg > 0: x = x - p                            presence  (generated only)
+ *         if bias: x = x + bias[v]                        -inf bans a token
+ *         out[t][v] = T(x)                                ONE rounding to the model dtype
+ *     prompt_count[v] = cp; gen_count[v] = cg             stored only where it changed
+ * r == 1, f == 0 and p == 0 each skip their line (exactly, also for infinities); fp32 subnormals are kept; a NaN logit stays NaN; zeros
+ * of both signs take the product (x > 0 is false).  A token outside [0, V) matches no v.  The bits do not depend on how an element
+ * was loaded: 16 bytes at a time where the base of a row (of the counts, of bias) is 16-byte aligned, element by element where it is
+ * not (rows 1 .. T-1 of an odd V).  One launch, no atomics, no workspace; plain vector stores.  Never synchronises, never allocates,
+ * stream-capturable.  Before any launch — CC_ERR_BAD_ARG: T outside 1 .. CC_GEMV_MULTI_MAX_T, V <= 0, row_stride < V, a NULL logits /
+ * out / prompt_count / gen_count / gen_start (or pos with tokens given), out overlapping logits without being it,
+ * repetition_penalty not finite or <= 0, frequency_penalty or presence_penalty not finite; CC_ERR_UNSUPPORTED: a dtype that is none
+ * of CC_DT_F32 / CC_DT_BF16 / CC_DT_F16. */
+int cc_token_counts_add(int32_t* prompt_count, int32_t* gen_count, int32_t V, const int32_t* tokens, int32_t n, int32_t first_pos,
+                        const int32_t* gen_start, cc_stream_t stream);
+int cc_logits_penalize(const void* logits, void* out, int32_t T, int32_t V, int64_t row_stride, int32_t dtype, int32_t* prompt_count,
+                       int32_t* gen_count, const int32_t* tokens, const int32_t* pos, const int32_t* gen_start,
+                       float repetition_penalty, float frequency_penalty, float presence_penalty, const float* bias,
+                       cc_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * One-shot sum all-reduce over the GPUs of ONE node, for the decode-size messages of tensor parallelism.
  * ref: tp.py:134-138, 156-160 (`all_reduce(sum)` of the wo and FFN outputs: 2 * dim bytes, 8-16 KiB, twice per layer).
