@@ -213,7 +213,7 @@ int cc_silu_mul(const void* a, const void* b, int64_t n, int32_t dtype, void* ou
 // first index of the largest ROUNDED probability (torch.argmax returns the first maximal element).
 // Two small launches over kSmBlocks workgroups instead of torch's softmax + reduce kernels (35 + 41 us at vocab
 // 128256; a single-workgroup version is VALU-bound on one CU at 39 us):
-//   pass 1: per-slice (max, sum of exp) partials;
+//   pass 1: per-slice (max, sum of exp) partials; a slice of nothing but -inf leaves (-inf, 0) like an empty one;
 //   pass 2: every workgroup folds the partials itself (fixed order), writes its slice of probabilities and
 //           min-reduces a 64-bit key (~orderable(p) << 32 | index); the last workgroup to arrive (ticket counter,
 //           no spinning) publishes the token.  The arg-min over keys is order independent -> deterministic.
@@ -266,8 +266,13 @@ __global__ __launch_bounds__(kSmThreads) void softmax_partial_kernel(const T* lo
   __syncthreads();
   float sum = 0.f;
   int k = 0;
-  for (int i = lo + threadIdx.x; i < hi; i += kSmThreads, k++)
-    sum += sm_exp<T>((k < 4 ? x[k] : ElemTraits<T>::load(logits, (size_t)i)) - mx);
+  for (int i = lo + threadIdx.x; i < hi; i += kSmThreads, k++) {
+    // -inf (a banned token) adds exactly 0 whatever the slice's maximum: in a slice of nothing but -inf, -inf - mx would be NaN and
+    // poison the row, where torch.softmax (global maximum) gives the rest of the row its distribution.  Per element: a NaN beside
+    // the -inf (fmaxf skipped it, mx is still -inf) and a +inf (inf - inf) must still make the sum NaN.
+    const float v = k < 4 ? x[k] : ElemTraits<T>::load(logits, (size_t)i);
+    sum += v == -INFINITY ? 0.f : sm_exp<T>(v - mx);
+  }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, CC_WAVE);
   if (lane == 0) sm_f[wave] = sum;

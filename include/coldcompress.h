@@ -881,7 +881,12 @@ int cc_gemv_fused_mx4_multi(const uint8_t* W, const uint8_t* scales, const uint8
 
 /* Greedy sampling tail, ref: generation_utils.py:136-142: probs[V] = dtype(softmax_fp32(logits[V])),
  * *idx_out = first index of the largest rounded probability (torch.argmax semantics).  Two small launches; `workspace`
- * (cc_softmax_argmax_workspace_bytes) needs no initialisation. */
+ * (cc_softmax_argmax_workspace_bytes) needs no initialisation.
+ * Infinite and NaN logits follow torch.softmax / torch.argmax:
+ *   -inf   (a banned token, LogitPenalties' bias) has probability exactly 0 and takes no part in the sum, wherever it stands and
+ *          however many there are — whole slices of the vocabulary included; one finite logit among -inf gives exactly 1.0 there;
+ *   all -inf, any +inf, any NaN: every probability is NaN and *idx_out = 0 (NaN counts as the maximum, the first one wins), an
+ *          index inside the vocabulary. */
 size_t cc_softmax_argmax_workspace_bytes(void);
 int cc_softmax_argmax(const void* logits, int32_t V, int32_t dtype, void* probs, int32_t* idx_out, void* workspace,
                       size_t workspace_bytes, cc_stream_t stream);

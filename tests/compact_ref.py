@@ -304,21 +304,22 @@ def reference(c):
 
 
 # ------------------------------------------------------------------------------------------------ marshalling
-def run_oracle(o, c):
-    """-> (return code, {output name: CPU tensor}) of the oracle's twin on host copies of the case's tensors."""
-    op = OPS[c.op]
+def run_oracle(o, c, ops=None):
+    """-> (return code, {output name: CPU tensor}) of the oracle's twin on host copies of the case's tensors (ops: another module's
+    table of operations, tests/glue_ref.py)."""
+    op = (ops or OPS)[c.op]
     arrs = {n: (None if v is None else (to_np(v) if v.numel() else np.zeros(1, np.uint8))) for n, v in c.t.items()}
     rc = o.fns()[op.entry](*op.args(c, lambda n: o.ptr(arrs[n])))
     return rc, {n: (from_np(arrs[n], c.t[n].dtype) if c.t[n].numel() else c.t[n].clone()) for n in op.outputs if c.t.get(n) is not None}
 
 
-def run_device(c, device="cuda"):
+def run_device(c, device="cuda", ops=None):
     """-> (return code, {output name: CPU tensor}) of the device entry point.  Every tensor of the case sits inside a larger buffer
     pre-filled with the sentinel of its type (NaN, -7, 0xAB); after the call the margins on both sides of EVERY buffer must still hold
     it, and every tensor that is not an output must be bit for bit what was uploaded."""
     from cold_compress_amd import _abi
 
-    op = OPS[c.op]
+    op = (ops or OPS)[c.op]
     bufs = {}
     for n, v in c.t.items():
         if v is None:

@@ -119,6 +119,22 @@ def test_targets_outside_the_vocabulary_64_rows_and_null_outputs(dtype):
     assert torch.equal(alone.view(torch.int32), lp[:4].view(torch.int32))
 
 
+def test_a_whole_slice_of_inf():
+    """ids 128000..128255 at -inf (a banned block: the last of the 128 slices, ids 128016.., holds nothing else), in the second row
+    the first slice as well: logprob, lse and rank as float64 gives them; a banned target scores -inf."""
+    from cold_compress_amd.harness import glue
+
+    V, dtype = 128256, torch.bfloat16
+    rows = (torch.randn(2, V, generator=torch.Generator().manual_seed(12)) * 3).to(dtype)
+    rows[:, 128000:] = -float("inf")
+    rows[1, :1008] = -float("inf")
+    tg = [5, 127999]
+    lp, lse, rk = glue.logprob_rows(rows.to(DEV), torch.tensor(tg, dtype=torch.int32, device=DEV))
+    _check(list(rows), tg, ["banned block"] * 2, lp.cpu(), lse.cpu(), rk.cpu(), "whole slice of -inf")
+    lp, lse2, _ = glue.logprob_rows(rows.to(DEV), torch.tensor([128100, 3], dtype=torch.int32, device=DEV))
+    assert lp.tolist() == [-float("inf")] * 2 and torch.equal(lse2, lse) and bool(torch.isfinite(lse).all())
+
+
 def _bits(out):
     return [o.cpu().view(torch.int32) for o in out]
 

@@ -67,6 +67,25 @@ def test_ties_at_the_pivot_are_all_kept(dtype):
         assert (probs.float().cpu().numpy() != 0).tolist() == [True, True, False, False]
 
 
+def test_a_whole_slice_of_banned_tokens():
+    """ids 128000..128255 at -inf (LogitPenalties' ban of Llama-3's reserved tokens): the last of the 128 slices of the vocabulary
+    (ids 128016..) holds nothing else, the first is banned as well.  The sampler subtracts the global maximum, so the row keeps its
+    distribution: exact zeros on the banned ids, no NaN, the twin's probabilities and an accepted token."""
+    from cold_compress_amd.harness import glue
+
+    V = 128256
+    logits = (torch.randn(V, generator=torch.Generator().manual_seed(11)) * 3).to(torch.bfloat16)
+    logits[128000:] = -float("inf")
+    logits[:1008] = -float("inf")
+    dl = logits.to(DEV)
+    for top_k in (None, 50):
+        probs, idx = glue.sample_topk(dl, 0.8, top_k, 7, _pos(3))
+        tw = S.twin(logits, 0.8, top_k, 7, 3)
+        assert not bool(torch.isnan(probs).any()) and bool((probs[128000:] == 0).all()) and bool((probs[:1008] == 0).all())
+        S.check_probs(probs, tw, torch.bfloat16)
+        assert S.accepts(int(idx), tw) is not None and 1008 <= int(idx) < 128000
+
+
 def test_stateless_in_any_order_and_under_graph_replay():
     """64 positions at V = 32000: ascending, shuffled, and inside ONE captured graph replayed while the host only rewrites the device
     position — the same token per position, and the twin's."""
