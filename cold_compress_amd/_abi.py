@@ -76,6 +76,11 @@ SIGNATURES = {
     "cc_logits_penalize": (C.c_int, [_vp, _vp, _i32, _i32, C.c_int64, _i32, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _vp, _vp]),
     "cc_gemv_fused": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
     "cc_gemv_fused_multi": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "cc_w12_geometry": (C.c_int, [_i32, _i32, _i32, _vp]),
+    "cc_w12_meta_words": (_sz, []),
+    "cc_w12_pack": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "cc_gemv_fused_w12": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _i32,
+                                    _vp, _i32, _i32, _i32, _vp]),
     "cc_gemv_fused_w8": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
     "cc_gemv_fused_w4": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     "cc_gemv_fused_mx4": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
@@ -190,6 +195,8 @@ DEVICE_ONLY = {"cc_error_string", "cc_device_info", "cc_decode_step_single_launc
                "cc_decode_step_qkv_available", "cc_debug_qkv_trace",
                "cc_kv_requant_batch",  # (its oracle is the per-cache twin of cc_kv_requant_pair)
                "cc_gemv_fused_multi",  # cc_gemv_fused for up to 4 input vectors: its checker is cc_gemv_fused itself, row by row, bit for bit
+               # the 12-bit packed copy of dense bf16 weights: its checker is cc_gemv_fused itself, bit for bit, and a numpy decoder of the format
+               "cc_w12_geometry", "cc_w12_meta_words", "cc_w12_pack", "cc_gemv_fused_w12",
                "cc_gemv_fused_w8",  # int8 weight-only GEMV: its checker is the fp32 torch composition of the reference's formula
                "cc_gemv_fused_w4",  # int4 group-wise weight-only GEMV: likewise
                "cc_gemv_fused_mx4",  # MXFP4 weight-only GEMV: likewise (and bit-exact known-answer cases)

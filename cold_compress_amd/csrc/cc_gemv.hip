@@ -21,40 +21,17 @@
 
 namespace {
 
-struct GemvArgs {
-  const void* W;
-  const void* W3;      // second matrix of the SwiGLU pair, or null
-  const void* x;       // [K]
-  const void* delta;   // [K] pending residual, or null
-  const void* norm_w;  // [K] RMSNorm weight, or null (no norm prologue)
-  const void* bias;    // [N] or null
-  const void* freqs;   // [head_dim/2, 2] (cos, sin) of this position, or null
-  void* h_out;         // [K] x + delta, or null
-  void* y;             // [N]
-  float eps;
-  int N, K, rope_rows, head_dim;
-};
-
 constexpr int kGvThreads = 256;
 constexpr int kGvWaves = kGvThreads / 64;
+static_assert(kGvThreads == kGvCoreThreads, "gemv_body's workgroup");
 
 template <typename T, bool SWIGLU, int RB, int CU, int XS>
 __global__ __launch_bounds__(kGvThreads) void gemv_kernel(GemvArgs a) {
+  // (the body, shared with the 12-bit packed form: cc_gemv_core.h)
   constexpr int VEC = 16 / (int)sizeof(T);
-  __shared__ float sm_red[kGvWaves];
-  __shared__ float sm_part[kGvWaves][2][RB];
-  const int K = a.K, N = a.N;
-  const int nch = K / VEC;
-  const T* xg = reinterpret_cast<const T*>(a.x);
+  const int N = a.N, nch = a.K / VEC;
+  const int nstep = ((nch + 63) / 64 + kGvWaves - 1) / kGvWaves;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-
-  // ---- Work decomposition: a WORKGROUP owns RB consecutive rows at a time; its four waves split K (wave w takes
-  //      the 1 KiB segments w, w+4, w+8, ... of every row), CU segments per row in flight per wave, and the four
-  //      partial sums meet in LDS.  For the decode shapes this puts a whole matrix in flight in one phase
-  //      (wo: 2 rows x 2 segments per wave; w2: 4 rows x 4 of 7 segments) instead of looping inside a wave.
-  //      The FIRST tile's weight loads are issued before the input vector is touched: W does not depend on x.
-  const int nseg = (nch + 63) / 64;                      // 1 KiB segments per row
-  const int nstep = (nseg + kGvWaves - 1) / kGvWaves;    // segments per wave (<= XS, checked by the launcher)
   const uint4* Wv = reinterpret_cast<const uint4*>(a.W);
   const uint4* W3v = reinterpret_cast<const uint4*>(a.W3);
   uint4 w[RB][CU], w3[RB][CU];
@@ -74,142 +51,10 @@ __global__ __launch_bounds__(kGvThreads) void gemv_kernel(GemvArgs a) {
       }
     }
   };
-  const int row_first = blockIdx.x * RB;
-  if (row_first < N) issue(row_first, 0);
-
-  // ---- the input vector: every lane keeps exactly the 16-byte chunks it will multiply (no LDS staging).  With a
-  //      norm prologue, x / delta / norm weight of those chunks are requested together (one memory round trip), the
-  //      four waves exchange their partial sums of squares through LDS (one barrier), and the normalised chunks
-  //      replace h in the same registers.
-  uint4 xr[XS];
-  if (a.norm_w != nullptr) {
-    const T* dg = reinterpret_cast<const T*>(a.delta);
-    const T* wg = reinterpret_cast<const T*>(a.norm_w);
-    Vec16<T> xv[XS], dv[XS], nv[XS];
-#pragma unroll
-    for (int j = 0; j < XS; j++) {
-      const int c = (j * kGvWaves + wave) * 64 + lane;
-      if (j < nstep && c < nch) {
-        xv[j].load(xg + (size_t)c * VEC);
-        if (dg != nullptr) dv[j].load(dg + (size_t)c * VEC);
-        nv[j].load(wg + (size_t)c * VEC);
-      }
-    }
-    float ss = 0.f;
-#pragma unroll
-    for (int j = 0; j < XS; j++) {
-      const int c = (j * kGvWaves + wave) * 64 + lane;
-      xr[j] = make_uint4(0, 0, 0, 0);
-      if (j < nstep && c < nch) {
-        float h[VEC];
-        xv[j].unpack(h);
-        if (dg != nullptr) {
-          float d[VEC];
-          dv[j].unpack(d);
-#pragma unroll
-          for (int e = 0; e < VEC; e++) h[e] = ElemTraits<T>::rnd(__fadd_rn(h[e], d[e]));  // model-dtype residual add
-        }
-#pragma unroll
-        for (int e = 0; e < VEC; e++) ss = fmaf(h[e], h[e], ss);
-        xr[j] = pack16<T>(h);  // h is already rounded to T: packing is exact
-        if (a.h_out != nullptr && blockIdx.x == 0) reinterpret_cast<uint4*>(a.h_out)[c] = xr[j];
-      }
-    }
-    ss = gv_wave_sum(ss);
-    if (lane == 0) sm_red[wave] = ss;
-    __syncthreads();
-    const float tot = (sm_red[0] + sm_red[1]) + (sm_red[2] + sm_red[3]);
-    const float rs = rsqrtf(tot / (float)K + a.eps);  // ref: model.py:452-457 (fp32 inside)
-#pragma unroll
-    for (int j = 0; j < XS; j++) {
-      const int c = (j * kGvWaves + wave) * 64 + lane;
-      if (j < nstep && c < nch) {
-        Vec16<T> hv;
-        float h[VEC], wf[VEC], o[VEC];
-        hv.raw = xr[j];
-        hv.unpack(h);
-        nv[j].unpack(wf);
-#pragma unroll
-        for (int e = 0; e < VEC; e++) o[e] = ElemTraits<T>::rnd(__fmul_rn(ElemTraits<T>::rnd(cc_opaque_f32(__fmul_rn(h[e], rs))), wf[e]));  // (opaque: see the epilogue)
-        xr[j] = pack16<T>(o);
-      }
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < XS; j++) {
-      const int c = (j * kGvWaves + wave) * 64 + lane;
-      xr[j] = (j < nstep && c < nch) ? reinterpret_cast<const uint4*>(xg)[c] : make_uint4(0, 0, 0, 0);
-    }
-  }
-
-  T* yo = reinterpret_cast<T*>(a.y);
-  bool first = true;
-  for (int r0 = row_first; r0 < N; r0 += gridDim.x * RB) {
-    float acc[RB], acc3[RB];
-#pragma unroll
-    for (int r = 0; r < RB; r++) acc[r] = acc3[r] = 0.f;
-#pragma unroll
-    for (int s0 = 0; s0 < XS; s0 += CU) {
-      if (s0 < nstep) {
-        if (!first) issue(r0, s0);
-        first = false;
-#pragma unroll
-        for (int u = 0; u < CU; u++) {
-          const uint4 xv = xr[s0 + u < XS ? s0 + u : XS - 1];  // beyond nstep the weights are zero-filled
-#pragma unroll
-          for (int r = 0; r < RB; r++) {
-            acc[r] = Dot16<T>::run(w[r][u], xv, acc[r]);
-            if (SWIGLU) acc3[r] = Dot16<T>::run(w3[r][u], xv, acc3[r]);
-          }
-        }
-      }
-    }
-    // ---- the four K-quarters of every row meet in LDS (fixed order: deterministic)
-#pragma unroll
-    for (int r = 0; r < RB; r++) {
-      const float s = gv_wave_sum(acc[r]);
-      float s3 = 0.f;
-      if (SWIGLU) s3 = gv_wave_sum(acc3[r]);
-      if (lane == 0) {
-        sm_part[wave][0][r] = s;
-        if (SWIGLU) sm_part[wave][1][r] = s3;
-      }
-    }
-    __syncthreads();
-    if (wave == 0) {
-      float out = 0.f;  // lane r finishes row r0 + r
-      const int r = lane < RB ? lane : 0;
-      float s = (sm_part[0][0][r] + sm_part[1][0][r]) + (sm_part[2][0][r] + sm_part[3][0][r]);
-      const int row = r0 + r;
-      if (a.bias != nullptr && row < N) s += ElemTraits<T>::load(reinterpret_cast<const T*>(a.bias), (size_t)row);
-      // (cc_opaque_f32: the fp32 value first, THEN its rounding — otherwise the f16 instantiations may fuse the bias add / the
-      //  rotation with the conversion into one v_fma_mix rounding, differently in different kernels: the QKV form of the layer step,
-      //  cc_attn_decode_qkv.hip, runs these operations too and must give the same bits)
-      s = ElemTraits<T>::rnd(cc_opaque_f32(s));  // the Linear's output in the model dtype
-      if (SWIGLU) {
-        const float s3 = ElemTraits<T>::rnd((sm_part[0][1][r] + sm_part[1][1][r]) + (sm_part[2][1][r] + sm_part[3][1][r]));
-        const float sl = ElemTraits<T>::rnd(__fdiv_rn(s, 1.0f + expf(-s)));  // F.silu -> dtype (model.py:443)
-        s = __fmul_rn(sl, s3);
-      }
-      out = s;
-      if (a.freqs != nullptr) {  // RoPE on the (even, odd) row pairs of the q / k heads (model.py:507-519)
-        const float other = gv_dpp<0xB1>(out);  // the pair partner lives in lane ^ 1 (r0 is even)
-        if (row < a.rope_rows) {
-          const int pr = (row % a.head_dim) >> 1;
-          const float c = ElemTraits<T>::load(reinterpret_cast<const T*>(a.freqs), (size_t)pr * 2);
-          const float sn = ElemTraits<T>::load(reinterpret_cast<const T*>(a.freqs), (size_t)pr * 2 + 1);
-          out = (row & 1) ? __fadd_rn(__fmul_rn(out, c), __fmul_rn(other, sn)) : __fsub_rn(__fmul_rn(out, c), __fmul_rn(other, sn));
-        }
-      }
-      if (lane < RB && row < N) ElemTraits<T>::store(yo, (size_t)row, cc_opaque_f32(out));
-    }
-    __syncthreads();  // sm_part is reused by the next row group
-  }
+  auto get = [&](int r, int u) { return w[r][u]; };
+  auto get3 = [&](int r, int u) { return w3[r][u]; };
+  gemv_body<T, SWIGLU, RB, CU, XS>(a, issue, get, get3);
 }
-
-struct GvCfg {
-  int rb, cu, cap;
-};
 
 static GvCfg pick_cfg(const GemvArgs& a, int vec) {
   static int env_rb = -1, env_cu = -1, env_cap = 2048;

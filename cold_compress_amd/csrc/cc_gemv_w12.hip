@@ -1,0 +1,343 @@
+// cc_gemv_w12.hip — cc_gemv.hip's single-vector bf16 GEMV over a LOSSLESS 12-bit packed copy of the weights ("w12"): the same
+// five decode-layer forms, the same bits, three quarters of the HBM bytes.
+//
+// A bf16 weight is 1 sign, 8 exponent and 7 mantissa bits, and a weight tensor uses few exponents.  w12 keeps sign + mantissa as
+// one byte and the exponent as a 4-bit index into a window of 16 consecutive exponents that starts at a per-tensor `base`.
+//
+// Codes: the 16-byte chunk of 8 weights that gemv_kernel gives a lane becomes 12 bytes (three dwords), at the same chunk index:
+//   dword 0, 1 : byte i = (sign << 7) | mantissa of weight i (i = 0 .. 7)
+//   dword 2    : exponent indices; weight 2 j at bits [4 j, 4 j + 4), weight 2 j + 1 at bits [16 + 4 j, 16 + 4 j + 4)
+// A wave's 64 lanes read 768 contiguous bytes per (row, segment) with one 12-byte load each.  A pair of weights decodes to its
+// packed bf16 dword in five VALU operations as written (v_perm doubles the two bytes, v_and_or keeps sign + mantissa and places the
+// base, shift + and + shifted add place the two indices; the compiler emits six).  The decoded uint4 is exactly the dense chunk and
+// feeds the unchanged Dot16 chain of gemv_body (cc_gemv_core.h).  Where it pays and where it does not: DESIGN.md §2.17.
+//
+// Escapes: a weight whose exponent lies outside the window (±0, subnormals, inf / NaN and outliers included) keeps an arbitrary
+// code and is put right after the decode from a patch record.  A record is 32 bytes, one per (row group, issue phase, wave) — the
+// RB x CU chunks a wave requests at once — at a wave-uniform address requested together with the tile:
+//   dword 0      : count (0 .. 7), or 0xFFFFFFFF when the tile has more than 7 escapes
+//   dword 1 .. 7 : entries  (tile element r * CU + u) << 25 | lane << 19 | weight in chunk << 16 | raw bf16 bits
+// The kernel keeps a record in lanes 0 .. 7 of one register and reads it with v_readlane; patching sits behind a wave-uniform
+// `count != 0` branch.  An overflowing record makes its wave read the tile again from the dense
+// tensor, which stays resident (prefill and the block kernels use it).  Records follow the launch geometry, so a packed tensor is
+// tied to the (RB, CU) it was packed for (cc_w12_geometry).  Built and tested: K <= 16384; measured faster than the dense kernel and
+// therefore on by default in the harness: the pair and the LM-head classes at K <= 4096 only (cc_w12_geometry's fifth word).
+//
+// Packer (cc_w12_pack, once per tensor): exponent histogram -> the window of 16 that covers most weights -> codes and records.
+#include <cstdio>
+#include <cstdlib>
+
+#include "cc_common.h"
+#include "cc_gemv_core.h"
+
+namespace {
+
+constexpr int kW12Threads = kGvCoreThreads;
+constexpr int kW12Waves = kGvCoreWaves;
+constexpr uint32_t kW12Overflow = 0xFFFFFFFFu;
+constexpr int kW12Slots = 7;
+
+struct GemvW12Args {
+  GemvArgs g;           // g.W / g.W3: the dense tensors (read only by waves whose record overflowed)
+  const uint32_t* P;    // codes [N, K / 8, 3]
+  const uint32_t* P3;
+  const uint32_t* R;    // records [row groups, phases, 4 waves][8]
+  const uint32_t* R3;
+  uint32_t bw, bw3;     // base << 7 | base << 23
+};
+
+typedef unsigned int u32x3_t __attribute__((ext_vector_type(3)));
+
+__device__ __forceinline__ uint32_t w12_pair(uint32_t sm, uint32_t sel, uint32_t ex, int j, uint32_t bw) {
+  const uint32_t t = (__builtin_amdgcn_perm(sm, sm, sel) & 0x807f807fu) | bw;
+  return (((ex >> (4 * j)) & 0x000f000fu) << 7) + t;
+}
+__device__ __forceinline__ uint4 w12_decode(u32x3_t q, uint32_t bw) {
+  return make_uint4(w12_pair(q.x, 0x01010000u, q.z, 0, bw), w12_pair(q.x, 0x03030202u, q.z, 1, bw),
+                    w12_pair(q.y, 0x01010000u, q.z, 2, bw), w12_pair(q.y, 0x03030202u, q.z, 3, bw));
+}
+
+// the record of a tile lives in lanes 0 .. 7 of one register (word i in lane i); entries are read out with v_readlane
+__device__ __forceinline__ uint4 w12_patch(uint4 d, uint32_t rec, int cnt, int t, int lane) {
+  for (int e = 0; e < cnt; e++) {  // wave-uniform trip count (an overflowing record reads as -1: the tile was read again)
+    const uint32_t en = __builtin_amdgcn_readlane(rec, 1 + e);
+    if ((int)(en >> 25) == t) {
+      const bool hit = lane == (int)((en >> 19) & 63u);
+      const int k = (en >> 16) & 7;
+      const uint32_t sh = (k & 1) * 16;
+      const uint32_t keep = ~(0xffffu << sh), v = (en & 0xffffu) << sh;
+      const int word = k >> 1;
+      d.x = (hit && word == 0) ? (d.x & keep) | v : d.x;
+      d.y = (hit && word == 1) ? (d.y & keep) | v : d.y;
+      d.z = (hit && word == 2) ? (d.z & keep) | v : d.z;
+      d.w = (hit && word == 3) ? (d.w & keep) | v : d.w;
+    }
+  }
+  return d;
+}
+
+template <bool SWIGLU, int RB, int CU, int XS>
+__global__ __launch_bounds__(kW12Threads) void gemv_w12_kernel(GemvW12Args a) {
+  const int N = a.g.N, nch = a.g.K / 8;
+  const int nstep = ((nch + 63) / 64 + kW12Waves - 1) / kW12Waves;
+  const int nph = (nstep + CU - 1) / CU;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint4* Wv = reinterpret_cast<const uint4*>(a.g.W);
+  const uint4* W3v = reinterpret_cast<const uint4*>(a.g.W3);
+  u32x3_t q[RB][CU], q3[RB][CU];
+  uint32_t rec = 0, rec3 = 0;  // this tile's records: word i in lane i < 8
+  int tr0 = 0, ts0 = 0;    // this tile's first row and column step
+  auto issue = [&](int r0, int s0) {
+    tr0 = r0;
+    ts0 = s0;
+#pragma unroll
+    for (int u = 0; u < CU; u++) {
+      const int c = ((s0 + u) * kW12Waves + wave) * 64 + lane;
+      const bool cin = (s0 + u < nstep) && c < nch;
+#pragma unroll
+      for (int r = 0; r < RB; r++) {
+        const bool in = cin && (r0 + r < N);
+        const size_t off = ((size_t)(r0 + r) * nch + c) * 3;
+        const u32x3_t z = {0u, 0u, 0u};
+        q[r][u] = in ? __builtin_nontemporal_load(reinterpret_cast<const u32x3_t*>(a.P + off)) : z;
+        if (SWIGLU) q3[r][u] = in ? __builtin_nontemporal_load(reinterpret_cast<const u32x3_t*>(a.P3 + off)) : z;
+      }
+    }
+    const size_t at = (((size_t)(r0 / RB) * nph + s0 / CU) * kW12Waves + wave) * 8 + (lane & 7);
+    rec = a.R[at];
+    if (SWIGLU) rec3 = a.R3[at];
+  };
+  auto chunk = [&](u32x3_t code, uint32_t bw, uint32_t rc, const uint4* dense, int r, int u) {
+    const int c = ((ts0 + u) * kW12Waves + wave) * 64 + lane;
+    const bool in = (ts0 + u < nstep) && c < nch && (tr0 + r < N);
+    uint4 d = w12_decode(code, in ? bw : 0u);  // (outside the matrix: zero codes and no base decode to zeros, the dense kernel's fill)
+    const uint32_t cnt = __builtin_amdgcn_readlane(rc, 0);
+    if (cnt != 0u) {  // wave-uniform
+      if (cnt == kW12Overflow) {
+        d = in ? nt_load(dense + (size_t)(tr0 + r) * nch + c) : make_uint4(0, 0, 0, 0);
+      } else {
+        d = w12_patch(d, rc, (int)cnt, r * CU + u, lane);
+      }
+    }
+    return d;
+  };
+  auto get = [&](int r, int u) { return chunk(q[r][u], a.bw, rec, Wv, r, u); };
+  auto get3 = [&](int r, int u) { return chunk(q3[r][u], a.bw3, rec3, W3v, r, u); };
+  gemv_body<bf16_t, SWIGLU, RB, CU, XS>(a.g, issue, get, get3);
+}
+
+// ---- launch geometry.  The starting point is cc_gemv.hip's pick_cfg (the same loads in flight per lane, each a quarter shorter).
+static GvCfg pick_w12_cfg(int N, int K, bool swiglu) {
+  static int env_rb = -1, env_cu = -1, env_cap = 2048;
+  if (env_rb < 0) {  // tuning hook: CC_GEMV_W12_CFG="RB,CU[,max workgroups]"
+    env_rb = env_cu = 0;
+    if (const char* e = getenv("CC_GEMV_W12_CFG")) sscanf(e, "%d,%d,%d", &env_rb, &env_cu, &env_cap);
+  }
+  if (env_rb > 0 && env_cu > 0) return {env_rb, env_cu, env_cap};
+  const int nseg = (K / 8 + 63) / 64, nstep = (nseg + kW12Waves - 1) / kW12Waves;
+  GvCfg c;
+  c.cap = 2048;
+  if (nstep <= 2 && !swiglu) {
+    if (N >= 32768) {
+      c.rb = 2; c.cu = 2;
+    } else {
+      c.rb = 4; c.cu = 2;
+    }
+    c.cap = 1024;
+  } else if (nstep <= 2) {
+    c.rb = 2; c.cu = 2;
+  } else if (swiglu) {
+    c.rb = 2; c.cu = 4;
+  } else {
+    c.rb = 4; c.cu = 4;
+    c.cap = 512;
+  }
+  return c;
+}
+
+static int w12_xs(int K) {
+  const int nseg = (K / 8 + 63) / 64, nstep = (nseg + kW12Waves - 1) / kW12Waves;
+  return nstep <= 2 ? 2 : nstep <= 8 ? 8 : 0;  // (rows beyond 8 steps per wave, K > 16384, are not served: CC_ERR_UNSUPPORTED)
+}
+
+static bool w12_cfg_built(bool swiglu, int xs, int rb, int cu) {
+  const int key = (swiglu ? 100000 : 0) + xs * 1000 + rb * 10 + cu;
+  switch (key) {
+    case 2022: case 2042: case 8044: case 102022: case 108024: return true;
+    default: return false;
+  }
+}
+
+template <bool SWIGLU, int RB, int CU, int XS>
+static void launch_w12_cfg(const GemvW12Args& a, hipStream_t st, int cap) {
+  int blocks = (a.g.N + RB - 1) / RB;
+  if (blocks > cap) blocks = cap;
+  hipLaunchKernelGGL((gemv_w12_kernel<SWIGLU, RB, CU, XS>), dim3(blocks), dim3(kW12Threads), 0, st, a);
+}
+
+// ---- packer
+constexpr int kW12MetaBase = 0, kW12MetaRecords = 1, kW12MetaOverflow = 2, kW12MetaEscapes = 3, kW12MetaHist = 8;
+
+__global__ __launch_bounds__(256) void w12_hist_kernel(const uint16_t* W, size_t n, int32_t* meta) {
+  __shared__ int h[256];
+  h[threadIdx.x] = 0;
+  __syncthreads();
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) atomicAdd(&h[(W[i] >> 7) & 0xff], 1);
+  __syncthreads();
+  // (int32 bins: cc_w12_pack rejects tensors of 2^31 weights or more)
+  if (h[threadIdx.x]) atomicAdd(&meta[kW12MetaHist + threadIdx.x], h[threadIdx.x]);
+}
+
+__global__ void w12_base_kernel(int32_t* meta, int nrec) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  long long best = -1;
+  int base = 0;
+  for (int b = 0; b + 15 <= 255; b++) {  // base + 15 <= 255: the decode's index add never carries into the sign
+    long long s = 0;
+    for (int i = 0; i < 16; i++) s += meta[kW12MetaHist + b + i];
+    if (s > best) {
+      best = s;
+      base = b;
+    }
+  }
+  meta[kW12MetaBase] = base;
+  meta[kW12MetaRecords] = nrec;
+}
+
+// one wave per record: the RB x CU chunks per lane that gemv_w12_kernel's wave requests together
+__global__ __launch_bounds__(64) void w12_pack_kernel(const uint4* W, int N, int K, int RB, int CU, uint32_t* P, uint32_t* R, int32_t* meta) {
+  __shared__ uint32_t rec[8];
+  const int lane = threadIdx.x;
+  const int nch = K / 8;
+  const int nstep = ((nch + 63) / 64 + kW12Waves - 1) / kW12Waves;
+  const int nph = (nstep + CU - 1) / CU;
+  const int wave = blockIdx.x % kW12Waves;
+  const int ph = (blockIdx.x / kW12Waves) % nph;
+  const int rg = blockIdx.x / (kW12Waves * nph);
+  const int base = meta[kW12MetaBase];
+  if (lane < 8) rec[lane] = 0;
+  __syncthreads();
+  int count = 0;
+  for (int t = 0; t < RB * CU; t++) {
+    const int r = t / CU, u = t % CU;
+    const int row = rg * RB + r;
+    const int c = ((ph * CU + u) * kW12Waves + wave) * 64 + lane;
+    const bool in = row < N && (ph * CU + u) < nstep && c < nch;
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (in) v = W[(size_t)row * nch + c];
+    const uint32_t wd[4] = {v.x, v.y, v.z, v.w};
+    uint32_t sm[2] = {0, 0}, ex = 0;
+    for (int k = 0; k < 8; k++) {
+      const uint32_t bits = (wd[k >> 1] >> ((k & 1) * 16)) & 0xffffu;
+      const int idx = (int)((bits >> 7) & 0xffu) - base;
+      const bool esc = in && (idx < 0 || idx > 15);
+      if (!esc) {
+        sm[k >> 2] |= (((bits >> 8) & 0x80u) | (bits & 0x7fu)) << ((k & 3) * 8);
+        ex |= (uint32_t)(in ? idx : 0) << ((k & 1) * 16 + (k >> 1) * 4);
+      }
+      const unsigned long long m = __ballot(esc);
+      if (esc) {
+        const int slot = count + __popcll(m & ((1ull << lane) - 1ull));
+        if (slot < kW12Slots) rec[1 + slot] = ((uint32_t)t << 25) | ((uint32_t)lane << 19) | ((uint32_t)k << 16) | bits;
+      }
+      count += __popcll(m);
+    }
+    if (in) {
+      uint32_t* p = P + ((size_t)row * nch + c) * 3;
+      p[0] = sm[0];
+      p[1] = sm[1];
+      p[2] = ex;
+    }
+  }
+  __syncthreads();
+  if (lane == 0) {
+    rec[0] = count > kW12Slots ? kW12Overflow : (uint32_t)count;
+    if (count > kW12Slots) atomicAdd(&meta[kW12MetaOverflow], 1);
+    if (count) atomicAdd(&meta[kW12MetaEscapes], count);
+  }
+  __syncthreads();
+  if (lane < 8) R[(size_t)blockIdx.x * 8 + lane] = (count > kW12Slots && lane > 0) ? 0u : rec[lane];
+}
+
+}  // namespace
+
+extern "C" int cc_w12_geometry(int32_t N, int32_t K, int32_t swiglu, int32_t* out) {
+  if (!out || N <= 0 || K <= 0) return CC_ERR_BAD_ARG;
+  if (K % 8 || (size_t)K * 2 > 64 * 1024) return CC_ERR_UNSUPPORTED;
+  const GvCfg c = pick_w12_cfg(N, K, swiglu != 0);
+  const int xs = w12_xs(K);
+  if (xs == 0 || c.cu > xs || c.cap <= 0 || !w12_cfg_built(swiglu != 0, xs, c.rb, c.cu)) return CC_ERR_UNSUPPORTED;
+  out[0] = c.rb;
+  out[1] = c.cu;
+  out[2] = xs;
+  out[3] = c.cap;
+  // the launch classes that MEASURED faster than the dense kernel (the SwiGLU pair and the LM head at K = 4096,
+  // <true, 2, 2, 2> and <false, 2, 2, 2> with 1024 workgroups); every other class is served but stays dense by default
+  const int nstep = ((K / 8 + 63) / 64 + kW12Waves - 1) / kW12Waves;
+  out[4] = (nstep <= 2 && (swiglu != 0 || N >= 32768)) ? 1 : 0;
+  return CC_OK;
+}
+
+extern "C" size_t cc_w12_meta_words(void) { return kW12MetaHist + 256; }
+
+extern "C" int cc_w12_pack(const void* W, int32_t N, int32_t K, int32_t rb, int32_t cu, void* codes, void* records, void* meta,
+                           cc_stream_t stream) {
+  CC_ENTRY();
+  if (!W || !codes || !records || !meta || N <= 0 || K <= 0 || rb <= 0 || cu <= 0 || rb * cu > 64) return CC_ERR_BAD_ARG;
+  if (K % 8 || (size_t)K * 2 > 64 * 1024) return CC_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  const int nch = K / 8;
+  const int nstep = ((nch + 63) / 64 + kW12Waves - 1) / kW12Waves;
+  const int nph = (nstep + cu - 1) / cu;
+  const long long nrec = (long long)((N + rb - 1) / rb) * nph * kW12Waves;
+  if (nrec > 0x7fffffffLL || (long long)N * K >= 0x80000000LL) return CC_ERR_UNSUPPORTED;  // (the histogram counts in int32)
+  int32_t* m = reinterpret_cast<int32_t*>(meta);
+  if (hipMemsetAsync(m, 0, (kW12MetaHist + 256) * sizeof(int32_t), st) != hipSuccess) return CC_ERR_HIP;
+  const size_t n = (size_t)N * K;
+  int hb = (int)((n + 256 * 64 - 1) / (256 * 64));
+  if (hb > 2048) hb = 2048;
+  hipLaunchKernelGGL(w12_hist_kernel, dim3(hb), dim3(256), 0, st, reinterpret_cast<const uint16_t*>(W), n, m);
+  hipLaunchKernelGGL(w12_base_kernel, dim3(1), dim3(64), 0, st, m, (int)nrec);
+  hipLaunchKernelGGL(w12_pack_kernel, dim3((unsigned)nrec), dim3(64), 0, st, reinterpret_cast<const uint4*>(W), N, K, rb, cu,
+                     reinterpret_cast<uint32_t*>(codes), reinterpret_cast<uint32_t*>(records), m);
+  CC_LAUNCH_CHECK();
+  return CC_OK;
+}
+
+extern "C" int cc_gemv_fused_w12(const void* codes, const void* records, int32_t base, const void* codes3, const void* records3,
+                                 int32_t base3, int32_t rb, int32_t cu, const void* W, const void* W3, const void* x, const void* delta,
+                                 const void* norm_w, float eps, void* h_out, const void* bias, const void* freqs, int32_t rope_rows,
+                                 int32_t head_dim, void* y, int32_t N, int32_t K, int32_t dtype, cc_stream_t stream) {
+  CC_ENTRY();
+  if (!codes || !records || !W || !x || !y || N <= 0 || K <= 0 || !cc_dt_ok(dtype)) return CC_ERR_BAD_ARG;
+  if ((W3 != nullptr) != (codes3 != nullptr) || (W3 != nullptr) != (records3 != nullptr)) return CC_ERR_BAD_ARG;
+  if (base < 0 || base > 240 || (W3 && (base3 < 0 || base3 > 240))) return CC_ERR_BAD_ARG;
+  if ((delta || h_out) && !norm_w) return CC_ERR_BAD_ARG;
+  if (freqs && (W3 || rope_rows < 0 || rope_rows > N || head_dim <= 0 || (head_dim & 1) || (rope_rows % head_dim))) return CC_ERR_BAD_ARG;
+  if (W3 && bias) return CC_ERR_BAD_ARG;
+  if (dtype != CC_DT_BF16) return CC_ERR_UNSUPPORTED;
+  int32_t geo[5];
+  const int rc = cc_w12_geometry(N, K, W3 != nullptr, geo);
+  if (rc != CC_OK) return rc;
+  if (geo[0] != rb || geo[1] != cu) return CC_ERR_BAD_ARG;  // the records were laid out for another launch geometry
+  GemvW12Args a;
+  a.g = GemvArgs{W, W3, x, delta, norm_w, bias, freqs, h_out, y, eps, N, K, freqs ? rope_rows : 0, freqs ? head_dim : 2};
+  a.P = reinterpret_cast<const uint32_t*>(codes);
+  a.P3 = reinterpret_cast<const uint32_t*>(codes3);
+  a.R = reinterpret_cast<const uint32_t*>(records);
+  a.R3 = reinterpret_cast<const uint32_t*>(records3);
+  a.bw = ((uint32_t)base << 7) | ((uint32_t)base << 23);
+  a.bw3 = ((uint32_t)base3 << 7) | ((uint32_t)base3 << 23);
+  hipStream_t st = (hipStream_t)stream;
+  const int key = (W3 ? 100000 : 0) + geo[2] * 1000 + rb * 10 + cu;
+  switch (key) {  // (w12_cfg_built's list)
+    case 2022: launch_w12_cfg<false, 2, 2, 2>(a, st, geo[3]); break;
+    case 2042: launch_w12_cfg<false, 4, 2, 2>(a, st, geo[3]); break;
+    case 8044: launch_w12_cfg<false, 4, 4, 8>(a, st, geo[3]); break;
+    case 102022: launch_w12_cfg<true, 2, 2, 2>(a, st, geo[3]); break;
+    case 108024: launch_w12_cfg<true, 2, 4, 8>(a, st, geo[3]); break;
+    default: return CC_ERR_UNSUPPORTED;
+  }
+  CC_LAUNCH_CHECK();
+  return CC_OK;
+}

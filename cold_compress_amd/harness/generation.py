@@ -351,6 +351,7 @@ class GraphedDecoder:
                 self.out_logprob, self.out_rank = self.out_probs
             self.graph = graph
             self._epoch = self._cache_epoch()
+            self._w12_epoch = self._weights_epoch()
         finally:  # also when capture is refused (e.g. a collective that cannot be captured): the caller falls back to
             self.pos.copy_(pos0)  # eager launches and must find the state it handed in
             if pen is not None:
@@ -367,6 +368,14 @@ class GraphedDecoder:
     def _cache_epoch(self):
         """Moves when a cache changed something the captured steps carry by value (KVCacheRandom's per-generation seed)."""
         return sum(int(getattr(l.attention.kv_cache, "_graph_epoch", 0)) for l in self.model.layers)
+
+    def _weights_epoch(self):
+        """Moves when a packed copy that the captured step may read is gone or out of date (glue.w12_epoch: a dense weight changed in
+        place, or copies were dropped): the copies are rebuilt by an eager step only — so capture again (the warm-up steps run
+        eagerly)."""
+        from . import glue
+
+        return glue.w12_epoch() if glue.w12_enabled() else None
 
     def __call__(self, model, x, input_pos, next_token=None, **kw):
         sampling = tuple(kw.get(k, d) for k, d in zip(self._SETTINGS, self.sampling))
@@ -385,6 +394,8 @@ class GraphedDecoder:
                     self.pos.copy_(input_pos)
                     c.prepare_decode(self.pos)
             if self._cache_epoch() != self._epoch:  # (something the captured steps carry BY VALUE moved: capture again)
+                self.graph = None
+            elif self._weights_epoch() != self._w12_epoch:
                 self.graph = None
         if self.graph is None:
             self.tok.copy_(x)

@@ -8,6 +8,9 @@ launches per layer or to torch.compile.  On device tensors they call the C ABI (
 CPU model-wiring test brings its own eager twins: tests/host_glue.py).
 """
 import ctypes as C
+import os
+import warnings
+import weakref
 
 import torch
 
@@ -85,8 +88,129 @@ def gemv_supported(*weights):
     return all(ok(w) for w in weights)
 
 
+class W12Packed:
+    """The lossless 12-bit packed copy of one dense bf16 weight (cc_w12_pack; format: include/coldcompress.h).  `codes` uint32
+    [N, K / 8, 3], `records` uint32 [records, 8], `base` the first exponent of the window, (`rb`, `cu`, `xs`, `cap`) the launch
+    geometry it was packed for (the records follow `rb` and `cu`); `n_overflow` records hold more than 7 escapes (their tiles are
+    read from the dense tensor), `n_escapes` weights lie outside the window."""
+    __slots__ = ("codes", "records", "base", "rb", "cu", "xs", "cap", "n_records", "n_overflow", "n_escapes")
+
+
+W12_MAX_OVERFLOW = 0.01  # a tensor with more overflowing records than this share stays on cc_gemv_fused
+_W12_MARGIN = 1 << 30  # free device memory kept beyond a packed copy
+# (data_ptr, _version, shape, device, swiglu) -> (W12Packed, or None: refused, unsupported or no room, and not tried again for this
+# version of the weight; weak reference to the weight: while it lives its storage does, so the address cannot have been given to
+# another tensor)
+_w12_cache = {}
+_w12_geo = {}  # (N, K, swiglu) -> cc_w12_geometry's answer
+_w12_drops = 0  # moves whenever a packed copy is dropped: a captured graph may still hold its address (w12_epoch)
+_w12_warned = False
+
+
+def w12_enabled():
+    return os.environ.get("CC_W12", "1") != "0"
+
+
+def w12_geometry(N, K, swiglu=False):
+    """(RB, CU, input chunks per lane, most workgroups, faster) of the packed GEMV's launch for this shape and form, or None:
+    unsupported.  `faster`: 1 when that launch class measured faster than the dense kernel, else 0."""
+    key = (int(N), int(K), bool(swiglu))
+    if key not in _w12_geo:
+        out = (C.c_int32 * 5)()
+        ok = _abi.lib()["cc_w12_geometry"](key[0], key[1], int(key[2]), out) == _abi.CC_OK
+        _w12_geo[key] = tuple(out) if ok else None
+    return _w12_geo[key]
+
+
+def w12_nbytes(N, K, rb, cu):
+    nstep = -(-(-(-K // 512)) // 4)
+    return N * K * 3 // 2 + -(-N // rb) * -(-nstep // cu) * 4 * 32
+
+
+def w12_pack(weight, swiglu=False, refuse=True):
+    """Pack a dense bf16 [N, K] device tensor for the launch geometry of its shape (`swiglu`: as one of the W / W3 pair) ->
+    W12Packed, or None when the shape is unsupported or (`refuse`) more than W12_MAX_OVERFLOW of the records overflow.
+    Synchronises (reads the packer's counts back): not for use under stream capture."""
+    N, K = weight.shape
+    geo = w12_geometry(N, K, swiglu)
+    if geo is None or weight.dtype != torch.bfloat16 or not (weight.is_cuda and weight.is_contiguous()) or N * K >= 1 << 31:
+        return None
+    rb, cu = geo[0], geo[1]
+    nstep = -(-(-(-K // 512)) // 4)
+    nrec = -(-N // rb) * -(-nstep // cu) * 4
+    p = W12Packed()
+    p.codes = torch.empty((N, K // 8 * 3), dtype=torch.int32, device=weight.device)
+    p.records = torch.empty((nrec, 8), dtype=torch.int32, device=weight.device)
+    meta = torch.empty((int(_abi.lib()["cc_w12_meta_words"]()),), dtype=torch.int32, device=weight.device)
+    _abi.call("cc_w12_pack", _p(weight), N, K, rb, cu, _p(p.codes), _p(p.records), _p(meta), _stream())
+    m = meta[:4].tolist()
+    p.base, p.n_records, p.n_overflow, p.n_escapes = m
+    p.rb, p.cu, p.xs, p.cap = geo[:4]
+    if refuse and p.n_overflow > W12_MAX_OVERFLOW * p.n_records:
+        return None
+    return p
+
+
+def _w12_drop(key):
+    global _w12_drops
+    if _w12_cache.pop(key, None) is not None:
+        _w12_drops += 1
+
+
+def _w12_get(weight, swiglu, force=False):
+    """The packed copy of `weight`, built at its first eager use; None: take the plain path (a launch class that did not measure
+    faster than the dense kernel, unless `force`; under capture before a copy exists; refused by the packer; unsupported shape; no
+    room).  Keyed on the storage and its version counter: an in-place change of the weight drops the copy."""
+    global _w12_warned
+    N, K = weight.shape
+    geo = w12_geometry(N, K, swiglu)
+    if geo is None or not (force or geo[4]):
+        return None
+    key = (weight.data_ptr(), weight._version, tuple(weight.shape), weight.device, swiglu)
+    hit = _w12_cache.get(key)
+    if hit is not None and hit[1]() is not None:
+        return hit[0]
+    if torch.cuda.is_current_stream_capturing():
+        return None  # never pack under capture: this replayed graph keeps the plain kernel
+    for k in [k for k in _w12_cache if k[0] == key[0] and k[3] == key[3] and (k == key or k[1] != key[1] or k[2] != key[2])]:
+        _w12_drop(k)  # the weight changed in place (or its storage was reused): its old copy goes
+    # room: what the driver reports free plus what torch's allocator holds cached but unused
+    free = torch.cuda.mem_get_info(weight.device)[0] + torch.cuda.memory_reserved(weight.device) - torch.cuda.memory_allocated(weight.device)
+    p = None
+    if free >= w12_nbytes(N, K, geo[0], geo[1]) + _W12_MARGIN:
+        p = w12_pack(weight, swiglu)
+    elif not _w12_warned:
+        _w12_warned = True
+        warnings.warn("cold_compress_amd: not enough free device memory for the 12-bit packed weight copies; the remaining dense "
+                      "layers decode from their bf16 weights (CC_W12=0 switches the copies off)")
+    _w12_cache[key] = (p, weakref.ref(weight))  # (None as well: not tried again until the weight changes or the cache is cleared)
+    weakref.finalize(weight, _w12_drop, key)
+    return p
+
+
+def w12_epoch():
+    """Changes whenever a captured graph may hold the address of a packed copy that is gone or out of date: a copy was dropped
+    (w12_cache_clear, a repack, a freed weight), or a weight with a copy changed in place since (its version counter moved; the copy
+    is rebuilt by the next EAGER use only).  GraphedDecoder compares it before every replay and captures again when it moved; any
+    other holder of a captured graph over gemv_fused(..., w12=...) has to do the same."""
+    stale = 0
+    for key, (p, ref) in _w12_cache.items():
+        if p is not None:
+            w = ref()
+            if w is not None and w._version != key[1]:
+                stale += 1
+    return (_w12_drops, stale)
+
+
+def w12_cache_clear():
+    """Drop every packed copy.  Their memory is free for reuse at once: a captured graph that launched cc_gemv_fused_w12 must not
+    be replayed afterwards (w12_epoch moves; GraphedDecoder captures again)."""
+    for k in list(_w12_cache):
+        _w12_drop(k)
+
+
 def gemv_fused(weight, x, w3=None, delta=None, norm_weight=None, eps=1e-5, h_out=None, bias=None, freqs=None, rope_rows=0,
-               head_dim=0, scales=None, scales3=None, groupsize=None):
+               head_dim=0, scales=None, scales3=None, groupsize=None, w12=False):
     """One decode-time dense layer with its glue fused (cc_gemv_fused): optional RMSNorm(x + delta) prologue (h_out
     receives x + delta), optional SwiGLU pairing with `w3`, optional RoPE epilogue on the first `rope_rows` rows.
     x: [K] (any shape with K elements); returns [N] in the model dtype.
@@ -142,6 +266,18 @@ def gemv_fused(weight, x, w3=None, delta=None, norm_weight=None, eps=1e-5, h_out
                   _p(bias), _p(fc), int(rope_rows), int(head_dim), _p(y), N, K, _DT[dt], _stream())
         return y
     y = torch.empty((N,), dtype=weight.dtype, device=weight.device)
+    if w12 and weight.dtype == torch.bfloat16 and w12_enabled() and (w3 is None or w3.dtype == torch.bfloat16):
+        # the lossless 12-bit packed copies of the weights: the same bits from three quarters of the bytes (cc_gemv_fused_w12).
+        # w12=True: where that launch class measured faster than the dense kernel; w12="force": wherever the kernel serves the shape
+        force = w12 == "force"
+        pk = _w12_get(weight, w3 is not None, force)
+        pk3 = _w12_get(w3, True, force) if (w3 is not None and pk is not None) else None
+        if pk is not None and (w3 is None or pk3 is not None):
+            _abi.call("cc_gemv_fused_w12", _p(pk.codes), _p(pk.records), pk.base, _p(pk3.codes) if pk3 else None,
+                      _p(pk3.records) if pk3 else None, pk3.base if pk3 else 0, pk.rb, pk.cu, _p(weight), _p(w3), _p(xc), _p(dc),
+                      _p(norm_weight), float(eps), _p(h_out), _p(bias), _p(fc), int(rope_rows), int(head_dim), _p(y), N, K,
+                      _DT[weight.dtype], _stream())
+            return y
     _abi.call("cc_gemv_fused", _p(weight), _p(w3), _p(xc), _p(dc), _p(norm_weight),
               float(eps), _p(h_out), _p(bias), _p(fc), int(rope_rows), int(head_dim),
               _p(y), N, K, _DT[weight.dtype], _stream())

@@ -136,7 +136,7 @@ class FeedForward(nn.Module):
         if fused is not None:
             delta, norm, h_out = fused
             g = glue.gemv_fused(self.w1.weight, x, w3=self.w3.weight, delta=delta, norm_weight=norm.weight, eps=norm.eps, h_out=h_out,
-                                **{**_quant(self.w1), **_quant(self.w3, "3")})
+                                w12=True, **{**_quant(self.w1), **_quant(self.w3, "3")})
             return glue.gemv_fused(self.w2.weight, g, **_quant(self.w2)).view(1, 1, -1)
         return self.w2(glue.silu_mul(self.w1(x), self.w3(x)))
 
@@ -372,7 +372,7 @@ class Transformer(nn.Module):
                 and glue.gemv_supported(self.output.weight)):
             # final RMSNorm (with the last pending residual) fused into the streamed LM head
             return glue.gemv_fused(self.output.weight, x, delta=delta, norm_weight=self.norm.weight, eps=self.norm.eps,
-                                   **_quant(self.output)).view(1, 1, -1)
+                                   w12=True, **_quant(self.output)).view(1, 1, -1)
         return self.output(self.norm(x, delta)[1])
 
     def block_eligible(self, attn_top_k=1.0):

@@ -791,6 +791,38 @@ int cc_gemv_fused_multi(const void* W, const void* W3, const void* x, const void
                         void* h_out, const void* bias, const void* freqs, int32_t rope_rows, int32_t head_dim, void* y,
                         int32_t N, int32_t K, int32_t T, int32_t dtype, cc_stream_t stream);
 
+/* cc_gemv_fused over a LOSSLESS 12-bit packed copy of dense bf16 weights ("w12"): y and h_out are BIT-IDENTICAL to cc_gemv_fused
+ * with the same arguments, for three quarters of the weight bytes read.
+ *   codes     uint32 [N, K / 8, 3]: the 8 weights of 16-byte chunk c of a row as 12 bytes — dwords 0, 1: byte i = sign << 7 |
+ *             mantissa of weight i; dword 2: 4-bit exponent indices (exponent = base + index), weight 2 j at bits [4 j, 4 j + 4),
+ *             weight 2 j + 1 at bits [16 + 4 j, 16 + 4 j + 4).
+ *   records   uint32 [ceil(N / RB), ceil(nstep / CU), 4, 8] with nstep = ceil(ceil(K / 512) / 4): the weights whose exponent lies
+ *             outside [base, base + 15] ("escapes": ±0, subnormals, inf, NaN and outliers among them) of the RB x CU chunks per
+ *             lane that wave w of a workgroup requests together for row group g and issue phase p — element t = r * CU + u is
+ *             chunk ((p * CU + u) * 4 + w) * 64 + lane of row g * RB + r.  Word 0: the count, 0 .. 7, or 0xFFFFFFFF when there
+ *             are more than 7 (the kernel then reads that tile from W itself); words 1 .. 7: t << 25 | lane << 19 | weight in
+ *             chunk << 16 | the raw bf16 bits.  The code of an escaped weight is arbitrary.
+ * cc_w12_geometry: out[0 .. 3] = RB, CU, input chunks kept per lane, most workgroups of the launch for (N, K) and the form (swiglu:
+ *             the W / W3 pair); out[4] = 1 when that launch class measured faster than cc_gemv_fused on MI355X (the pair, and plain
+ *             matrices of 32768 rows or more, at K <= 4096), else 0: callers should keep such weights dense by default.
+ *             CC_ERR_UNSUPPORTED when K % 8 != 0 or K > 16384.  Host only.
+ * cc_w12_pack: packs W (bf16 [N, K], dense) for the geometry (rb, cu) into codes and records; meta is a device scratch of
+ *             cc_w12_meta_words() int32 that afterwards holds base (word 0), the number of records (1), of overflowing records (2)
+ *             and of escapes (3).  CC_ERR_UNSUPPORTED for 2^31 weights or more.  base is the start of the window of 16 exponents that covers most weights, 0 .. 240.
+ *             Asynchronous on `stream`; three launches, run once per tensor.
+ * cc_gemv_fused_w12: cc_gemv_fused's arguments behind the packed copy of W (and of W3, when W3 != NULL) and the (rb, cu) they were
+ *             packed for; CC_ERR_BAD_ARG when that is not cc_w12_geometry's answer for this call.  W and W3 stay arguments: tiles
+ *             whose record overflowed are read from them.  dtype: CC_DT_BF16 (others: CC_ERR_UNSUPPORTED).  A plain grid, no
+ *             atomics; arguments are validated before any launch: an error writes nothing. */
+int cc_w12_geometry(int32_t N, int32_t K, int32_t swiglu, int32_t* out);
+size_t cc_w12_meta_words(void);
+int cc_w12_pack(const void* W, int32_t N, int32_t K, int32_t rb, int32_t cu, void* codes, void* records, void* meta,
+                cc_stream_t stream);
+int cc_gemv_fused_w12(const void* codes, const void* records, int32_t base, const void* codes3, const void* records3,
+                      int32_t base3, int32_t rb, int32_t cu, const void* W, const void* W3, const void* x, const void* delta,
+                      const void* norm_w, float eps, void* h_out, const void* bias, const void* freqs, int32_t rope_rows,
+                      int32_t head_dim, void* y, int32_t N, int32_t K, int32_t dtype, cc_stream_t stream);
+
 /* The same decode-time dense layer over INT8 WEIGHT-ONLY matrices (the weight-only int8 checkpoint format, ref: quantize.py
  * WeightOnlyInt8QuantHandler / WeightOnlyInt8Linear): W, W3 int8 [N, K] row major, one scale per output row, scales / scales3 [N]
  * in `dtype`, which is also the activation, bias, freqs and output dtype.
