@@ -35,22 +35,7 @@ __global__ __launch_bounds__(kGvThreads) void gemv_kernel(GemvArgs a) {
   const uint4* Wv = reinterpret_cast<const uint4*>(a.W);
   const uint4* W3v = reinterpret_cast<const uint4*>(a.W3);
   uint4 w[RB][CU], w3[RB][CU];
-  auto issue = [&](int r0, int s0) {
-#pragma unroll
-    for (int u = 0; u < CU; u++) {
-      const int c = ((s0 + u) * kGvWaves + wave) * 64 + lane;
-      const bool cin = (s0 + u < nstep) && c < nch;
-#pragma unroll
-      for (int r = 0; r < RB; r++) {
-        const bool in = cin && (r0 + r < N);
-        const size_t off = (size_t)(r0 + r) * nch + c;
-        // non-temporal: 15 GB of weights pass once per token, nothing is gained by keeping them in L2 / the 256 MB
-        // Infinity Cache (measured: w1+w3 43.1 -> 40.1 us, w2 24.8 -> 22.5 us)
-        w[r][u] = in ? nt_load(Wv + off) : make_uint4(0, 0, 0, 0);
-        if (SWIGLU) w3[r][u] = in ? nt_load(W3v + off) : make_uint4(0, 0, 0, 0);
-      }
-    }
-  };
+  auto issue = gv_plain_tile<SWIGLU>(w, w3, Wv, W3v, N, nch, nstep, lane, wave);
   auto get = [&](int r, int u) { return w[r][u]; };
   auto get3 = [&](int r, int u) { return w3[r][u]; };
   gemv_body<T, SWIGLU, RB, CU, XS>(a, issue, get, get3);
@@ -93,44 +78,6 @@ static GvCfg pick_cfg(const GemvArgs& a, int vec) {
   return c;
 }
 
-template <typename T, bool SWIGLU, int RB, int CU, int XS>
-static void launch_cfg(const GemvArgs& a, hipStream_t st, int cap) {
-  int blocks = (a.N + RB - 1) / RB;
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL((gemv_kernel<T, SWIGLU, RB, CU, XS>), dim3(blocks), dim3(kGvThreads), 0, st, a);
-}
-
-template <typename T>
-static int launch_gemv(const GemvArgs& a, hipStream_t st) {
-  const int vec = 16 / (int)sizeof(T);
-  const GvCfg c = pick_cfg(a, vec);
-  const int nseg = (a.K / vec + 63) / 64, nstep = (nseg + kGvWaves - 1) / kGvWaves;
-  const int xs = nstep <= 2 ? 2 : nstep <= 8 ? 8 : 16;  // input chunks kept per lane
-  if (nstep > 16 || c.cu > xs) return CC_ERR_UNSUPPORTED;
-  const int key = (a.W3 ? 100000 : 0) + xs * 1000 + c.rb * 10 + c.cu;
-  switch (key) {
-    case 2022: launch_cfg<T, false, 2, 2, 2>(a, st, c.cap); break;
-    case 2042: launch_cfg<T, false, 4, 2, 2>(a, st, c.cap); break;
-    case 2082: launch_cfg<T, false, 8, 2, 2>(a, st, c.cap); break;
-    case 8022: launch_cfg<T, false, 2, 2, 8>(a, st, c.cap); break;
-    case 8024: launch_cfg<T, false, 2, 4, 8>(a, st, c.cap); break;
-    case 8044: launch_cfg<T, false, 4, 4, 8>(a, st, c.cap); break;
-    case 8028: launch_cfg<T, false, 2, 8, 8>(a, st, c.cap); break;
-    case 8048: launch_cfg<T, false, 4, 8, 8>(a, st, c.cap); break;
-    case 16044: launch_cfg<T, false, 4, 4, 16>(a, st, c.cap); break;
-    case 16028: launch_cfg<T, false, 2, 8, 16>(a, st, c.cap); break;
-    case 102022: launch_cfg<T, true, 2, 2, 2>(a, st, c.cap); break;
-    case 102042: launch_cfg<T, true, 4, 2, 2>(a, st, c.cap); break;
-    case 108022: launch_cfg<T, true, 2, 2, 8>(a, st, c.cap); break;
-    case 108024: launch_cfg<T, true, 2, 4, 8>(a, st, c.cap); break;
-    case 108028: launch_cfg<T, true, 2, 8, 8>(a, st, c.cap); break;
-    case 116024: launch_cfg<T, true, 2, 4, 16>(a, st, c.cap); break;
-    default: return CC_ERR_UNSUPPORTED;
-  }
-  CC_LAUNCH_CHECK();
-  return CC_OK;
-}
-
 // ---- the same product for NT input vectors from ONE pass over the weights (cc_gemv_fused_multi): blocks of decode steps whose
 //      input tokens are known (teacher forcing, the tail of a long prompt) need not stream W once per token.  Row t of y / h_out is
 //      BIT-IDENTICAL to gemv_kernel on row t of x / delta / freqs: the lane that owns a 16-byte chunk, the order of a lane's Dot16
@@ -155,20 +102,7 @@ __global__ __launch_bounds__(kGvThreads) void gemv_multi_kernel(GemvArgs a) {
   const uint4* Wv = reinterpret_cast<const uint4*>(a.W);
   const uint4* W3v = reinterpret_cast<const uint4*>(a.W3);
   uint4 w[RB][CU], w3[RB][CU];
-  auto issue = [&](int r0, int s0) {
-#pragma unroll
-    for (int u = 0; u < CU; u++) {
-      const int c = ((s0 + u) * kGvWaves + wave) * 64 + lane;
-      const bool cin = (s0 + u < nstep) && c < nch;
-#pragma unroll
-      for (int r = 0; r < RB; r++) {
-        const bool in = cin && (r0 + r < N);
-        const size_t off = (size_t)(r0 + r) * nch + c;
-        w[r][u] = in ? nt_load(Wv + off) : make_uint4(0, 0, 0, 0);
-        if (SWIGLU) w3[r][u] = in ? nt_load(W3v + off) : make_uint4(0, 0, 0, 0);
-      }
-    }
-  };
+  auto issue = gv_plain_tile<SWIGLU>(w, w3, Wv, W3v, N, nch, nstep, lane, wave);
   const int row_first = blockIdx.x * RB;
   if (row_first < N) issue(row_first, 0);
 
@@ -346,17 +280,22 @@ static GvCfg pick_multi_cfg(const GemvArgs& a, int vec, int xs, int nt) {
 }
 
 template <typename T, bool SWIGLU, int RB, int CU, int XS, int NT>
-static void launch_multi_cfg(const GemvArgs& a, hipStream_t st, int cap) {
+static void launch_cfg(const GemvArgs& a, hipStream_t st, int cap) {
   int blocks = (a.N + RB - 1) / RB;
   if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL((gemv_multi_kernel<T, SWIGLU, RB, CU, XS, NT>), dim3(blocks), dim3(kGvThreads), 0, st, a);
+  if constexpr (NT == 1) {
+    hipLaunchKernelGGL((gemv_kernel<T, SWIGLU, RB, CU, XS>), dim3(blocks), dim3(kGvThreads), 0, st, a);
+  } else {
+    hipLaunchKernelGGL((gemv_multi_kernel<T, SWIGLU, RB, CU, XS, NT>), dim3(blocks), dim3(kGvThreads), 0, st, a);
+  }
 }
 
+// NT = 1: the single-vector kernel (pick_multi_cfg is pick_cfg there, and every instantiation of the table is built)
 template <typename T, int NT>
-static int launch_gemv_multi(const GemvArgs& a, hipStream_t st) {
+static int launch_gemv(const GemvArgs& a, hipStream_t st) {
   const int vec = 16 / (int)sizeof(T);
   const int nseg = (a.K / vec + 63) / 64, nstep = (nseg + kGvWaves - 1) / kGvWaves;
-  const int xs = nstep <= 2 ? 2 : nstep <= 8 ? 8 : 16;
+  const int xs = nstep <= 2 ? 2 : nstep <= 8 ? 8 : 16;  // input chunks kept per lane
   const GvCfg c = pick_multi_cfg(a, vec, xs, NT);
   if (nstep > 16 || c.cu > xs) return CC_ERR_UNSUPPORTED;
   const int key = (a.W3 ? 100000 : 0) + xs * 1000 + c.rb * 10 + c.cu;
@@ -364,35 +303,35 @@ static int launch_gemv_multi(const GemvArgs& a, hipStream_t st) {
   constexpr bool kF32 = sizeof(T) == 4;
   constexpr bool kWide16 = !(kF32 && NT >= 3), kNarrow16 = kF32 && NT == 3, kWide8 = !(kF32 && NT == 4);
   switch (key) {
-    case 2022: launch_multi_cfg<T, false, 2, 2, 2, NT>(a, st, c.cap); break;
-    case 2042: launch_multi_cfg<T, false, 4, 2, 2, NT>(a, st, c.cap); break;
-    case 2082: launch_multi_cfg<T, false, 8, 2, 2, NT>(a, st, c.cap); break;
-    case 8022: launch_multi_cfg<T, false, 2, 2, 8, NT>(a, st, c.cap); break;
-    case 8024: launch_multi_cfg<T, false, 2, 4, 8, NT>(a, st, c.cap); break;
-    case 8044: launch_multi_cfg<T, false, 4, 4, 8, NT>(a, st, c.cap); break;
-    case 8028: launch_multi_cfg<T, false, 2, 8, 8, NT>(a, st, c.cap); break;
+    case 2022: launch_cfg<T, false, 2, 2, 2, NT>(a, st, c.cap); break;
+    case 2042: launch_cfg<T, false, 4, 2, 2, NT>(a, st, c.cap); break;
+    case 2082: launch_cfg<T, false, 8, 2, 2, NT>(a, st, c.cap); break;
+    case 8022: launch_cfg<T, false, 2, 2, 8, NT>(a, st, c.cap); break;
+    case 8024: launch_cfg<T, false, 2, 4, 8, NT>(a, st, c.cap); break;
+    case 8044: launch_cfg<T, false, 4, 4, 8, NT>(a, st, c.cap); break;
+    case 8028: launch_cfg<T, false, 2, 8, 8, NT>(a, st, c.cap); break;
     case 8048:
-      if constexpr (kWide8) launch_multi_cfg<T, false, 4, 8, 8, NT>(a, st, c.cap); else return CC_ERR_UNSUPPORTED;
+      if constexpr (kWide8) launch_cfg<T, false, 4, 8, 8, NT>(a, st, c.cap); else return CC_ERR_UNSUPPORTED;
       break;
     case 16044:
-      if constexpr (kWide16) launch_multi_cfg<T, false, 4, 4, 16, NT>(a, st, c.cap); else return CC_ERR_UNSUPPORTED;
+      if constexpr (kWide16) launch_cfg<T, false, 4, 4, 16, NT>(a, st, c.cap); else return CC_ERR_UNSUPPORTED;
       break;
     case 16028:
-      if constexpr (kWide16) launch_multi_cfg<T, false, 2, 8, 16, NT>(a, st, c.cap); else return CC_ERR_UNSUPPORTED;
+      if constexpr (kWide16) launch_cfg<T, false, 2, 8, 16, NT>(a, st, c.cap); else return CC_ERR_UNSUPPORTED;
       break;
     case 16022:
-      if constexpr (kNarrow16) launch_multi_cfg<T, false, 2, 2, 16, NT>(a, st, c.cap); else return CC_ERR_UNSUPPORTED;
+      if constexpr (kNarrow16) launch_cfg<T, false, 2, 2, 16, NT>(a, st, c.cap); else return CC_ERR_UNSUPPORTED;
       break;
-    case 102022: launch_multi_cfg<T, true, 2, 2, 2, NT>(a, st, c.cap); break;
-    case 102042: launch_multi_cfg<T, true, 4, 2, 2, NT>(a, st, c.cap); break;
-    case 108022: launch_multi_cfg<T, true, 2, 2, 8, NT>(a, st, c.cap); break;
-    case 108024: launch_multi_cfg<T, true, 2, 4, 8, NT>(a, st, c.cap); break;
-    case 108028: launch_multi_cfg<T, true, 2, 8, 8, NT>(a, st, c.cap); break;
+    case 102022: launch_cfg<T, true, 2, 2, 2, NT>(a, st, c.cap); break;
+    case 102042: launch_cfg<T, true, 4, 2, 2, NT>(a, st, c.cap); break;
+    case 108022: launch_cfg<T, true, 2, 2, 8, NT>(a, st, c.cap); break;
+    case 108024: launch_cfg<T, true, 2, 4, 8, NT>(a, st, c.cap); break;
+    case 108028: launch_cfg<T, true, 2, 8, 8, NT>(a, st, c.cap); break;
     case 116024:
-      if constexpr (kWide16) launch_multi_cfg<T, true, 2, 4, 16, NT>(a, st, c.cap); else return CC_ERR_UNSUPPORTED;
+      if constexpr (kWide16) launch_cfg<T, true, 2, 4, 16, NT>(a, st, c.cap); else return CC_ERR_UNSUPPORTED;
       break;
     case 116022:
-      if constexpr (kNarrow16) launch_multi_cfg<T, true, 2, 2, 16, NT>(a, st, c.cap); else return CC_ERR_UNSUPPORTED;
+      if constexpr (kNarrow16) launch_cfg<T, true, 2, 2, 16, NT>(a, st, c.cap); else return CC_ERR_UNSUPPORTED;
       break;
     default: return CC_ERR_UNSUPPORTED;
   }
@@ -403,9 +342,9 @@ static int launch_gemv_multi(const GemvArgs& a, hipStream_t st) {
 template <typename T>
 static int launch_gemv_multi_t(const GemvArgs& a, int nt, hipStream_t st) {
   switch (nt) {
-    case 1: return launch_gemv<T>(a, st);  // one token: the single-vector kernel itself
-    case 2: return launch_gemv_multi<T, 2>(a, st);
-    case 3: return launch_gemv_multi<T, 3>(a, st);
+    case 1: return launch_gemv<T, 1>(a, st);  // one token: the single-vector kernel itself
+    case 2: return launch_gemv<T, 2>(a, st);
+    case 3: return launch_gemv<T, 3>(a, st);
     default: break;
   }
   if (sizeof(T) == 4 && (size_t)a.K * sizeof(T) > 32 * 1024) {
@@ -419,26 +358,20 @@ static int launch_gemv_multi_t(const GemvArgs& a, int nt, hipStream_t st) {
     if (a.h_out) b.h_out = (char*)a.h_out + 2 * (size_t)a.K * es;
     if (a.freqs) b.freqs = (const char*)a.freqs + 2 * (size_t)a.head_dim * es;
     b.y = (char*)a.y + 2 * (size_t)a.N * es;
-    const int rc = launch_gemv_multi<T, 2>(a, st);
-    return rc != CC_OK ? rc : launch_gemv_multi<T, 2>(b, st);
+    const int rc = launch_gemv<T, 2>(a, st);
+    return rc != CC_OK ? rc : launch_gemv<T, 2>(b, st);
   }
-  return launch_gemv_multi<T, 4>(a, st);
+  return launch_gemv<T, 4>(a, st);
 }
 
 }  // namespace
 
-extern "C" int cc_gemv_fused_multi(const void* W, const void* W3, const void* x, const void* delta, const void* norm_w, float eps,
-                                   void* h_out, const void* bias, const void* freqs, int32_t rope_rows, int32_t head_dim, void* y,
-                                   int32_t N, int32_t K, int32_t T, int32_t dtype, cc_stream_t stream) {
-  CC_ENTRY();
-  if (!W || !x || !y || N <= 0 || K <= 0 || !cc_dt_ok(dtype)) return CC_ERR_BAD_ARG;
-  if (T < 1 || T > CC_GEMV_MULTI_MAX_T) return CC_ERR_BAD_ARG;
-  if ((delta || h_out) && !norm_w) return CC_ERR_BAD_ARG;
-  if (freqs && (W3 || rope_rows < 0 || rope_rows > N || head_dim <= 0 || (head_dim & 1) || (rope_rows % head_dim))) return CC_ERR_BAD_ARG;
-  if (W3 && bias) return CC_ERR_BAD_ARG;
+static int gemv_fused_entry(const void* W, const void* W3, const void* x, const void* delta, const void* norm_w, float eps, void* h_out,
+                            const void* bias, const void* freqs, int32_t rope_rows, int32_t head_dim, void* y, int32_t N, int32_t K,
+                            int32_t T, int32_t dtype, cc_stream_t stream) {
+  if (const int rc = gv_check_args(W, W3, x, delta, norm_w, h_out, bias, freqs, rope_rows, head_dim, y, N, K, T, dtype)) return rc;
   const int vec = 16 / (int)cc_dt_size(dtype);
   if (K % vec) return CC_ERR_UNSUPPORTED;
-  if ((size_t)K * cc_dt_size(dtype) > 64 * 1024) return CC_ERR_UNSUPPORTED;
   GemvArgs a{W, W3, x, delta, norm_w, bias, freqs, h_out, y, eps, N, K, freqs ? rope_rows : 0, freqs ? head_dim : 2};
   hipStream_t st = (hipStream_t)stream;
   switch (dtype) {
@@ -448,22 +381,16 @@ extern "C" int cc_gemv_fused_multi(const void* W, const void* W3, const void* x,
   }
 }
 
+extern "C" int cc_gemv_fused_multi(const void* W, const void* W3, const void* x, const void* delta, const void* norm_w, float eps,
+                                   void* h_out, const void* bias, const void* freqs, int32_t rope_rows, int32_t head_dim, void* y,
+                                   int32_t N, int32_t K, int32_t T, int32_t dtype, cc_stream_t stream) {
+  CC_ENTRY();
+  return gemv_fused_entry(W, W3, x, delta, norm_w, eps, h_out, bias, freqs, rope_rows, head_dim, y, N, K, T, dtype, stream);
+}
+
 extern "C" int cc_gemv_fused(const void* W, const void* W3, const void* x, const void* delta, const void* norm_w, float eps,
                              void* h_out, const void* bias, const void* freqs, int32_t rope_rows, int32_t head_dim, void* y,
                              int32_t N, int32_t K, int32_t dtype, cc_stream_t stream) {
   CC_ENTRY();
-  if (!W || !x || !y || N <= 0 || K <= 0 || !cc_dt_ok(dtype)) return CC_ERR_BAD_ARG;
-  if ((delta || h_out) && !norm_w) return CC_ERR_BAD_ARG;
-  if (freqs && (W3 || rope_rows < 0 || rope_rows > N || head_dim <= 0 || (head_dim & 1) || (rope_rows % head_dim))) return CC_ERR_BAD_ARG;
-  if (W3 && bias) return CC_ERR_BAD_ARG;
-  const int vec = 16 / (int)cc_dt_size(dtype);
-  if (K % vec) return CC_ERR_UNSUPPORTED;
-  if ((size_t)K * cc_dt_size(dtype) > 64 * 1024) return CC_ERR_UNSUPPORTED;  // 16 input chunks per lane at most
-  GemvArgs a{W, W3, x, delta, norm_w, bias, freqs, h_out, y, eps, N, K, freqs ? rope_rows : 0, freqs ? head_dim : 2};
-  hipStream_t st = (hipStream_t)stream;
-  switch (dtype) {
-    case CC_DT_F32: return launch_gemv<float>(a, st);
-    case CC_DT_BF16: return launch_gemv<bf16_t>(a, st);
-    default: return launch_gemv<f16_t>(a, st);
-  }
+  return gemv_fused_entry(W, W3, x, delta, norm_w, eps, h_out, bias, freqs, rope_rows, head_dim, y, N, K, 1, dtype, stream);
 }

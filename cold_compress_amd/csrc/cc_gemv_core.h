@@ -1,6 +1,8 @@
 // cc_gemv_core.h — the arithmetic of the streamed matrix-vector products (cc_gemv.hip), shared with the single-launch layer step
 // that folds the layer's QKV projection in (cc_attn_decode_qkv.hip): the SAME products, chains and reduction orders, so that the
-// fused launch and the stand-alone GEMV give bit-identical q / k / v.
+// fused launch and the stand-alone GEMV give bit-identical q / k / v.  Also here, once for the five cc_gemv*.hip: the weight tiles of
+// the two layouts (gv_plain_tile, gv_scaled_tile), the dense body (gemv_body) and the entry points' shared argument check
+// (gv_check_args).  DESIGN.md §2.19 lists which step lives where, and which are still one text per kernel.
 #pragma once
 #include "cc_common.h"
 
@@ -79,6 +81,63 @@ __device__ __forceinline__ uint4 pack16(const float* f) {
   }
 }
 
+constexpr int kGvCoreThreads = 256;  // the workgroup gemv_body is written for: four waves split a row's segments
+constexpr int kGvCoreWaves = kGvCoreThreads / 64;
+
+// ---- the weight tile of a wave, once for every kernel of a layout (single and multi forms of a format share it, and with it the
+//      chunk ownership): the returned issue(r0, s0) requests RB rows from r0 x CU column steps from s0 into w / w3, zero-filled
+//      outside the matrix.  It refers to the kernel's own variables, so they must outlive it.
+//      Non-temporal: 15 GB of weights pass once per token, nothing is gained by keeping them in L2 / the 256 MB Infinity Cache
+//      (measured: w1+w3 43.1 -> 40.1 us, w2 24.8 -> 22.5 us).
+//      The PLAIN layout (dense, int8): the four waves of a workgroup split every row's 1 KiB segments.
+template <bool SWIGLU, int RB, int CU>
+__device__ __forceinline__ auto gv_plain_tile(uint4 (&w)[RB][CU], uint4 (&w3)[RB][CU], const uint4* const& Wv, const uint4* const& W3v,
+                                              const int& N, const int& nch, const int& nstep, const int& lane, const int& wave) {
+  return [&](int r0, int s0) {
+#pragma unroll
+    for (int u = 0; u < CU; u++) {
+      const int c = ((s0 + u) * kGvCoreWaves + wave) * 64 + lane;
+      const bool cin = (s0 + u < nstep) && c < nch;
+#pragma unroll
+      for (int r = 0; r < RB; r++) {
+        const bool in = cin && (r0 + r < N);
+        const size_t off = (size_t)(r0 + r) * nch + c;
+        w[r][u] = in ? nt_load(Wv + off) : make_uint4(0, 0, 0, 0);
+        if (SWIGLU) w3[r][u] = in ? nt_load(W3v + off) : make_uint4(0, 0, 0, 0);
+      }
+    }
+  };
+}
+//      The SCALED layout (int4, MXFP4): WS waves per row (wave ws of them takes segments ws, ws + WS, ...), r0 is this wave's first
+//      row, and a 32-bit scale word travels beside every chunk, read from the format's table sc (sc3 for W3): GROUPED, the word of
+//      the chunk's group, sc[row * ngr + (c >> gshift)]; otherwise the chunk's own, sc[row * nch + c] (ngr and gshift are not read).
+//      FILL stands beside zero-filled codes.
+template <bool SWIGLU, int WS, bool GROUPED, uint32_t FILL, int RB, int CU, typename P>
+__device__ __forceinline__ auto gv_scaled_tile(uint4 (&w)[RB][CU], uint4 (&w3)[RB][CU], uint32_t (&q)[RB][CU], uint32_t (&q3)[RB][CU],
+                                               const uint4* const& Wv, const uint4* const& W3v, const P* const& sc, const P* const& sc3,
+                                               const int& N, const int& nch, const int& nstep, const int& lane, const int& ws,
+                                               const int& ngr, const int& gshift) {
+  return [&](int r0, int s0) {
+#pragma unroll
+    for (int u = 0; u < CU; u++) {
+      const int c = ((s0 + u) * WS + ws) * 64 + lane;
+      const bool cin = (s0 + u < nstep) && c < nch;
+#pragma unroll
+      for (int r = 0; r < RB; r++) {
+        const bool in = cin && (r0 + r < N);
+        const size_t off = (size_t)(r0 + r) * nch + c;
+        const size_t qoff = GROUPED ? (size_t)(r0 + r) * ngr + (c >> gshift) : off;
+        w[r][u] = in ? nt_load(Wv + off) : make_uint4(0, 0, 0, 0);
+        q[r][u] = in ? (uint32_t)__builtin_nontemporal_load(sc + qoff) : FILL;
+        if (SWIGLU) {
+          w3[r][u] = in ? nt_load(W3v + off) : make_uint4(0, 0, 0, 0);
+          q3[r][u] = in ? (uint32_t)__builtin_nontemporal_load(sc3 + qoff) : FILL;
+        }
+      }
+    }
+  };
+}
+
 // ---- the single-vector GEMV (cc_gemv.hip's gemv_kernel) as a body over three callables of the kernel that owns the weight
 //      registers: issue(r0, s0) requests a wave's RB x CU weight chunks, get(r, u) / get3(r, u) hand one of them out as 16 bytes of
 //      T.  gemv_kernel reads them from the dense tensor; cc_gemv_w12.hip rebuilds the same 16 bytes from the 12-bit packed copy.
@@ -96,9 +155,6 @@ struct GemvArgs {
   float eps;
   int N, K, rope_rows, head_dim;
 };
-
-constexpr int kGvCoreThreads = 256;  // the workgroup gemv_body is written for: four waves split a row's segments
-constexpr int kGvCoreWaves = kGvCoreThreads / 64;
 
 template <typename T, bool SWIGLU, int RB, int CU, int XS, typename ISSUE, typename GET, typename GET3>
 __device__ __forceinline__ void gemv_body(const GemvArgs& a, ISSUE&& issue, GET&& get, GET3&& get3) {
@@ -254,5 +310,20 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, ISSUE&& issue, GET&
 struct GvCfg {
   int rb, cu, cap;
 };
+
+// ---- the argument conditions all cc_gemv_fused* entry points share (T = 1 for a single-vector entry point).  An entry point checks
+//      its own pointers and pairings before this, and what its format supports (dtype, K's multiple, alignment) after it: every
+//      CC_ERR_BAD_ARG condition comes before every CC_ERR_UNSUPPORTED one.
+static inline int gv_check_args(const void* W, const void* W3, const void* x, const void* delta, const void* norm_w, const void* h_out,
+                                const void* bias, const void* freqs, int rope_rows, int head_dim, const void* y, int N, int K, int T,
+                                int dtype) {
+  if (!W || !x || !y || N <= 0 || K <= 0 || !cc_dt_ok(dtype)) return CC_ERR_BAD_ARG;
+  if (T < 1 || T > CC_GEMV_MULTI_MAX_T) return CC_ERR_BAD_ARG;
+  if ((delta || h_out) && !norm_w) return CC_ERR_BAD_ARG;
+  if (freqs && (W3 || rope_rows < 0 || rope_rows > N || head_dim <= 0 || (head_dim & 1) || (rope_rows % head_dim))) return CC_ERR_BAD_ARG;
+  if (W3 && bias) return CC_ERR_BAD_ARG;
+  if ((size_t)K * cc_dt_size(dtype) > 64 * 1024) return CC_ERR_UNSUPPORTED;  // 16 input chunks per lane at most
+  return CC_OK;
+}
 
 }  // namespace

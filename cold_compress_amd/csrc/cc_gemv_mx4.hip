@@ -19,9 +19,12 @@
 // chains and the same LDS reduction): h_out and the normalised input are bit-identical to cc_gemv_fused's.  The normalised vector
 // is passed to the lanes that multiply it through LDS (K * 2 bytes, norm forms only).
 //
-// TWO COPIES: gemv_mx4_multi_kernel at the end of this file (the same product for up to four input vectors) repeats gemv_mx4_kernel's weight tile,
-// prologue, row loop and epilogue, token by token, and promises the same bits.  A change to the chunk ownership, a chain's order, a
-// reduction or a rounding point here has to be made there too (tests/test_gpu_gemv_wo_multi.py compares the two bit for bit).
+// TWO COPIES: gemv_mx4_multi_kernel further down (the same product for up to four input vectors) repeats gemv_mx4_kernel's prologue,
+// row loop and epilogue, token by token, and promises the same bits; the code / scale-byte tile, and with it the chunk ownership, is
+// ONE function for both (gv_scaled_tile, cc_gemv_core.h, shared with the int4 kernel).  A change to a chain's order, a reduction or a
+// rounding point here has to be made there too (tests/test_gpu_gemv_wo_multi.py compares the two bit for bit).  The copies stay
+// because moving those steps into shared functions changes the single-vector kernels' machine code.  Launcher,
+// MX4_CASE table and argument checks exist once, for every token count (NT = 1: the single-vector kernel).
 #include <cstdio>
 #include <cstdlib>
 
@@ -48,8 +51,6 @@ struct GemvMx4Args {
 
 constexpr int kMx4Threads = 256;
 constexpr int kMx4Waves = kMx4Threads / 64;
-
-__device__ __forceinline__ uint32_t nt_load_u8(const uint8_t* p) { return __builtin_nontemporal_load(p); }
 
 __device__ __forceinline__ float dot2_bf16(uint32_t a, uint32_t b, float acc) {
   return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, a), __builtin_bit_cast(bf16x2_t, b), acc, false);
@@ -94,24 +95,7 @@ __global__ __launch_bounds__(kMx4Threads) void gemv_mx4_kernel(GemvMx4Args a) {
   const uint4* W3v = reinterpret_cast<const uint4*>(a.W3);
   uint4 w[RB][CU], w3[RB][CU];
   uint32_t q[RB][CU], q3[RB][CU];  // the chunks' scale bytes (127, i.e. 1.0, beside zero-filled codes)
-  auto issue = [&](int r0, int s0) {  // r0: this wave's first row
-#pragma unroll
-    for (int u = 0; u < CU; u++) {
-      const int c = ((s0 + u) * WS + ws) * 64 + lane;
-      const bool cin = (s0 + u < nstep) && c < nch;
-#pragma unroll
-      for (int r = 0; r < RB; r++) {
-        const bool in = cin && (r0 + r < N);
-        const size_t off = (size_t)(r0 + r) * nch + c;
-        w[r][u] = in ? nt_load(Wv + off) : make_uint4(0, 0, 0, 0);
-        q[r][u] = in ? nt_load_u8(a.sc + off) : 127u;
-        if (SWIGLU) {
-          w3[r][u] = in ? nt_load(W3v + off) : make_uint4(0, 0, 0, 0);
-          q3[r][u] = in ? nt_load_u8(a.sc3 + off) : 127u;
-        }
-      }
-    }
-  };
+  auto issue = gv_scaled_tile<SWIGLU, WS, false, 127u>(w, w3, q, q3, Wv, W3v, a.sc, a.sc3, N, nch, nstep, lane, ws, nch, nch);
   const int row_first = blockIdx.x * RW;  // < N (the launcher sizes the grid)
   issue(row_first + rg * RB, 0);
 
@@ -271,67 +255,6 @@ static Mx4Cfg pick_mx4_cfg(const GemvMx4Args& a, int nstep) {
   return a.W3 != nullptr ? Mx4Cfg{2, 2, 512} : Mx4Cfg{4, 2, 512};
 }
 
-template <bool SWIGLU, int RB, int CU, int XS, int WS>
-static void launch_mx4_cfg(const GemvMx4Args& a, hipStream_t st, int cap) {
-  constexpr int RW = RB * (kMx4Waves / WS);
-  int blocks = (a.N + RW - 1) / RW;
-  if (blocks > cap) blocks = cap;
-  const size_t lds = a.norm_w != nullptr ? (size_t)a.K * sizeof(bf16_t) : 0;
-  hipLaunchKernelGGL((gemv_mx4_kernel<SWIGLU, RB, CU, XS, WS>), dim3(blocks), dim3(kMx4Threads), lds, st, a);
-}
-
-static int launch_gemv_mx4(const GemvMx4Args& a, hipStream_t st) {
-  const int nseg = (a.K / 32 + 63) / 64;
-  const int ws = nseg >= 3 ? 4 : nseg;  // waves per row: a short row leaves no wave idle
-  const int nstep = (nseg + ws - 1) / ws;
-  const Mx4Cfg c = pick_mx4_cfg(a, nstep);
-  const int xs = nstep <= 1 ? 1 : nstep <= 2 ? 2 : 4;  // input chunks kept per lane
-  if (nstep > 4 || c.cu > xs || c.cap <= 0) return CC_ERR_UNSUPPORTED;
-  const int key = (a.W3 ? 100000 : 0) + ws * 10000 + xs * 1000 + c.rb * 10 + c.cu;
-#define MX4_CASE(SW, WS_, XS_, RB_, CU_) \
-  case (SW ? 100000 : 0) + WS_ * 10000 + XS_ * 1000 + RB_ * 10 + CU_: launch_mx4_cfg<SW, RB_, CU_, XS_, WS_>(a, st, c.cap); break;
-  switch (key) {
-    MX4_CASE(false, 1, 1, 2, 1) MX4_CASE(false, 1, 1, 4, 1) MX4_CASE(false, 1, 1, 8, 1)
-    MX4_CASE(false, 2, 1, 2, 1) MX4_CASE(false, 2, 1, 4, 1) MX4_CASE(false, 2, 1, 8, 1)
-    MX4_CASE(false, 4, 1, 2, 1) MX4_CASE(false, 4, 1, 4, 1) MX4_CASE(false, 4, 1, 8, 1)
-    MX4_CASE(false, 4, 2, 4, 1) MX4_CASE(false, 4, 2, 8, 1) MX4_CASE(false, 4, 2, 2, 2) MX4_CASE(false, 4, 2, 4, 2) MX4_CASE(false, 4, 2, 8, 2)
-    MX4_CASE(false, 4, 4, 2, 4) MX4_CASE(false, 4, 4, 4, 2) MX4_CASE(false, 4, 4, 8, 2) MX4_CASE(false, 4, 4, 4, 4)
-    MX4_CASE(true, 1, 1, 2, 1) MX4_CASE(true, 1, 1, 4, 1) MX4_CASE(true, 1, 1, 8, 1)
-    MX4_CASE(true, 2, 1, 2, 1) MX4_CASE(true, 2, 1, 4, 1) MX4_CASE(true, 2, 1, 8, 1)
-    MX4_CASE(true, 4, 1, 2, 1) MX4_CASE(true, 4, 1, 4, 1) MX4_CASE(true, 4, 1, 8, 1)
-    MX4_CASE(true, 4, 2, 2, 1) MX4_CASE(true, 4, 2, 4, 1) MX4_CASE(true, 4, 2, 2, 2) MX4_CASE(true, 4, 2, 4, 2)
-    MX4_CASE(true, 4, 4, 2, 2) MX4_CASE(true, 4, 4, 4, 2) MX4_CASE(true, 4, 4, 2, 4)
-    default: return CC_ERR_UNSUPPORTED;
-  }
-#undef MX4_CASE
-  CC_LAUNCH_CHECK();
-  return CC_OK;
-}
-
-}  // namespace
-
-static inline bool mx4_aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-extern "C" int cc_gemv_fused_mx4(const uint8_t* W, const uint8_t* scales, const uint8_t* W3, const uint8_t* scales3, const void* x,
-                                 const void* delta, const void* norm_w, float eps, void* h_out, const void* bias, const void* freqs,
-                                 int32_t rope_rows, int32_t head_dim, void* y, int32_t N, int32_t K, int32_t dtype, cc_stream_t stream) {
-  CC_ENTRY();
-  if (!W || !scales || !x || !y || N <= 0 || K <= 0 || !cc_dt_ok(dtype)) return CC_ERR_BAD_ARG;
-  if ((W3 != nullptr) != (scales3 != nullptr)) return CC_ERR_BAD_ARG;
-  if ((delta || h_out) && !norm_w) return CC_ERR_BAD_ARG;
-  if (freqs && (W3 || rope_rows < 0 || rope_rows > N || head_dim <= 0 || (head_dim & 1) || (rope_rows % head_dim))) return CC_ERR_BAD_ARG;
-  if (W3 && bias) return CC_ERR_BAD_ARG;
-  // 16-byte vector accesses to the codes, the input vector and the prologue's operands; 2-byte elements elsewhere (null: aligned)
-  if (!mx4_aligned(W, 16) || !mx4_aligned(W3, 16) || !mx4_aligned(x, 16) || !mx4_aligned(delta, 16) || !mx4_aligned(norm_w, 16) ||
-      !mx4_aligned(h_out, 16) || !mx4_aligned(bias, 2) || !mx4_aligned(freqs, 2) || !mx4_aligned(y, 2))
-    return CC_ERR_BAD_ARG;
-  if (dtype != CC_DT_BF16) return CC_ERR_UNSUPPORTED;  // bf16 models only
-  if (K % 32) return CC_ERR_UNSUPPORTED;               // whole MX blocks
-  if ((size_t)K * sizeof(bf16_t) > 64 * 1024) return CC_ERR_UNSUPPORTED;
-  GemvMx4Args a{W, W3, scales, scales3, x, delta, norm_w, bias, freqs, h_out, y, eps, N, K, freqs ? rope_rows : 0, freqs ? head_dim : 2};
-  return launch_gemv_mx4(a, (hipStream_t)stream);
-}
-
 // ---- the same product for NT input vectors from ONE pass over the MXFP4 weights (cc_gemv_fused_mx4_multi): cc_gemv.hip's
 //      gemv_multi_kernel for this file's kernel.  Row t of y / h_out is BIT-IDENTICAL to gemv_mx4_kernel on row t of x / delta / freqs:
 //      the lane that owns a 16-byte code chunk, the order of that lane's dot2 chain, gv_wave_sum, the meet of a row's WS waves (WS
@@ -344,8 +267,6 @@ extern "C" int cc_gemv_fused_mx4(const uint8_t* W, const uint8_t* scales, const 
 //      sum of squares are formed first, in the 16-bit kernel's chunk layout, with h parked in the registers that will hold the token's
 //      input (4 * XS uint4: a lane never owns more 8-element chunks than that); then the tokens pass through the buffer one after the
 //      other — normalise token t into it, barrier, every lane picks up the 64-byte pieces it multiplies, barrier, the next token.
-namespace {
-
 __device__ __forceinline__ void deq_mx4_word(uint32_t w, float scale, uint32_t* p) {
   p[0] = cc_mx4_dequant2<bf16_t, 0>(w, scale);
   p[1] = cc_mx4_dequant2<bf16_t, 1>(w, scale);
@@ -393,24 +314,7 @@ __global__ __launch_bounds__(kMx4Threads) void gemv_mx4_multi_kernel(GemvMx4Args
   const uint4* W3v = reinterpret_cast<const uint4*>(a.W3);
   uint4 w[RB][CU], w3[RB][CU];
   uint32_t q[RB][CU], q3[RB][CU];
-  auto issue = [&](int r0, int s0) {  // r0: this wave's first row
-#pragma unroll
-    for (int u = 0; u < CU; u++) {
-      const int c = ((s0 + u) * WS + ws) * 64 + lane;
-      const bool cin = (s0 + u < nstep) && c < nch;
-#pragma unroll
-      for (int r = 0; r < RB; r++) {
-        const bool in = cin && (r0 + r < N);
-        const size_t off = (size_t)(r0 + r) * nch + c;
-        w[r][u] = in ? nt_load(Wv + off) : make_uint4(0, 0, 0, 0);
-        q[r][u] = in ? nt_load_u8(a.sc + off) : 127u;
-        if (SWIGLU) {
-          w3[r][u] = in ? nt_load(W3v + off) : make_uint4(0, 0, 0, 0);
-          q3[r][u] = in ? nt_load_u8(a.sc3 + off) : 127u;
-        }
-      }
-    }
-  };
+  auto issue = gv_scaled_tile<SWIGLU, WS, false, 127u>(w, w3, q, q3, Wv, W3v, a.sc, a.sc3, N, nch, nstep, lane, ws, nch, nch);
   const int row_first = blockIdx.x * RW;  // < N (the launcher sizes the grid)
   issue(row_first + rg * RB, 0);
 
@@ -585,96 +489,103 @@ __global__ __launch_bounds__(kMx4Threads) void gemv_mx4_multi_kernel(GemvMx4Args
   }
 }
 
+// NT = 1: the single-vector kernel at the geometry asked for.  NT > 1: only the DEFAULT geometry of a shape class (pick_mx4_cfg
+// without the tuning hook: 4 x 1 for one segment per wave, else 2 x 2 for the pair and 4 x 2) is built, ten instantiations per NT
+// (DESIGN.md §2.12 has their register figures; 8 rows per wave at WS = 1 would need more than wave 0's 64 finishing lanes), and every
+// geometry of the class runs it: the same bits — results do not depend on RB or CU — with the hook's cap on the grid.  WS stays
+// launch_gemv_mx4's function of K, which the order of a row's sum does depend on.
 template <bool SWIGLU, int RB, int CU, int XS, int WS, int NT>
-static void launch_mx4_multi_cfg(const GemvMx4Args& a, hipStream_t st, int cap) {
-  constexpr int RWm = RB * (kMx4Waves / WS);
-  int blocks = (a.N + RWm - 1) / RWm;
+static void launch_mx4_geo(const GemvMx4Args& a, hipStream_t st, int cap) {
+  constexpr int RW = RB * (kMx4Waves / WS);
+  int blocks = (a.N + RW - 1) / RW;
   if (blocks > cap) blocks = cap;
-  const size_t lds = a.norm_w != nullptr ? (size_t)a.K * sizeof(bf16_t) : 0;  // the single kernel's: one staging buffer for the NT tokens
-  hipLaunchKernelGGL((gemv_mx4_multi_kernel<SWIGLU, RB, CU, XS, WS, NT>), dim3(blocks), dim3(kMx4Threads), lds, st, a);
-}
-
-// true for the switch keys launch_gemv_mx4 serves (its MX4_CASE list): what a CC_GEMV_MX4_CFG may name
-static bool mx4_single_serves(int key) {
-#define MX4_KEY(SW, WS_, XS_, RB_, CU_) case (SW ? 100000 : 0) + WS_ * 10000 + XS_ * 1000 + RB_ * 10 + CU_:
-  switch (key) {
-    MX4_KEY(false, 1, 1, 2, 1) MX4_KEY(false, 1, 1, 4, 1) MX4_KEY(false, 1, 1, 8, 1)
-    MX4_KEY(false, 2, 1, 2, 1) MX4_KEY(false, 2, 1, 4, 1) MX4_KEY(false, 2, 1, 8, 1)
-    MX4_KEY(false, 4, 1, 2, 1) MX4_KEY(false, 4, 1, 4, 1) MX4_KEY(false, 4, 1, 8, 1)
-    MX4_KEY(false, 4, 2, 4, 1) MX4_KEY(false, 4, 2, 8, 1) MX4_KEY(false, 4, 2, 2, 2) MX4_KEY(false, 4, 2, 4, 2) MX4_KEY(false, 4, 2, 8, 2)
-    MX4_KEY(false, 4, 4, 2, 4) MX4_KEY(false, 4, 4, 4, 2) MX4_KEY(false, 4, 4, 8, 2) MX4_KEY(false, 4, 4, 4, 4)
-    MX4_KEY(true, 1, 1, 2, 1) MX4_KEY(true, 1, 1, 4, 1) MX4_KEY(true, 1, 1, 8, 1)
-    MX4_KEY(true, 2, 1, 2, 1) MX4_KEY(true, 2, 1, 4, 1) MX4_KEY(true, 2, 1, 8, 1)
-    MX4_KEY(true, 4, 1, 2, 1) MX4_KEY(true, 4, 1, 4, 1) MX4_KEY(true, 4, 1, 8, 1)
-    MX4_KEY(true, 4, 2, 2, 1) MX4_KEY(true, 4, 2, 4, 1) MX4_KEY(true, 4, 2, 2, 2) MX4_KEY(true, 4, 2, 4, 2)
-    MX4_KEY(true, 4, 4, 2, 2) MX4_KEY(true, 4, 4, 4, 2) MX4_KEY(true, 4, 4, 2, 4)
-      return true;
-    default: return false;
-  }
-#undef MX4_KEY
-}
-
-// The geometry of a multi launch: pick_mx4_cfg's choice for the shape (results do not depend on it); WS stays launch_gemv_mx4's
-// function of K, which the order of a row's sum does depend on.  Only the ten instantiations a default launch selects are built
-// (DESIGN.md §2.12 has their register figures; 8 rows per wave at WS = 1 would need more than wave 0's 64 finishing lanes).  A
-// CC_GEMV_MX4_CFG that names another geometry launch_gemv_mx4 serves runs the shape's DEFAULT geometry here, with the hook's cap on
-// the grid: the same bits, and the same CC_ERR_UNSUPPORTED cases as the single-vector entry point under that setting.
-template <int NT>
-static int launch_gemv_mx4_multi(const GemvMx4Args& a, hipStream_t st) {
-  const int nseg = (a.K / 32 + 63) / 64;
-  const int ws = nseg >= 3 ? 4 : nseg;
-  const int nstep = (nseg + ws - 1) / ws;
-  Mx4Cfg c = pick_mx4_cfg(a, nstep);
-  const int xs = nstep <= 1 ? 1 : nstep <= 2 ? 2 : 4;
-  if (nstep > 4 || c.cu > xs || c.cap <= 0) return CC_ERR_UNSUPPORTED;
-  if (!mx4_single_serves((a.W3 ? 100000 : 0) + ws * 10000 + xs * 1000 + c.rb * 10 + c.cu)) return CC_ERR_UNSUPPORTED;
-  if (nstep <= 1) {  // the default geometry of the shape class (pick_mx4_cfg without the tuning hook)
-    c.rb = 4; c.cu = 1;
+  const size_t lds = a.norm_w != nullptr ? (size_t)a.K * sizeof(bf16_t) : 0;  // one staging buffer, whatever NT
+  if constexpr (NT == 1) {
+    hipLaunchKernelGGL((gemv_mx4_kernel<SWIGLU, RB, CU, XS, WS>), dim3(blocks), dim3(kMx4Threads), lds, st, a);
   } else {
-    c.rb = a.W3 != nullptr ? 2 : 4; c.cu = 2;
+    hipLaunchKernelGGL((gemv_mx4_multi_kernel<SWIGLU, RB, CU, XS, WS, NT>), dim3(blocks), dim3(kMx4Threads), lds, st, a);
   }
+}
+template <bool SWIGLU, int RB, int CU, int XS, int WS, int NT>
+static void launch_mx4_cfg(const GemvMx4Args& a, hipStream_t st, int cap) {
+  if constexpr (NT == 1) {
+    launch_mx4_geo<SWIGLU, RB, CU, XS, WS, 1>(a, st, cap);
+  } else {
+    launch_mx4_geo<SWIGLU, XS == 1 ? 4 : SWIGLU ? 2 : 4, XS == 1 ? 1 : 2, XS, WS, NT>(a, st, cap);
+  }
+}
+
+// (the same CC_ERR_UNSUPPORTED cases for every NT: a CC_GEMV_MX4_CFG must name a geometry of this table)
+template <int NT>
+static int launch_gemv_mx4(const GemvMx4Args& a, hipStream_t st) {
+  const int nseg = (a.K / 32 + 63) / 64;
+  const int ws = nseg >= 3 ? 4 : nseg;  // waves per row: a short row leaves no wave idle
+  const int nstep = (nseg + ws - 1) / ws;
+  const Mx4Cfg c = pick_mx4_cfg(a, nstep);
+  const int xs = nstep <= 1 ? 1 : nstep <= 2 ? 2 : 4;  // input chunks kept per lane
+  if (nstep > 4 || c.cu > xs || c.cap <= 0) return CC_ERR_UNSUPPORTED;
   const int key = (a.W3 ? 100000 : 0) + ws * 10000 + xs * 1000 + c.rb * 10 + c.cu;
-#define MX4M_CASE(SW, WS_, XS_, RB_, CU_) \
-  case (SW ? 100000 : 0) + WS_ * 10000 + XS_ * 1000 + RB_ * 10 + CU_: launch_mx4_multi_cfg<SW, RB_, CU_, XS_, WS_, NT>(a, st, c.cap); break;
+#define MX4_CASE(SW, WS_, XS_, RB_, CU_) \
+  case (SW ? 100000 : 0) + WS_ * 10000 + XS_ * 1000 + RB_ * 10 + CU_: launch_mx4_cfg<SW, RB_, CU_, XS_, WS_, NT>(a, st, c.cap); break;
   switch (key) {
-    MX4M_CASE(false, 1, 1, 4, 1) MX4M_CASE(false, 2, 1, 4, 1) MX4M_CASE(false, 4, 1, 4, 1) MX4M_CASE(false, 4, 2, 4, 2) MX4M_CASE(false, 4, 4, 4, 2)
-    MX4M_CASE(true, 1, 1, 4, 1) MX4M_CASE(true, 2, 1, 4, 1) MX4M_CASE(true, 4, 1, 4, 1) MX4M_CASE(true, 4, 2, 2, 2) MX4M_CASE(true, 4, 4, 2, 2)
+    MX4_CASE(false, 1, 1, 2, 1) MX4_CASE(false, 1, 1, 4, 1) MX4_CASE(false, 1, 1, 8, 1)
+    MX4_CASE(false, 2, 1, 2, 1) MX4_CASE(false, 2, 1, 4, 1) MX4_CASE(false, 2, 1, 8, 1)
+    MX4_CASE(false, 4, 1, 2, 1) MX4_CASE(false, 4, 1, 4, 1) MX4_CASE(false, 4, 1, 8, 1)
+    MX4_CASE(false, 4, 2, 4, 1) MX4_CASE(false, 4, 2, 8, 1) MX4_CASE(false, 4, 2, 2, 2) MX4_CASE(false, 4, 2, 4, 2) MX4_CASE(false, 4, 2, 8, 2)
+    MX4_CASE(false, 4, 4, 2, 4) MX4_CASE(false, 4, 4, 4, 2) MX4_CASE(false, 4, 4, 8, 2) MX4_CASE(false, 4, 4, 4, 4)
+    MX4_CASE(true, 1, 1, 2, 1) MX4_CASE(true, 1, 1, 4, 1) MX4_CASE(true, 1, 1, 8, 1)
+    MX4_CASE(true, 2, 1, 2, 1) MX4_CASE(true, 2, 1, 4, 1) MX4_CASE(true, 2, 1, 8, 1)
+    MX4_CASE(true, 4, 1, 2, 1) MX4_CASE(true, 4, 1, 4, 1) MX4_CASE(true, 4, 1, 8, 1)
+    MX4_CASE(true, 4, 2, 2, 1) MX4_CASE(true, 4, 2, 4, 1) MX4_CASE(true, 4, 2, 2, 2) MX4_CASE(true, 4, 2, 4, 2)
+    MX4_CASE(true, 4, 4, 2, 2) MX4_CASE(true, 4, 4, 4, 2) MX4_CASE(true, 4, 4, 2, 4)
     default: return CC_ERR_UNSUPPORTED;
   }
-#undef MX4M_CASE
+#undef MX4_CASE
   CC_LAUNCH_CHECK();
   return CC_OK;
 }
 
-static int launch_gemv_mx4_multi_t(const GemvMx4Args& a, int nt, hipStream_t st) {
+static int launch_gemv_mx4_t(const GemvMx4Args& a, int nt, hipStream_t st) {
   switch (nt) {
-    case 1: return launch_gemv_mx4(a, st);  // one token: the single-vector kernel itself
-    case 2: return launch_gemv_mx4_multi<2>(a, st);
-    case 3: return launch_gemv_mx4_multi<3>(a, st);
-    default: return launch_gemv_mx4_multi<4>(a, st);
+    case 1: return launch_gemv_mx4<1>(a, st);  // one token: the single-vector kernel itself
+    case 2: return launch_gemv_mx4<2>(a, st);
+    case 3: return launch_gemv_mx4<3>(a, st);
+    default: return launch_gemv_mx4<4>(a, st);
   }
 }
 
 }  // namespace
+
+static inline bool mx4_aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+static int gemv_fused_mx4_entry(const uint8_t* W, const uint8_t* scales, const uint8_t* W3, const uint8_t* scales3, const void* x,
+                                const void* delta, const void* norm_w, float eps, void* h_out, const void* bias, const void* freqs,
+                                int32_t rope_rows, int32_t head_dim, void* y, int32_t N, int32_t K, int32_t T, int32_t dtype,
+                                cc_stream_t stream) {
+  if (!scales || (W3 != nullptr) != (scales3 != nullptr)) return CC_ERR_BAD_ARG;
+  // 16-byte vector accesses to the codes, the input vector and the prologue's operands; 2-byte elements elsewhere (null: aligned).
+  // (row t of x / delta / h_out starts K * 2 bytes behind row t - 1: K % 32 == 0 keeps every row as aligned as the first)
+  if (!mx4_aligned(W, 16) || !mx4_aligned(W3, 16) || !mx4_aligned(x, 16) || !mx4_aligned(delta, 16) || !mx4_aligned(norm_w, 16) ||
+      !mx4_aligned(h_out, 16) || !mx4_aligned(bias, 2) || !mx4_aligned(freqs, 2) || !mx4_aligned(y, 2))
+    return CC_ERR_BAD_ARG;
+  if (const int rc = gv_check_args(W, W3, x, delta, norm_w, h_out, bias, freqs, rope_rows, head_dim, y, N, K, T, dtype)) return rc;
+  if (dtype != CC_DT_BF16) return CC_ERR_UNSUPPORTED;  // bf16 models only
+  if (K % 32) return CC_ERR_UNSUPPORTED;               // whole MX blocks
+  GemvMx4Args a{W, W3, scales, scales3, x, delta, norm_w, bias, freqs, h_out, y, eps, N, K, freqs ? rope_rows : 0, freqs ? head_dim : 2};
+  return launch_gemv_mx4_t(a, T, (hipStream_t)stream);
+}
+
+extern "C" int cc_gemv_fused_mx4(const uint8_t* W, const uint8_t* scales, const uint8_t* W3, const uint8_t* scales3, const void* x,
+                                 const void* delta, const void* norm_w, float eps, void* h_out, const void* bias, const void* freqs,
+                                 int32_t rope_rows, int32_t head_dim, void* y, int32_t N, int32_t K, int32_t dtype, cc_stream_t stream) {
+  CC_ENTRY();
+  return gemv_fused_mx4_entry(W, scales, W3, scales3, x, delta, norm_w, eps, h_out, bias, freqs, rope_rows, head_dim, y, N, K, 1, dtype, stream);
+}
 
 extern "C" int cc_gemv_fused_mx4_multi(const uint8_t* W, const uint8_t* scales, const uint8_t* W3, const uint8_t* scales3, const void* x,
                                        const void* delta, const void* norm_w, float eps, void* h_out, const void* bias, const void* freqs,
                                        int32_t rope_rows, int32_t head_dim, void* y, int32_t N, int32_t K, int32_t T, int32_t dtype,
                                        cc_stream_t stream) {
   CC_ENTRY();
-  if (!W || !scales || !x || !y || N <= 0 || K <= 0 || !cc_dt_ok(dtype)) return CC_ERR_BAD_ARG;
-  if (T < 1 || T > CC_GEMV_MULTI_MAX_T) return CC_ERR_BAD_ARG;
-  if ((W3 != nullptr) != (scales3 != nullptr)) return CC_ERR_BAD_ARG;
-  if ((delta || h_out) && !norm_w) return CC_ERR_BAD_ARG;
-  if (freqs && (W3 || rope_rows < 0 || rope_rows > N || head_dim <= 0 || (head_dim & 1) || (rope_rows % head_dim))) return CC_ERR_BAD_ARG;
-  if (W3 && bias) return CC_ERR_BAD_ARG;
-  // (row t of x / delta / h_out starts K * 2 bytes behind row t - 1: K % 32 == 0 keeps every row as aligned as the first)
-  if (!mx4_aligned(W, 16) || !mx4_aligned(W3, 16) || !mx4_aligned(x, 16) || !mx4_aligned(delta, 16) || !mx4_aligned(norm_w, 16) ||
-      !mx4_aligned(h_out, 16) || !mx4_aligned(bias, 2) || !mx4_aligned(freqs, 2) || !mx4_aligned(y, 2))
-    return CC_ERR_BAD_ARG;
-  if (dtype != CC_DT_BF16) return CC_ERR_UNSUPPORTED;  // bf16 models only
-  if (K % 32) return CC_ERR_UNSUPPORTED;               // whole MX blocks
-  if ((size_t)K * sizeof(bf16_t) > 64 * 1024) return CC_ERR_UNSUPPORTED;
-  GemvMx4Args a{W, W3, scales, scales3, x, delta, norm_w, bias, freqs, h_out, y, eps, N, K, freqs ? rope_rows : 0, freqs ? head_dim : 2};
-  return launch_gemv_mx4_multi_t(a, T, (hipStream_t)stream);
+  return gemv_fused_mx4_entry(W, scales, W3, scales3, x, delta, norm_w, eps, h_out, bias, freqs, rope_rows, head_dim, y, N, K, T, dtype, stream);
 }

@@ -46,8 +46,6 @@ struct GemvW4Args {
 constexpr int kW4Threads = 256;
 constexpr int kW4Waves = kW4Threads / 64;
 
-__device__ __forceinline__ uint32_t nt_load_u32(const uint32_t* p) { return __builtin_nontemporal_load(p); }
-
 __device__ __forceinline__ float dot2_bf16(uint32_t a, uint32_t b, float acc) {
   return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, a), __builtin_bit_cast(bf16x2_t, b), acc, false);
 }
@@ -96,25 +94,7 @@ __global__ __launch_bounds__(kW4Threads) void gemv_w4_kernel(GemvW4Args a) {
   const uint4* W3v = reinterpret_cast<const uint4*>(a.W3);
   uint4 w[RB][CU], w3[RB][CU];
   uint32_t q[RB][CU], q3[RB][CU];
-  auto issue = [&](int r0, int s0) {  // r0: this wave's first row
-#pragma unroll
-    for (int u = 0; u < CU; u++) {
-      const int c = ((s0 + u) * WS + ws) * 64 + lane;
-      const bool cin = (s0 + u < nstep) && c < nch;
-#pragma unroll
-      for (int r = 0; r < RB; r++) {
-        const bool in = cin && (r0 + r < N);
-        const size_t off = (size_t)(r0 + r) * nch + c;
-        const size_t qoff = (size_t)(r0 + r) * ngr + (c >> a.gshift);
-        w[r][u] = in ? nt_load(Wv + off) : make_uint4(0, 0, 0, 0);
-        q[r][u] = in ? nt_load_u32(a.qp + qoff) : 0u;
-        if (SWIGLU) {
-          w3[r][u] = in ? nt_load(W3v + off) : make_uint4(0, 0, 0, 0);
-          q3[r][u] = in ? nt_load_u32(a.qp3 + qoff) : 0u;
-        }
-      }
-    }
-  };
+  auto issue = gv_scaled_tile<SWIGLU, WS, true, 0u>(w, w3, q, q3, Wv, W3v, a.qp, a.qp3, N, nch, nstep, lane, ws, ngr, a.gshift);
   const int row_first = blockIdx.x * RW;  // < N (the launcher sizes the grid)
   issue(row_first + rg * RB, 0);
 
@@ -339,16 +319,12 @@ extern "C" int cc_gemv_fused_w4(const uint8_t* W, const void* qparams, const uin
                                 int32_t rope_rows, int32_t head_dim, void* y, int32_t N, int32_t K, int32_t groupsize, int32_t dtype,
                                 cc_stream_t stream) {
   CC_ENTRY();
-  if (!W || !qparams || !x || !y || N <= 0 || K <= 0 || !cc_dt_ok(dtype)) return CC_ERR_BAD_ARG;
-  if ((W3 != nullptr) != (qparams3 != nullptr)) return CC_ERR_BAD_ARG;
-  if ((delta || h_out) && !norm_w) return CC_ERR_BAD_ARG;
-  if (freqs && (W3 || rope_rows < 0 || rope_rows > N || head_dim <= 0 || (head_dim & 1) || (rope_rows % head_dim))) return CC_ERR_BAD_ARG;
-  if (W3 && bias) return CC_ERR_BAD_ARG;
+  if (!qparams || (W3 != nullptr) != (qparams3 != nullptr)) return CC_ERR_BAD_ARG;
   const int gshift = groupsize == 32 ? 0 : groupsize == 64 ? 1 : groupsize == 128 ? 2 : groupsize == 256 ? 3 : -1;
   if (gshift < 0) return CC_ERR_BAD_ARG;
+  if (const int rc = gv_check_args(W, W3, x, delta, norm_w, h_out, bias, freqs, rope_rows, head_dim, y, N, K, 1, dtype)) return rc;
   if (dtype != CC_DT_BF16) return CC_ERR_UNSUPPORTED;  // bf16 models only (the reference's int4 kernel is bf16-only)
   if (K % groupsize) return CC_ERR_UNSUPPORTED;
-  if ((size_t)K * sizeof(bf16_t) > 64 * 1024) return CC_ERR_UNSUPPORTED;
   GemvW4Args a{W, W3, reinterpret_cast<const uint32_t*>(qparams), reinterpret_cast<const uint32_t*>(qparams3), x, delta, norm_w, bias,
                freqs, h_out, y, eps, N, K, gshift, freqs ? rope_rows : 0, freqs ? head_dim : 2};
   return launch_gemv_w4(a, (hipStream_t)stream);

@@ -15,9 +15,12 @@
 // chains and the same LDS reduction): h_out and the normalised input are bit-identical to cc_gemv_fused's.  The normalised vector
 // is passed to the lanes that multiply it through LDS (K * 2 bytes, norm forms only).
 //
-// TWO COPIES: gemv_w8_multi_kernel at the end of this file (the same product for up to four input vectors) repeats gemv_w8_kernel's weight tile,
-// prologue, row loop and epilogue, token by token, and promises the same bits.  A change to the chunk ownership, a chain's order, a
-// reduction or a rounding point here has to be made there too (tests/test_gpu_gemv_wo_multi.py compares the two bit for bit).
+// TWO COPIES: gemv_w8_multi_kernel further down (the same product for up to four input vectors) repeats gemv_w8_kernel's prologue,
+// row loop and epilogue, token by token, and promises the same bits; the weight tile, and with it the chunk ownership, is ONE function
+// for both (gv_plain_tile, cc_gemv_core.h, shared with the dense kernels).  A change to a chain's order, a reduction or a rounding
+// point here has to be made there too (tests/test_gpu_gemv_wo_multi.py compares the two bit for bit).  The copies stay because
+// moving those steps into shared functions changes the single-vector kernels' machine code.  Launcher, switch table
+// and argument checks exist once, for every token count (NT = 1: the single-vector kernel).
 #include <cstdio>
 #include <cstdlib>
 
@@ -96,20 +99,7 @@ __global__ __launch_bounds__(kW8Threads) void gemv_w8_kernel(GemvW8Args a) {
   const uint4* Wv = reinterpret_cast<const uint4*>(a.W);
   const uint4* W3v = reinterpret_cast<const uint4*>(a.W3);
   uint4 w[RB][CU], w3[RB][CU];
-  auto issue = [&](int r0, int s0) {
-#pragma unroll
-    for (int u = 0; u < CU; u++) {
-      const int c = ((s0 + u) * kW8Waves + wave) * 64 + lane;
-      const bool cin = (s0 + u < nstep) && c < nch;
-#pragma unroll
-      for (int r = 0; r < RB; r++) {
-        const bool in = cin && (r0 + r < N);
-        const size_t off = (size_t)(r0 + r) * nch + c;
-        w[r][u] = in ? nt_load(Wv + off) : make_uint4(0, 0, 0, 0);
-        if (SWIGLU) w3[r][u] = in ? nt_load(W3v + off) : make_uint4(0, 0, 0, 0);
-      }
-    }
-  };
+  auto issue = gv_plain_tile<SWIGLU>(w, w3, Wv, W3v, N, nch, nstep, lane, wave);
   const int row_first = blockIdx.x * RB;
   if (row_first < N) issue(row_first, 0);
 
@@ -275,61 +265,6 @@ static W8Cfg pick_w8_cfg(const GemvW8Args& a, int nstep) {
   return a.W3 != nullptr ? W8Cfg{2, 2, 2048} : W8Cfg{4, 2, 512};
 }
 
-template <typename T, bool SWIGLU, int RB, int CU, int XS>
-static void launch_w8_cfg(const GemvW8Args& a, hipStream_t st, int cap) {
-  int blocks = (a.N + RB - 1) / RB;
-  if (blocks > cap) blocks = cap;
-  const size_t lds = a.norm_w != nullptr ? (size_t)a.K * sizeof(T) : 0;
-  hipLaunchKernelGGL((gemv_w8_kernel<T, SWIGLU, RB, CU, XS>), dim3(blocks), dim3(kW8Threads), lds, st, a);
-}
-
-template <typename T>
-static int launch_gemv_w8(const GemvW8Args& a, hipStream_t st) {
-  const int nseg = (a.K / 16 + 63) / 64, nstep = (nseg + kW8Waves - 1) / kW8Waves;
-  const W8Cfg c = pick_w8_cfg(a, nstep);
-  const int xs = nstep <= 1 ? 1 : nstep <= 2 ? 2 : nstep <= 4 ? 4 : 8;  // input chunk pairs kept per lane
-  if (nstep > 8 || c.cu > xs || c.cap <= 0) return CC_ERR_UNSUPPORTED;
-  const int key = (a.W3 ? 100000 : 0) + xs * 1000 + c.rb * 10 + c.cu;
-  switch (key) {
-    case 1041: launch_w8_cfg<T, false, 4, 1, 1>(a, st, c.cap); break;
-    case 1081: launch_w8_cfg<T, false, 8, 1, 1>(a, st, c.cap); break;
-    case 2042: launch_w8_cfg<T, false, 4, 2, 2>(a, st, c.cap); break;
-    case 4024: launch_w8_cfg<T, false, 2, 4, 4>(a, st, c.cap); break;
-    case 4042: launch_w8_cfg<T, false, 4, 2, 4>(a, st, c.cap); break;
-    case 4044: launch_w8_cfg<T, false, 4, 4, 4>(a, st, c.cap); break;
-    case 4082: launch_w8_cfg<T, false, 8, 2, 4>(a, st, c.cap); break;
-    case 8042: launch_w8_cfg<T, false, 4, 2, 8>(a, st, c.cap); break;
-    case 101021: launch_w8_cfg<T, true, 2, 1, 1>(a, st, c.cap); break;
-    case 101041: launch_w8_cfg<T, true, 4, 1, 1>(a, st, c.cap); break;
-    case 101081: launch_w8_cfg<T, true, 8, 1, 1>(a, st, c.cap); break;
-    case 102022: launch_w8_cfg<T, true, 2, 2, 2>(a, st, c.cap); break;
-    case 104024: launch_w8_cfg<T, true, 2, 4, 4>(a, st, c.cap); break;
-    case 108022: launch_w8_cfg<T, true, 2, 2, 8>(a, st, c.cap); break;
-    default: return CC_ERR_UNSUPPORTED;
-  }
-  CC_LAUNCH_CHECK();
-  return CC_OK;
-}
-
-}  // namespace
-
-extern "C" int cc_gemv_fused_w8(const int8_t* W, const void* scales, const int8_t* W3, const void* scales3, const void* x,
-                                const void* delta, const void* norm_w, float eps, void* h_out, const void* bias, const void* freqs,
-                                int32_t rope_rows, int32_t head_dim, void* y, int32_t N, int32_t K, int32_t dtype, cc_stream_t stream) {
-  CC_ENTRY();
-  if (!W || !scales || !x || !y || N <= 0 || K <= 0 || !cc_dt_ok(dtype)) return CC_ERR_BAD_ARG;
-  if ((W3 != nullptr) != (scales3 != nullptr)) return CC_ERR_BAD_ARG;
-  if ((delta || h_out) && !norm_w) return CC_ERR_BAD_ARG;
-  if (freqs && (W3 || rope_rows < 0 || rope_rows > N || head_dim <= 0 || (head_dim & 1) || (rope_rows % head_dim))) return CC_ERR_BAD_ARG;
-  if (W3 && bias) return CC_ERR_BAD_ARG;
-  if (dtype == CC_DT_F32) return CC_ERR_UNSUPPORTED;  // 16-bit activations only
-  if (K % 16) return CC_ERR_UNSUPPORTED;
-  if ((size_t)K * cc_dt_size(dtype) > 64 * 1024) return CC_ERR_UNSUPPORTED;
-  GemvW8Args a{W, W3, scales, scales3, x, delta, norm_w, bias, freqs, h_out, y, eps, N, K, freqs ? rope_rows : 0, freqs ? head_dim : 2};
-  hipStream_t st = (hipStream_t)stream;
-  return dtype == CC_DT_BF16 ? launch_gemv_w8<bf16_t>(a, st) : launch_gemv_w8<f16_t>(a, st);
-}
-
 // ---- the same product for NT input vectors from ONE pass over the int8 weights (cc_gemv_fused_w8_multi): cc_gemv.hip's
 //      gemv_multi_kernel for this file's kernel.  Row t of y / h_out is BIT-IDENTICAL to gemv_w8_kernel on row t of x / delta / freqs:
 //      the lane that owns a 16-byte weight chunk, the order of that lane's dot2 chain, gv_wave_sum, the four-wave meet
@@ -342,8 +277,6 @@ extern "C" int cc_gemv_fused_w8(const int8_t* W, const void* scales, const int8_
 //      sum of squares are formed first, in the 16-bit kernel's chunk layout, with h parked in the registers that will hold the token's
 //      input (2 * XS uint4, the same count); then the tokens pass through the buffer one after the other — normalise token t into it,
 //      barrier, every lane picks up the 32-byte pieces it multiplies, barrier, the next token.
-namespace {
-
 template <typename T>
 struct DeqW8;  // one code word -> the two packed pairs DotW8<T>::word multiplies, and that multiply
 template <>
@@ -406,20 +339,7 @@ __global__ __launch_bounds__(kW8Threads) void gemv_w8_multi_kernel(GemvW8Args a)
   const uint4* Wv = reinterpret_cast<const uint4*>(a.W);
   const uint4* W3v = reinterpret_cast<const uint4*>(a.W3);
   uint4 w[RB][CU], w3[RB][CU];
-  auto issue = [&](int r0, int s0) {
-#pragma unroll
-    for (int u = 0; u < CU; u++) {
-      const int c = ((s0 + u) * kW8Waves + wave) * 64 + lane;
-      const bool cin = (s0 + u < nstep) && c < nch;
-#pragma unroll
-      for (int r = 0; r < RB; r++) {
-        const bool in = cin && (r0 + r < N);
-        const size_t off = (size_t)(r0 + r) * nch + c;
-        w[r][u] = in ? nt_load(Wv + off) : make_uint4(0, 0, 0, 0);
-        if (SWIGLU) w3[r][u] = in ? nt_load(W3v + off) : make_uint4(0, 0, 0, 0);
-      }
-    }
-  };
+  auto issue = gv_plain_tile<SWIGLU>(w, w3, Wv, W3v, N, nch, nstep, lane, wave);
   const int row_first = blockIdx.x * RB;
   if (row_first < N) issue(row_first, 0);
 
@@ -594,38 +514,42 @@ __global__ __launch_bounds__(kW8Threads) void gemv_w8_multi_kernel(GemvW8Args a)
   }
 }
 
-// The geometry of a multi launch: pick_w8_cfg's choice for the shape (results do not depend on it).  DESIGN.md §2.12 has the register
-// figures of every instantiation: none of them needs fewer rows or column steps in flight.
+// The geometry of a multi launch is pick_w8_cfg's choice for the shape too (results do not depend on it).  DESIGN.md §2.12 has the
+// register figures of every instantiation: none of them needs fewer rows or column steps in flight.
 template <typename T, bool SWIGLU, int RB, int CU, int XS, int NT>
-static void launch_w8_multi_cfg(const GemvW8Args& a, hipStream_t st, int cap) {
+static void launch_w8_cfg(const GemvW8Args& a, hipStream_t st, int cap) {
   int blocks = (a.N + RB - 1) / RB;
   if (blocks > cap) blocks = cap;
-  const size_t lds = a.norm_w != nullptr ? (size_t)a.K * sizeof(T) : 0;  // the single kernel's: one staging buffer for the NT tokens
-  hipLaunchKernelGGL((gemv_w8_multi_kernel<T, SWIGLU, RB, CU, XS, NT>), dim3(blocks), dim3(kW8Threads), lds, st, a);
+  const size_t lds = a.norm_w != nullptr ? (size_t)a.K * sizeof(T) : 0;  // one staging buffer, whatever NT
+  if constexpr (NT == 1) {
+    hipLaunchKernelGGL((gemv_w8_kernel<T, SWIGLU, RB, CU, XS>), dim3(blocks), dim3(kW8Threads), lds, st, a);
+  } else {
+    hipLaunchKernelGGL((gemv_w8_multi_kernel<T, SWIGLU, RB, CU, XS, NT>), dim3(blocks), dim3(kW8Threads), lds, st, a);
+  }
 }
 
 template <typename T, int NT>
-static int launch_gemv_w8_multi(const GemvW8Args& a, hipStream_t st) {
+static int launch_gemv_w8(const GemvW8Args& a, hipStream_t st) {
   const int nseg = (a.K / 16 + 63) / 64, nstep = (nseg + kW8Waves - 1) / kW8Waves;
   const W8Cfg c = pick_w8_cfg(a, nstep);
-  const int xs = nstep <= 1 ? 1 : nstep <= 2 ? 2 : nstep <= 4 ? 4 : 8;
+  const int xs = nstep <= 1 ? 1 : nstep <= 2 ? 2 : nstep <= 4 ? 4 : 8;  // input chunk pairs kept per lane
   if (nstep > 8 || c.cu > xs || c.cap <= 0) return CC_ERR_UNSUPPORTED;
   const int key = (a.W3 ? 100000 : 0) + xs * 1000 + c.rb * 10 + c.cu;
-  switch (key) {  // launch_gemv_w8's instantiations
-    case 1041: launch_w8_multi_cfg<T, false, 4, 1, 1, NT>(a, st, c.cap); break;
-    case 1081: launch_w8_multi_cfg<T, false, 8, 1, 1, NT>(a, st, c.cap); break;
-    case 2042: launch_w8_multi_cfg<T, false, 4, 2, 2, NT>(a, st, c.cap); break;
-    case 4024: launch_w8_multi_cfg<T, false, 2, 4, 4, NT>(a, st, c.cap); break;
-    case 4042: launch_w8_multi_cfg<T, false, 4, 2, 4, NT>(a, st, c.cap); break;
-    case 4044: launch_w8_multi_cfg<T, false, 4, 4, 4, NT>(a, st, c.cap); break;
-    case 4082: launch_w8_multi_cfg<T, false, 8, 2, 4, NT>(a, st, c.cap); break;
-    case 8042: launch_w8_multi_cfg<T, false, 4, 2, 8, NT>(a, st, c.cap); break;
-    case 101021: launch_w8_multi_cfg<T, true, 2, 1, 1, NT>(a, st, c.cap); break;
-    case 101041: launch_w8_multi_cfg<T, true, 4, 1, 1, NT>(a, st, c.cap); break;
-    case 101081: launch_w8_multi_cfg<T, true, 8, 1, 1, NT>(a, st, c.cap); break;
-    case 102022: launch_w8_multi_cfg<T, true, 2, 2, 2, NT>(a, st, c.cap); break;
-    case 104024: launch_w8_multi_cfg<T, true, 2, 4, 4, NT>(a, st, c.cap); break;
-    case 108022: launch_w8_multi_cfg<T, true, 2, 2, 8, NT>(a, st, c.cap); break;
+  switch (key) {
+    case 1041: launch_w8_cfg<T, false, 4, 1, 1, NT>(a, st, c.cap); break;
+    case 1081: launch_w8_cfg<T, false, 8, 1, 1, NT>(a, st, c.cap); break;
+    case 2042: launch_w8_cfg<T, false, 4, 2, 2, NT>(a, st, c.cap); break;
+    case 4024: launch_w8_cfg<T, false, 2, 4, 4, NT>(a, st, c.cap); break;
+    case 4042: launch_w8_cfg<T, false, 4, 2, 4, NT>(a, st, c.cap); break;
+    case 4044: launch_w8_cfg<T, false, 4, 4, 4, NT>(a, st, c.cap); break;
+    case 4082: launch_w8_cfg<T, false, 8, 2, 4, NT>(a, st, c.cap); break;
+    case 8042: launch_w8_cfg<T, false, 4, 2, 8, NT>(a, st, c.cap); break;
+    case 101021: launch_w8_cfg<T, true, 2, 1, 1, NT>(a, st, c.cap); break;
+    case 101041: launch_w8_cfg<T, true, 4, 1, 1, NT>(a, st, c.cap); break;
+    case 101081: launch_w8_cfg<T, true, 8, 1, 1, NT>(a, st, c.cap); break;
+    case 102022: launch_w8_cfg<T, true, 2, 2, 2, NT>(a, st, c.cap); break;
+    case 104024: launch_w8_cfg<T, true, 2, 4, 4, NT>(a, st, c.cap); break;
+    case 108022: launch_w8_cfg<T, true, 2, 2, 8, NT>(a, st, c.cap); break;
     default: return CC_ERR_UNSUPPORTED;
   }
   CC_LAUNCH_CHECK();
@@ -633,32 +557,40 @@ static int launch_gemv_w8_multi(const GemvW8Args& a, hipStream_t st) {
 }
 
 template <typename T>
-static int launch_gemv_w8_multi_t(const GemvW8Args& a, int nt, hipStream_t st) {
+static int launch_gemv_w8_t(const GemvW8Args& a, int nt, hipStream_t st) {
   switch (nt) {
-    case 1: return launch_gemv_w8<T>(a, st);  // one token: the single-vector kernel itself
-    case 2: return launch_gemv_w8_multi<T, 2>(a, st);
-    case 3: return launch_gemv_w8_multi<T, 3>(a, st);
-    default: return launch_gemv_w8_multi<T, 4>(a, st);
+    case 1: return launch_gemv_w8<T, 1>(a, st);  // one token: the single-vector kernel itself
+    case 2: return launch_gemv_w8<T, 2>(a, st);
+    case 3: return launch_gemv_w8<T, 3>(a, st);
+    default: return launch_gemv_w8<T, 4>(a, st);
   }
 }
 
 }  // namespace
+
+static int gemv_fused_w8_entry(const int8_t* W, const void* scales, const int8_t* W3, const void* scales3, const void* x, const void* delta,
+                               const void* norm_w, float eps, void* h_out, const void* bias, const void* freqs, int32_t rope_rows,
+                               int32_t head_dim, void* y, int32_t N, int32_t K, int32_t T, int32_t dtype, cc_stream_t stream) {
+  if (!scales || (W3 != nullptr) != (scales3 != nullptr)) return CC_ERR_BAD_ARG;
+  if (const int rc = gv_check_args(W, W3, x, delta, norm_w, h_out, bias, freqs, rope_rows, head_dim, y, N, K, T, dtype)) return rc;
+  if (dtype == CC_DT_F32) return CC_ERR_UNSUPPORTED;  // 16-bit activations only
+  if (K % 16) return CC_ERR_UNSUPPORTED;
+  GemvW8Args a{W, W3, scales, scales3, x, delta, norm_w, bias, freqs, h_out, y, eps, N, K, freqs ? rope_rows : 0, freqs ? head_dim : 2};
+  hipStream_t st = (hipStream_t)stream;
+  return dtype == CC_DT_BF16 ? launch_gemv_w8_t<bf16_t>(a, T, st) : launch_gemv_w8_t<f16_t>(a, T, st);
+}
+
+extern "C" int cc_gemv_fused_w8(const int8_t* W, const void* scales, const int8_t* W3, const void* scales3, const void* x,
+                                const void* delta, const void* norm_w, float eps, void* h_out, const void* bias, const void* freqs,
+                                int32_t rope_rows, int32_t head_dim, void* y, int32_t N, int32_t K, int32_t dtype, cc_stream_t stream) {
+  CC_ENTRY();
+  return gemv_fused_w8_entry(W, scales, W3, scales3, x, delta, norm_w, eps, h_out, bias, freqs, rope_rows, head_dim, y, N, K, 1, dtype, stream);
+}
 
 extern "C" int cc_gemv_fused_w8_multi(const int8_t* W, const void* scales, const int8_t* W3, const void* scales3, const void* x,
                                       const void* delta, const void* norm_w, float eps, void* h_out, const void* bias, const void* freqs,
                                       int32_t rope_rows, int32_t head_dim, void* y, int32_t N, int32_t K, int32_t T, int32_t dtype,
                                       cc_stream_t stream) {
   CC_ENTRY();
-  if (!W || !scales || !x || !y || N <= 0 || K <= 0 || !cc_dt_ok(dtype)) return CC_ERR_BAD_ARG;
-  if (T < 1 || T > CC_GEMV_MULTI_MAX_T) return CC_ERR_BAD_ARG;
-  if ((W3 != nullptr) != (scales3 != nullptr)) return CC_ERR_BAD_ARG;
-  if ((delta || h_out) && !norm_w) return CC_ERR_BAD_ARG;
-  if (freqs && (W3 || rope_rows < 0 || rope_rows > N || head_dim <= 0 || (head_dim & 1) || (rope_rows % head_dim))) return CC_ERR_BAD_ARG;
-  if (W3 && bias) return CC_ERR_BAD_ARG;
-  if (dtype == CC_DT_F32) return CC_ERR_UNSUPPORTED;  // 16-bit activations only
-  if (K % 16) return CC_ERR_UNSUPPORTED;
-  if ((size_t)K * cc_dt_size(dtype) > 64 * 1024) return CC_ERR_UNSUPPORTED;
-  GemvW8Args a{W, W3, scales, scales3, x, delta, norm_w, bias, freqs, h_out, y, eps, N, K, freqs ? rope_rows : 0, freqs ? head_dim : 2};
-  hipStream_t st = (hipStream_t)stream;
-  return dtype == CC_DT_BF16 ? launch_gemv_w8_multi_t<bf16_t>(a, T, st) : launch_gemv_w8_multi_t<f16_t>(a, T, st);
+  return gemv_fused_w8_entry(W, scales, W3, scales3, x, delta, norm_w, eps, h_out, bias, freqs, rope_rows, head_dim, y, N, K, T, dtype, stream);
 }
