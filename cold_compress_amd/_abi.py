@@ -72,6 +72,8 @@ SIGNATURES = {
     "cc_sample_nucleus": (C.c_int, [_vp, _i32, _i32, _f32, _i32, _f32, _f32, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "cc_logprob_rows_workspace_bytes": (_sz, []),
     "cc_logprob_rows": (C.c_int, [_vp, _i32, _i32, C.c_int64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "cc_logprob_topn_workspace_bytes": (_sz, []),
+    "cc_logprob_topn": (C.c_int, [_vp, _i32, _i32, C.c_int64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "cc_token_counts_add": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp]),
     "cc_logits_penalize": (C.c_int, [_vp, _vp, _i32, _i32, C.c_int64, _i32, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _vp, _vp]),
     "cc_gemv_fused": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
@@ -205,6 +207,7 @@ DEVICE_ONLY = {"cc_error_string", "cc_device_info", "cc_decode_step_single_launc
                "cc_sample_topk_workspace_bytes", "cc_sample_topk",  # sampling tail: its checker is the numpy twin of the contract (tests/sample_twin.py)
                "cc_sample_nucleus_workspace_bytes", "cc_sample_nucleus",  # top-p / min-p on the same tail: likewise (tests/sample_nucleus_twin.py)
                "cc_logprob_rows_workspace_bytes", "cc_logprob_rows",  # per-token log-probabilities: float64 torch.log_softmax and the fp32 twin of the contract (tests/logprob_twin.py)
+               "cc_logprob_topn_workspace_bytes", "cc_logprob_topn",  # the N best alternatives of a row: the float64 order and values (tests/logprob_topn_twin.py)
                "cc_token_counts_add", "cc_logits_penalize",  # token-history penalties: the fp32 torch twin of the contract (tests/penalty_twin.py)
                # the fused quantised cache's ring and hybrid steps: their checker is the same policy's 16-bit step on the dequantised values
                "cc_decode_step_heavy_hitter_ring_quant", "cc_decode_step_hybrid_quant_rc", "cc_decode_step_hybrid_quant_single_launch",

@@ -7,6 +7,13 @@
 //             arrives as one 16-byte load (the row's base is 16-byte aligned) or element by element (it is not): the same row gives the
 //             same bits at any alignment, alone or as row r of T.
 //   fold      T workgroups of one wave: M = max m_g, S = sum s_g * exp(m_g - M) in a fixed order, the counts, and the three results.
+// cc_logprob_topn adds the row's N best alternatives (N <= CC_LOGPROB_MAX_TOPN) to the same two launches.  Every non-NaN element has
+// a 64-bit key, (its value as an orderable pattern, +0 and -0 alike) << 32 | ~index: a larger key comes earlier in the contract's total
+// order and no two elements share one, so "the next in the order" is the largest key below the previous pick — no taken flags.
+//   partial   as above (the same code: the three results keep their bits), then N rounds leave the slice's N largest keys, 0 where
+//             the slice has no more, in the workspace: the whole top-N may sit in one slice.
+//   fold      as above, then one wave merges the 128 sorted lists through LDS in N rounds, and lanes 0..N-1 write (id, (x_id - M) - log S)
+//             with x_id read from the row itself, which is what the row's logprob is made of.
 #include "cc_common.h"
 
 namespace {
@@ -20,6 +27,11 @@ struct LpPart {
 };
 struct LpWs {  // caller-provided scratch (cc_logprob_rows_workspace_bytes); row r's launch writes part[r] before its fold reads it
   LpPart part[CC_LOGPROB_MAX_ROWS][kLpSlices];
+};
+typedef unsigned long long lp_key_t;
+struct LpTopWs {  // cc_logprob_topn_workspace_bytes: the partials, and per slice its N largest keys in descending order (0: no more)
+  LpWs lp;
+  lp_key_t cand[CC_LOGPROB_MAX_ROWS][kLpSlices][CC_LOGPROB_MAX_TOPN];
 };
 
 __device__ __forceinline__ void lp_slice(int V, int& lo, int& hi) {  // multiples of 8 elements: slice starts are 16 bytes apart
@@ -54,9 +66,43 @@ __device__ __forceinline__ void lp_group(const T* row, int base, int n, bool ali
 // exp(x - m) of libm grade; exactly 1 at the maximum itself, also where the maximum is infinite (inf - inf is NaN)
 __device__ __forceinline__ float lp_exp(float x, float m) { return x == m ? 1.0f : expf(__fsub_rn(x, m)); }
 
-template <typename T>
+// the place of element (x, i) in the total order as a key: larger x first (+0 and -0 alike), then lower i; 0 for a NaN (never listed).
+// The smallest key of a real element is -inf's, 0x007fffff << 32: 0 is free to mean "none".
+__device__ __forceinline__ lp_key_t lp_key(float x, int i) {
+  if (x != x) return 0ull;
+  unsigned int u = x == 0.f ? 0u : __float_as_uint(x);
+  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((lp_key_t)u << 32) | (lp_key_t)(0xffffffffu - (unsigned int)i);
+}
+__device__ __forceinline__ int lp_key_index(lp_key_t k) { return (int)(0xffffffffu - (unsigned int)(k & 0xffffffffull)); }
+__device__ __forceinline__ lp_key_t lp_key_max(lp_key_t a, lp_key_t b) { return a > b ? a : b; }
+// the key of another lane of the same row of 16 lanes, by a DPP move of each half (no trip through the LDS crossbar)
+template <int kCtrl>
+__device__ __forceinline__ lp_key_t lp_key_dpp(lp_key_t v) {
+  const unsigned int lo = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)(unsigned int)v, kCtrl, 0xf, 0xf, false);
+  const unsigned int hi = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)(unsigned int)(v >> 32), kCtrl, 0xf, 0xf, false);
+  return ((lp_key_t)hi << 32) | (lp_key_t)lo;
+}
+__device__ __forceinline__ lp_key_t lp_key_lane(lp_key_t v, int lane) {
+  const unsigned int lo = (unsigned int)__builtin_amdgcn_readlane((int)(unsigned int)v, lane);
+  const unsigned int hi = (unsigned int)__builtin_amdgcn_readlane((int)(unsigned int)(v >> 32), lane);
+  return ((lp_key_t)hi << 32) | (lp_key_t)lo;
+}
+// The wave's largest key, uniform; all 64 lanes must be active.  A round of the selection is one of these and little else, so it
+// stays off ds_bpermute: quad_perm [1,0,3,2] and [2,3,0,1] give every lane its quad's maximum, row_ror 4 and 8 its row's, and the
+// four rows meet through v_readlane.
+__device__ __forceinline__ lp_key_t wave_max_key(lp_key_t v) {
+  v = lp_key_max(v, lp_key_dpp<0xb1>(v));
+  v = lp_key_max(v, lp_key_dpp<0x4e>(v));
+  v = lp_key_max(v, lp_key_dpp<0x124>(v));
+  v = lp_key_max(v, lp_key_dpp<0x128>(v));
+  return lp_key_max(lp_key_max(lp_key_lane(v, 0), lp_key_lane(v, 16)), lp_key_max(lp_key_lane(v, 32), lp_key_lane(v, 48)));
+}
+
+// kTop: cc_logprob_topn's launch, which goes on to the slice's `topn` largest keys (tws); the LpPart is the same code either way
+template <typename T, bool kTop>
 __global__ __launch_bounds__(kLpThreads) void logprob_partial_kernel(const T* logits, int V, long long row_stride, const int32_t* targets,
-                                                                     const int32_t* fallback, LpWs* ws) {
+                                                                     const int32_t* fallback, LpWs* ws, int topn, LpTopWs* tws) {
   constexpr int N = Vec16<T>::N;
   __shared__ float s_f[kLpWaves];
   __shared__ unsigned int s_c[kLpWaves];
@@ -126,12 +172,50 @@ __global__ __launch_bounds__(kLpThreads) void logprob_partial_kernel(const T* lo
     p.pad = 0u;
     ws->part[r][blockIdx.x] = p;
   }
+  if constexpr (kTop) {
+    // round j: the largest key of the slice below round j - 1's pick.  The thread's first group waits in registers as keys;
+    // a further group (V > 128 * 256 * N) is read again
+    __shared__ lp_key_t s_k[2][kLpWaves];
+    lp_key_t kf[N];
+#pragma unroll
+    for (int e = 0; e < N; e++) {
+      const int i = lo + (int)threadIdx.x * N + e;
+      kf[e] = ((int)threadIdx.x < ngroups && i < hi) ? lp_key(first[e], i) : 0ull;
+    }
+    lp_key_t prev = ~0ull, mine = 0ull;
+    for (int j = 0; j < topn; j++) {
+      lp_key_t best = 0ull;
+#pragma unroll
+      for (int e = 0; e < N; e++)
+        if (kf[e] < prev) best = lp_key_max(best, kf[e]);
+      for (int g = threadIdx.x + kLpThreads; g < ngroups; g += kLpThreads) {
+        const int base = lo + g * N, n = min(N, hi - base);
+        float x[N];
+        lp_group<T>(row, base, n, aligned, x);
+#pragma unroll
+        for (int e = 0; e < N; e++) {
+          const lp_key_t k = e < n ? lp_key(x[e], base + e) : 0ull;
+          if (k < prev) best = lp_key_max(best, k);
+        }
+      }
+      best = wave_max_key(best);
+      if (lane == 0) s_k[j & 1][wave] = best;
+      __syncthreads();  // (two buffers: round j + 1's barrier stands between these reads and round j + 2's writes)
+      prev = lp_key_max(lp_key_max(s_k[j & 1][0], s_k[j & 1][1]), lp_key_max(s_k[j & 1][2], s_k[j & 1][3]));
+      if ((int)threadIdx.x == j) mine = prev;  // (0 once the slice is exhausted, and from then on)
+    }
+    // thread j kept round j's pick: one coalesced store behind the rounds
+    if ((int)threadIdx.x < topn) tws->cand[r][blockIdx.x][threadIdx.x] = mine;
+  }
 }
 
+// the fold of one row by one wave: lane 0 writes the three results (each may be NULL); M and log S are returned in every lane
+struct LpFolded {
+  float M, logS;
+};
 template <typename T>
-__global__ __launch_bounds__(CC_WAVE) void logprob_fold_kernel(const T* logits, int V, long long row_stride, const int32_t* targets,
-                                                               const int32_t* fallback, float* logprob, float* lse, int32_t* rank,
-                                                               const LpWs* ws) {
+__device__ __forceinline__ LpFolded lp_fold_row(const T* logits, int V, long long row_stride, const int32_t* targets, const int32_t* fallback,
+                                                float* logprob, float* lse, int32_t* rank, const LpWs* ws) {
   static_assert(kLpSlices == 2 * CC_WAVE, "lane l folds slices l and l + 64");
   const int lane = threadIdx.x, r = blockIdx.x;
   const LpPart a = ws->part[r][lane], b = ws->part[r][lane + CC_WAVE];
@@ -145,30 +229,104 @@ __global__ __launch_bounds__(CC_WAVE) void logprob_fold_kernel(const T* logits, 
     S = __fadd_rn(S, __shfl_xor(S, off, CC_WAVE));
     above += __shfl_xor(above, off, CC_WAVE);
   }
-  if (lane != 0) return;
+  LpFolded f;
+  f.M = M;
+  f.logS = logf(S);  // (the butterfly leaves the same S in every lane)
+  if (lane != 0) return f;
   const float nan = __uint_as_float(0x7fc00000u);
-  const float logS = logf(S);
-  if (lse) lse[r] = __fadd_rn(M, logS);
+  if (lse) lse[r] = __fadd_rn(M, f.logS);
   const int t = lp_target(targets, fallback, r, V);
   float lp = nan;
   int32_t rk = -1;
   if (t >= 0) {
     const float xt = ElemTraits<T>::load(logits + (size_t)r * (size_t)row_stride, (size_t)t);
     // a +inf in the row: exp(inf - inf) makes the softmax's sum NaN, and with it every element's log-probability (torch.log_softmax)
-    if (M != INFINITY) lp = __fsub_rn(__fsub_rn(xt, M), logS);
+    if (M != INFINITY) lp = __fsub_rn(__fsub_rn(xt, M), f.logS);
     if (xt == xt) rk = (int32_t)above;
   }
-  logprob[r] = lp;
+  if (logprob) logprob[r] = lp;
   if (rank) rank[r] = rk;
+  return f;
+}
+
+template <typename T>
+__global__ __launch_bounds__(CC_WAVE) void logprob_fold_kernel(const T* logits, int V, long long row_stride, const int32_t* targets,
+                                                               const int32_t* fallback, float* logprob, float* lse, int32_t* rank,
+                                                               const LpWs* ws) {
+  lp_fold_row<T>(logits, V, row_stride, targets, fallback, logprob, lse, rank, ws);
+}
+
+// the fold, then the merge of the row's 128 sorted candidate lists: lane l holds the heads of slices l and l + 64; round j's winner is
+// the wave's largest head, and the lane that held it moves on in that list
+template <typename T>
+__global__ __launch_bounds__(CC_WAVE) void logprob_topn_fold_kernel(const T* logits, int V, long long row_stride, const int32_t* targets,
+                                                                    const int32_t* fallback, int topn, float* logprob, float* lse,
+                                                                    int32_t* rank, int32_t* top_ids, float* top_logprobs,
+                                                                    const LpTopWs* tws) {
+  __shared__ lp_key_t s_c[kLpSlices * CC_LOGPROB_MAX_TOPN];
+  const int lane = threadIdx.x, r = blockIdx.x;
+  // the lane's two lists, every load in flight before the first is waited for (a loop of load-then-store pays the whole latency
+  // of a global load per trip: 40 trips at N = 20), then into LDS, where the merge can index them
+  lp_key_t ra[CC_LOGPROB_MAX_TOPN], rb[CC_LOGPROB_MAX_TOPN];
+#pragma unroll
+  for (int j = 0; j < CC_LOGPROB_MAX_TOPN; j++) {
+    ra[j] = j < topn ? tws->cand[r][lane][j] : 0ull;
+    rb[j] = j < topn ? tws->cand[r][lane + CC_WAVE][j] : 0ull;
+  }
+  const LpFolded f = lp_fold_row<T>(logits, V, row_stride, targets, fallback, logprob, lse, rank, &tws->lp);
+  lp_key_t* la = s_c + lane * topn;
+  lp_key_t* lb = s_c + (lane + CC_WAVE) * topn;
+#pragma unroll
+  for (int j = 0; j < CC_LOGPROB_MAX_TOPN; j++)
+    if (j < topn) {
+      la[j] = ra[j];
+      lb[j] = rb[j];
+    }
+  __syncthreads();
+  int pa = 0, pb = 0;
+  lp_key_t ka = la[0], kb = lb[0], mine = 0ull;
+  for (int j = 0; j < topn; j++) {
+    const lp_key_t w = wave_max_key(lp_key_max(ka, kb));
+    if (lane == j) mine = w;
+    if (w == 0ull) break;  // (uniform: fewer than N non-NaN elements in the row)
+    if (ka == w) {
+      pa++;
+      ka = pa < topn ? la[pa] : 0ull;
+    } else if (kb == w) {
+      pb++;
+      kb = pb < topn ? lb[pb] : 0ull;
+    }
+  }
+  if (lane >= topn) return;
+  int32_t id = -1;
+  float lp = __uint_as_float(0x7fc00000u);
+  if (mine != 0ull) {
+    id = lp_key_index(mine);
+    const float x = ElemTraits<T>::load(logits + (size_t)r * (size_t)row_stride, (size_t)id);
+    if (f.M != INFINITY) lp = __fsub_rn(__fsub_rn(x, f.M), f.logS);
+  }
+  top_ids[(size_t)r * topn + lane] = id;
+  top_logprobs[(size_t)r * topn + lane] = lp;
 }
 
 template <typename T>
 void lp_launch(const void* logits_, int T_rows, int V, long long row_stride, const int32_t* targets, const int32_t* fallback, float* logprob,
                float* lse, int32_t* rank, LpWs* ws, hipStream_t st) {
   const T* logits = (const T*)logits_;
-  hipLaunchKernelGGL(logprob_partial_kernel<T>, dim3(kLpSlices, T_rows), dim3(kLpThreads), 0, st, logits, V, row_stride, targets, fallback, ws);
+  hipLaunchKernelGGL((logprob_partial_kernel<T, false>), dim3(kLpSlices, T_rows), dim3(kLpThreads), 0, st, logits, V, row_stride, targets, fallback, ws,
+                     0, (LpTopWs*)nullptr);
   hipLaunchKernelGGL(logprob_fold_kernel<T>, dim3(T_rows), dim3(CC_WAVE), 0, st, logits, V, row_stride, targets, fallback, logprob, lse, rank,
                      (const LpWs*)ws);
+}
+
+template <typename T>
+void lp_topn_launch(const void* logits_, int T_rows, int V, long long row_stride, const int32_t* targets, const int32_t* fallback, int topn,
+                    float* logprob, float* lse, int32_t* rank, int32_t* top_ids, float* top_logprobs, LpTopWs* tws, hipStream_t st) {
+  const T* logits = (const T*)logits_;
+  hipLaunchKernelGGL((logprob_partial_kernel<T, true>), dim3(kLpSlices, T_rows), dim3(kLpThreads), 0, st, logits, V, row_stride, targets, fallback,
+                     &tws->lp, topn, tws);
+  hipLaunchKernelGGL(logprob_topn_fold_kernel<T>, dim3(T_rows), dim3(CC_WAVE), 0, st, logits, V, row_stride, targets, fallback, topn, logprob, lse,
+                     rank, top_ids, top_logprobs, (const LpTopWs*)tws);
 }
 }  // namespace
 
@@ -188,6 +346,28 @@ extern "C" int cc_logprob_rows(const void* logits, int32_t T, int32_t V, int64_t
     case CC_DT_F32: lp_launch<float>(logits, T, V, row_stride, targets, fallback, logprob, lse, rank, ws, st); break;
     case CC_DT_BF16: lp_launch<bf16_t>(logits, T, V, row_stride, targets, fallback, logprob, lse, rank, ws, st); break;
     default: lp_launch<f16_t>(logits, T, V, row_stride, targets, fallback, logprob, lse, rank, ws, st); break;
+  }
+  CC_LAUNCH_CHECK();
+  return CC_OK;
+}
+
+extern "C" size_t cc_logprob_topn_workspace_bytes(void) { return sizeof(LpTopWs); }
+
+extern "C" int cc_logprob_topn(const void* logits, int32_t T, int32_t V, int64_t row_stride, int32_t dtype, const int32_t* targets,
+                               const int32_t* fallback, int32_t N, float* logprob, float* lse, int32_t* rank, int32_t* top_ids,
+                               float* top_logprobs, void* workspace, size_t workspace_bytes, cc_stream_t stream) {
+  CC_ENTRY();
+  if (!logits || !top_ids || !top_logprobs || !workspace || N < 1 || N > CC_LOGPROB_MAX_TOPN || T < 1 || T > CC_LOGPROB_MAX_ROWS || V < 1 ||
+      row_stride < (int64_t)V || !cc_dt_ok(dtype))
+    return CC_ERR_BAD_ARG;
+  if (workspace_bytes < sizeof(LpTopWs)) return CC_ERR_WORKSPACE;
+  if (((uintptr_t)workspace & 15u) != 0 || ((uintptr_t)logits & (cc_dt_size(dtype) - 1)) != 0) return CC_ERR_BAD_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  LpTopWs* tws = reinterpret_cast<LpTopWs*>(workspace);
+  switch (dtype) {
+    case CC_DT_F32: lp_topn_launch<float>(logits, T, V, row_stride, targets, fallback, N, logprob, lse, rank, top_ids, top_logprobs, tws, st); break;
+    case CC_DT_BF16: lp_topn_launch<bf16_t>(logits, T, V, row_stride, targets, fallback, N, logprob, lse, rank, top_ids, top_logprobs, tws, st); break;
+    default: lp_topn_launch<f16_t>(logits, T, V, row_stride, targets, fallback, N, logprob, lse, rank, top_ids, top_logprobs, tws, st); break;
   }
   CC_LAUNCH_CHECK();
   return CC_OK;

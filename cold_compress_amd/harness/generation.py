@@ -229,6 +229,87 @@ def token_logprobs(logits, targets, fallback=None):
     return logprob, rank.to(torch.int32)
 
 
+class TokenTopScores(NamedTuple):
+    """What `generate(..., logprobs=True, top_logprobs=n)` returns: TokenScores' two vectors, and per committed token the ids of the n
+    most likely tokens of the model's own row (int32 [tokens, n]: larger logit first, equal logits by lower id; -1 where the row has
+    fewer than n non-NaN logits) with their fp32 log-probabilities ([tokens, n]; NaN behind an id of -1)."""
+
+    logprob: torch.Tensor
+    rank: torch.Tensor
+    top_ids: torch.Tensor
+    top_logprobs: torch.Tensor
+
+
+MAX_TOP_LOGPROBS = 20  # (CC_LOGPROB_MAX_TOPN)
+
+
+def token_top_logprobs(logits, n, targets=None, fallback=None):
+    """token_logprobs' two results and each row's `n` most likely alternatives (include/coldcompress.h, cc_logprob_topn): the ids of
+    the n first elements in the order (larger logit first, equal logits by lower id, NaN never listed) and their log-probabilities,
+    padded with -1 / NaN.  `targets` and `fallback` both None: no target (NaN and -1), the alternatives alone.
+    -> (logprob [T] fp32, rank [T] int32, top_ids [T, n] int32, top_logprobs [T, n] fp32).  Device tensors run the kernel (T <= 64);
+    CPU tensors the same contract in torch: an fp32 log_softmax and a stable descending sort over the non-NaN elements."""
+    if not 1 <= int(n) <= MAX_TOP_LOGPROBS:
+        raise ValueError(f"token_top_logprobs: n must be in 1..{MAX_TOP_LOGPROBS}, got {n}")
+    n = int(n)
+    rows = logits[0]
+    T, V = rows.shape
+    if rows.is_cuda:
+        from . import glue
+
+        tg = None if targets is None else targets.reshape(-1).to(torch.int32)
+        fb = None if fallback is None else fallback.reshape(-1).to(torch.int32)
+        logprob, _, rank, top_ids, top_lp = glue.logprob_topn(rows, n, tg, fb)
+        return logprob, rank, top_ids, top_lp
+    logprob, rank = token_logprobs(logits, targets, fallback)
+    x = rows.float()
+    isnan = torch.isnan(x)
+    by_value = torch.sort(torch.where(isnan, torch.full_like(x, -float("inf")), x), dim=1, descending=True, stable=True).indices
+    nan_last = torch.sort(isnan.gather(1, by_value).to(torch.int8), dim=1, stable=True).indices  # (stable: the value order is kept)
+    order = by_value.gather(1, nan_last)
+    k = min(n, V)
+    listed = torch.arange(k).view(1, k) < (V - isnan.sum(dim=1)).view(T, 1)
+    top_ids = torch.full((T, n), -1, dtype=torch.int64)
+    top_lp = torch.full((T, n), float("nan"), dtype=torch.float32)
+    top_ids[:, :k] = torch.where(listed, order[:, :k], top_ids[:, :k])
+    top_lp[:, :k] = torch.where(listed, torch.log_softmax(x, dim=-1).gather(1, order[:, :k]), top_lp[:, :k])
+    return logprob, rank, top_ids.to(torch.int32), top_lp
+
+
+def _check_top_logprobs(kw):
+    """-> kw's `top_logprobs` as an int or None; ValueError for one without logprobs=True or outside 1..20."""
+    n = kw.get("top_logprobs")
+    if n is None:
+        return None
+    if not kw.get("logprobs", False):
+        raise ValueError("top_logprobs needs logprobs=True")
+    if isinstance(n, bool) or int(n) != n or not 1 <= int(n) <= MAX_TOP_LOGPROBS:
+        raise ValueError(f"top_logprobs must be an integer in 1..{MAX_TOP_LOGPROBS}, got {n}")
+    return int(n)
+
+
+def _score_rows(rows, targets, fallback=None, top_logprobs=None):
+    """TokenScores of logits rows [1, T, V], or TokenTopScores with `top_logprobs` alternatives per row."""
+    if top_logprobs is None:
+        return TokenScores(*token_logprobs(rows, targets, fallback))
+    return TokenTopScores(*token_top_logprobs(rows, top_logprobs, targets, fallback))
+
+
+def _clone_scores(s):
+    return type(s)(*(t.clone() for t in s))
+
+
+def _cat_scores(parts, top_logprobs, device):
+    """scores of single commits, in order, as one TokenScores / TokenTopScores (empty tensors for no commit at all)."""
+    if parts:
+        return type(parts[0])(*(torch.cat(ts) for ts in zip(*parts)))
+    lp, rk = torch.empty(0, dtype=torch.float32, device=device), torch.empty(0, dtype=torch.int32, device=device)
+    if top_logprobs is None:
+        return TokenScores(lp, rk)
+    return TokenTopScores(lp, rk, torch.empty((0, top_logprobs), dtype=torch.int32, device=device),
+                          torch.empty((0, top_logprobs), dtype=torch.float32, device=device))
+
+
 def perplexity(logprob, every=500):
     """The reference's perplexity arithmetic (eval.py:230-241) on a vector of per-token log-probabilities, in float64:
     {"ppl": exp(mean(-logprob)), "ppl@500": the same over the first 500 tokens, "ppl@1000": ...}; `every` None: "ppl" alone."""
@@ -241,37 +322,40 @@ def perplexity(logprob, every=500):
     return out
 
 
-def _scored(logits, next_token, temperature, top_k, seed, input_pos, top_p, min_p, score_target=None, chosen_from=None):
+def _scored(logits, next_token, temperature, top_k, seed, input_pos, top_p, min_p, score_target=None, chosen_from=None, top_logprobs=None):
     """One step's token and its TokenScores (logprobs=True).  A forced step runs no softmax and keeps no row: it is scored against its
     forced token.  A free step chooses its token exactly as greedy / sample do and scores it through `fallback`; so does a captured
     step (`score_target`: a one-element int32 device tensor the replay reads — the forced token, or -1 for what the step chose).
-    `chosen_from`: the penalised logits the token is chosen from (LogitPenalties); the scores stay the model's own row's."""
+    `chosen_from`: the penalised logits the token is chosen from (LogitPenalties); the scores stay the model's own row's.
+    `top_logprobs`: TokenTopScores with that many alternatives of the same row, from the same call."""
     row = logits[:, -1:]
     if next_token is not None and score_target is None:
-        return next_token, TokenScores(*token_logprobs(row, next_token.view(1)))
+        return next_token, _score_rows(row, next_token.view(1), None, top_logprobs)
     pick = row if chosen_from is None else chosen_from[:, -1:]
     if temperature is None:
         idx_next, _ = greedy(pick, None)
     else:
         idx_next, _ = sample(pick, None, temperature, top_k, seed, input_pos, top_p=top_p, min_p=min_p)
-    scores = TokenScores(*token_logprobs(row, score_target, fallback=idx_next.view(1)))
+    scores = _score_rows(row, score_target, idx_next.view(1), top_logprobs)
     return (idx_next if next_token is None else next_token), scores
 
 
 def prefill(model, x, input_pos, next_token=None, temperature=None, top_k=None, seed=0, top_p=None, min_p=None, logprobs=False,
-            penalties=None, **_):
+            penalties=None, top_logprobs=None, **_):
     """ref: generation_utils.py:145-160 — the causal mask is implicit in the HIP prefill kernel.  `temperature` None: greedy;
     otherwise the token is drawn at the last prompt position (sample), behind the top_k / top_p / min_p filters.  `logprobs`: the
     second result is the token's TokenScores, taken from the last row, instead of that row's probabilities.  `penalties` (a
     LogitPenalties whose `reset` has counted this prompt): the token is chosen from the penalised last row and the probabilities are
-    that row's; the scores stay the model's own."""
+    that row's; the scores stay the model's own.  `top_logprobs` (with `logprobs`): TokenTopScores with that many alternatives."""
+    top_logprobs = _check_top_logprobs(dict(logprobs=logprobs, top_logprobs=top_logprobs))
     logits = model(x, input_pos, mask=None, is_prefill=True)
     pen = _active_penalties(penalties)
     chosen_from = None
     if pen is not None:  # (the prompt is already counted: this row adds nothing)
         chosen_from = pen.apply(logits[:, -1:])
     if logprobs:
-        return _scored(logits, next_token, temperature, top_k, seed, input_pos[-1:], top_p, min_p, chosen_from=chosen_from)
+        return _scored(logits, next_token, temperature, top_k, seed, input_pos[-1:], top_p, min_p, chosen_from=chosen_from,
+                       top_logprobs=top_logprobs)
     if chosen_from is not None:
         logits = chosen_from
     if temperature is None:
@@ -280,15 +364,18 @@ def prefill(model, x, input_pos, next_token=None, temperature=None, top_k=None, 
 
 
 def decode_one_token(model, x, input_pos, next_token=None, attn_top_k=1.0, temperature=None, top_k=None, seed=0, top_p=None, min_p=None,
-                     logprobs=False, score_target=None, penalties=None, **_):
+                     logprobs=False, score_target=None, penalties=None, top_logprobs=None, **_):
     """ref: generation_utils.py:163-178.  `temperature` None: greedy; otherwise the token is drawn at `input_pos` (sample).
     `logprobs`: the second result is the token's TokenScores instead of the row's probabilities (_scored).  `penalties`: the step's
-    input `x` at `input_pos` is counted (both read from device memory) and the token is chosen from the penalised row."""
+    input `x` at `input_pos` is counted (both read from device memory) and the token is chosen from the penalised row.
+    `top_logprobs` (with `logprobs`): TokenTopScores with that many alternatives of the model's own row."""
+    top_logprobs = _check_top_logprobs(dict(logprobs=logprobs, top_logprobs=top_logprobs))
     logits = model(x, input_pos, is_prefill=False, attn_top_k=attn_top_k)
     pen = _active_penalties(penalties)
     chosen_from = pen.apply(logits[:, -1:], x, input_pos) if pen is not None else None
     if logprobs:
-        return _scored(logits, next_token, temperature, top_k, seed, input_pos, top_p, min_p, score_target, chosen_from=chosen_from)
+        return _scored(logits, next_token, temperature, top_k, seed, input_pos, top_p, min_p, score_target, chosen_from=chosen_from,
+                       top_logprobs=top_logprobs)
     if chosen_from is not None:
         logits = chosen_from
     if temperature is None:
@@ -306,14 +393,19 @@ class GraphedDecoder:
     `self.target` (the forced token, copied in before the replay; -1 for a free step) or else the token the step just wrote, into
     static tensors that the caller clones as it clones the token.  `penalties` (a LogitPenalties; None or a neutral one: none) is
     one more: the captured step holds the addresses of its buffers and advances its counts from `self.tok` / `self.pos`; objects
-    compare by identity, so the same object reused across generations does not capture again."""
+    compare by identity, so the same object reused across generations does not capture again.  `top_logprobs` (with `logprobs`) is
+    the last: the captured step then ends with cc_logprob_topn in place of cc_logprob_rows and `out_probs` is a TokenTopScores of
+    static tensors, `out_top_ids` and `out_top_logprobs` among them; another width captures again."""
 
-    _SETTINGS = ("temperature", "top_k", "seed", "top_p", "min_p", "logprobs", "penalties")
+    _SETTINGS = ("temperature", "top_k", "seed", "top_p", "min_p", "logprobs", "penalties", "top_logprobs")
     _LOGPROBS = 5  # (index of `logprobs` in the settings)
+    _PENALTIES = 6  # (index of `penalties`: compared after normalisation)
 
-    def __init__(self, model, warmup=2, temperature=None, top_k=None, seed=0, top_p=None, min_p=None, logprobs=False, penalties=None):
+    def __init__(self, model, warmup=2, temperature=None, top_k=None, seed=0, top_p=None, min_p=None, logprobs=False, penalties=None,
+                 top_logprobs=None):
         self.model = model
-        self.sampling = (temperature, top_k, seed, top_p, min_p, logprobs, _active_penalties(penalties))
+        top_logprobs = _check_top_logprobs(dict(logprobs=logprobs, top_logprobs=top_logprobs))
+        self.sampling = (temperature, top_k, seed, top_p, min_p, logprobs, _active_penalties(penalties), top_logprobs)
         dev = model.output.weight.device
         self.tok = torch.zeros((1, 1), dtype=torch.int32, device=dev)
         self.pos = torch.zeros((1,), dtype=torch.int32, device=dev)
@@ -348,7 +440,8 @@ class GraphedDecoder:
             with torch.cuda.graph(graph):
                 self.out_tok, self.out_probs = decode_one_token(self.model, self.tok, self.pos, **kw)
             if kw["logprobs"]:
-                self.out_logprob, self.out_rank = self.out_probs
+                self.out_logprob, self.out_rank = self.out_probs[:2]
+                self.out_top_ids, self.out_top_logprobs = self.out_probs[2:] if kw["top_logprobs"] is not None else (None, None)
             self.graph = graph
             self._epoch = self._cache_epoch()
             self._w12_epoch = self._weights_epoch()
@@ -379,7 +472,7 @@ class GraphedDecoder:
 
     def __call__(self, model, x, input_pos, next_token=None, **kw):
         sampling = tuple(kw.get(k, d) for k, d in zip(self._SETTINGS, self.sampling))
-        sampling = sampling[:-1] + (_active_penalties(sampling[-1]),)
+        sampling = sampling[:self._PENALTIES] + (_active_penalties(sampling[self._PENALTIES]),) + sampling[self._PENALTIES + 1:]
         if sampling != self.sampling:  # (carried by value, like what _cache_epoch watches: capture again)
             self.sampling = sampling
             self.graph = None
@@ -635,6 +728,9 @@ def decode_n_tokens(model, cur_token, input_pos, decode_one_token, num_new_token
     TokenScores(logprob, rank), one element per committed token in commit order (trimmed with the tokens when the loop rewinds).  A
     forced step runs no softmax and is scored against its forced token; a free step draws its token as before and scores it; a block
     scores its T rows in one call.
+    `top_logprobs` (ours, with `logprobs`; default None: as above): TokenTopScores in place of TokenScores — every element also has
+    the n most likely tokens of the model's own row and their log-probabilities (no temperature, filters or penalties), from the same
+    call that scores it.
     `penalties` (ours; default None: this loop as it was): a LogitPenalties whose counts hold the prompt; every step counts its input
     token and chooses from the penalised row (a block in one call over its T rows).  Launches behind a set status word do nothing to
     the caches but their penalise launches still count their garbage inputs: a rewind rebuilds the counts from the inputs of the
@@ -642,6 +738,7 @@ def decode_n_tokens(model, cur_token, input_pos, decode_one_token, num_new_token
     new_tokens, new_probs, incs = [], [], []
     pen = _active_penalties(kw.get("penalties"))
     logprobs = bool(kw.get("logprobs", False))
+    top_n = _check_top_logprobs(kw)
     recover = kw.pop("recover", None)
     block = kw.pop("forced_block", 1)
     block = 1 if block is None else max(1, min(int(block), _MAX_BLOCK))
@@ -657,7 +754,7 @@ def decode_n_tokens(model, cur_token, input_pos, decode_one_token, num_new_token
     def commit(k, nt, npb):
         nonlocal cur, stopped
         new_tokens.append(nt.clone())
-        new_probs.append(TokenScores(npb.logprob.clone(), npb.rank.clone()) if logprobs else npb.clone())
+        new_probs.append(_clone_scores(npb) if logprobs else npb.clone())
         teacher_force = prefix is not None and k < len(prefix)
         if terminator_ids and nt in terminator_ids and not teacher_force:
             stopped = True
@@ -711,9 +808,9 @@ def decode_n_tokens(model, cur_token, input_pos, decode_one_token, num_new_token
                                      min_p=kw.get("min_p"))
                 fallback = torch.zeros((T,), dtype=torch.int32, device=logits.device)
                 fallback[T - 1:] = last.view(1)
-            lp, rk = token_logprobs(own, targets, fallback)
+            scores = _score_rows(own, targets, fallback, top_n)
             for t in range(T):
-                commit(k + t, forced_at(k + t) if t < n_forced else last, TokenScores(lp[t:t + 1], rk[t:t + 1]))
+                commit(k + t, forced_at(k + t) if t < n_forced else last, type(scores)(*(s[t:t + 1] for s in scores)))
             return
         for t in range(T):
             row = logits[:, t:t + 1]
@@ -766,9 +863,7 @@ def decode_n_tokens(model, cur_token, input_pos, decode_one_token, num_new_token
         if not running and not watch.outstanding():
             break
     if logprobs:
-        dev = cur_token.device
-        return new_tokens, TokenScores(torch.cat([p.logprob for p in new_probs]) if new_probs else torch.empty(0, dtype=torch.float32, device=dev),
-                                       torch.cat([p.rank for p in new_probs]) if new_probs else torch.empty(0, dtype=torch.int32, device=dev))
+        return new_tokens, _cat_scores(new_probs, top_n, cur_token.device)
     return new_tokens, new_probs
 
 
@@ -782,7 +877,10 @@ def generate(model, prompt, prefill, decode_one_token, max_new_tokens, next_toke
     `penalties=LogitPenalties(...)` (ours): repetition / frequency / presence penalties and a logit bias on every row a token is
     chosen from, with the token history on the device; the object is reset with the tokens that are prefilled, and positions from the
     ORIGINAL prompt length on count as generated (a teacher-forced continuation included).  The returned probability rows are the
-    penalised distribution's; `logprobs` keeps scoring under the model's own."""
+    penalised distribution's; `logprobs` keeps scoring under the model's own.  `top_logprobs=n` (ours, with `logprobs=True`, 1..20):
+    the second result is TokenTopScores — the two vectors, and per token the n most likely tokens of the model's own row with their
+    log-probabilities; a ValueError before anything runs for an n outside 1..20 or without `logprobs=True`."""
+    _check_top_logprobs(kw)
     prompt_length = prompt.size(0)
     device, dtype = prompt.device, prompt.dtype
     gen_start = prompt_length  # (penalties: a prompt tail that is fed through decode steps below still counts as prompt)
@@ -823,7 +921,7 @@ def generate(model, prompt, prefill, decode_one_token, max_new_tokens, next_toke
     t1 = time.perf_counter()
     logprobs = bool(kw.get("logprobs", False))
     next_token = ret[0].clone()
-    next_tok_probs = TokenScores(ret[1].logprob.clone(), ret[1].rank.clone()) if logprobs else ret[1].clone()
+    next_tok_probs = _clone_scores(ret[1]) if logprobs else ret[1].clone()
     seq[prompt_length] = next_token
     input_pos = torch.tensor([prompt_length], device=device, dtype=torch.int)
     toks, tok_probs = decode_n_tokens(model, next_token.view(1, -1), input_pos, decode_one_token, max_new_tokens - 1,
@@ -852,7 +950,7 @@ def generate(model, prompt, prefill, decode_one_token, max_new_tokens, next_toke
     if -1 in seq:
         seq = seq[: torch.where(seq == -1)[0][0]]
     if logprobs:  # (element 0: the token behind the prefill, scored from the prefill's last row)
-        return seq, TokenScores(torch.cat([next_tok_probs.logprob, tok_probs.logprob]), torch.cat([next_tok_probs.rank, tok_probs.rank])), stats
+        return seq, type(tok_probs)(*(torch.cat(ts) for ts in zip(next_tok_probs, tok_probs))), stats
     return seq, [next_tok_probs] + tok_probs, stats
 
 

@@ -3,7 +3,7 @@
 These are NOT part of the cache/attention hot path — they are the model-side code around it
 (ref: model.py:317-327, 375-387, 442-443, 452-457, 507-519), which the reference leaves to ~45 eager elementwise
 launches per layer or to torch.compile.  On device tensors they call the C ABI (`cc_add_rmsnorm`, `cc_qkv_rope`,
-`cc_silu_mul`, `cc_gemv_fused`, `cc_gemv_fused_multi` and its int8 / MXFP4 forms, `cc_softmax_argmax`, `cc_sample_topk`, `cc_sample_nucleus`, `cc_logprob_rows`,
+`cc_silu_mul`, `cc_gemv_fused`, `cc_gemv_fused_multi` and its int8 / MXFP4 forms, `cc_softmax_argmax`, `cc_sample_topk`, `cc_sample_nucleus`, `cc_logprob_rows`, `cc_logprob_topn`,
 `cc_token_counts_add`, `cc_logits_penalize`); CPU tensors raise — there is no host path in the package (the
 CPU model-wiring test brings its own eager twins: tests/host_glue.py).
 """
@@ -461,6 +461,45 @@ def logprob_rows(logits_2d, targets=None, fallback=None, want_rank=True):
 
 
 _LP_WS = {}
+
+
+def logprob_topn(logits_2d, n, targets=None, fallback=None):
+    """logprob_rows' three results and each row's `n` most likely alternatives (cc_logprob_topn; include/coldcompress.h has the
+    contract): the ids of the n first elements in the order (larger logit first, equal logits by lower id, NaN never) and their fp32
+    log-probabilities, padded with -1 / NaN where the row has fewer.  logits_2d, targets and fallback as logprob_rows takes them (a
+    strided view is passed as it is; both None: no target, NaN and -1); 1 <= n <= 20.
+    -> (logprob [T] fp32, lse [T] fp32, rank [T] int32, top_ids [T, n] int32, top_logprobs [T, n] fp32)."""
+    if not logits_2d.is_cuda:
+        _host(logits_2d, "logprob_topn logits")
+    x = logits_2d.view(1, -1) if logits_2d.dim() == 1 else logits_2d
+    if x.dim() != 2 or x.dtype not in _DT:
+        raise _abi.ColdCompressError(f"logprob_topn: logits must be [T, V] in float32 / bfloat16 / float16, got {x.dtype} {tuple(x.shape)}")
+    if not 1 <= int(n) <= LOGPROB_MAX_TOPN:
+        raise _abi.ColdCompressError(f"logprob_topn: n must be in 1..{LOGPROB_MAX_TOPN}, got {n}")
+    n = int(n)
+    T, V = x.shape
+    if V > 1 and x.stride(1) != 1 or (T > 1 and x.stride(0) < V):
+        x = x.contiguous()
+    stride = x.stride(0) if T > 1 else V
+    for name, t in (("targets", targets), ("fallback", fallback)):
+        if t is not None and not (t.is_cuda and t.dtype == torch.int32 and t.numel() == T and t.is_contiguous()):
+            raise _abi.ColdCompressError(f"logprob_topn: {name} must be a contiguous int32 device tensor of {T} elements, got {t.dtype} "
+                                         f"{tuple(t.shape)} on {t.device}")
+    logprob = torch.empty((T,), dtype=torch.float32, device=x.device)
+    lse = torch.empty((T,), dtype=torch.float32, device=x.device)
+    rank = torch.empty((T,), dtype=torch.int32, device=x.device)
+    top_ids = torch.empty((T, n), dtype=torch.int32, device=x.device)
+    top_logprobs = torch.empty((T, n), dtype=torch.float32, device=x.device)
+    ws = _LPT_WS.get(x.device)
+    if ws is None:
+        ws = _LPT_WS[x.device] = torch.empty(int(_abi.lib()["cc_logprob_topn_workspace_bytes"]()), dtype=torch.uint8, device=x.device)
+    _abi.call("cc_logprob_topn", _p(x), T, V, int(stride), _DT[x.dtype], _p(targets), _p(fallback), n, _p(logprob), _p(lse), _p(rank),
+              _p(top_ids), _p(top_logprobs), _p(ws), ws.numel(), _stream())
+    return logprob, lse, rank, top_ids, top_logprobs
+
+
+LOGPROB_MAX_TOPN = 20  # (CC_LOGPROB_MAX_TOPN)
+_LPT_WS = {}
 
 
 def _counts_ok(what, V, prompt_count, gen_count, gen_start):

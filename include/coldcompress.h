@@ -1018,6 +1018,38 @@ int cc_logprob_rows(const void* logits, int32_t T, int32_t V, int64_t row_stride
                     const int32_t* fallback, float* logprob, float* lse, int32_t* rank, void* workspace, size_t workspace_bytes,
                     cc_stream_t stream);
 
+/* The N most likely alternatives of each row next to its target's score: the OpenAI API's `top_logprobs`, vLLM's `logprobs=N`.
+ * logits, T, V, row_stride, dtype, targets and fallback are cc_logprob_rows' in every respect (T <= CC_LOGPROB_MAX_ROWS, every
+ * pointer a device pointer), and logprob[T], lse[T], rank[T] receive the bits cc_logprob_rows writes for the same arguments; each of
+ * the three may be NULL here (a caller may want the alternatives alone).  top_ids[T * N] (int32) and top_logprobs[T * N] (fp32), row r
+ * at + r * N, 1 <= N <= CC_LOGPROB_MAX_TOPN.
+ *   1. order     top_ids[r * N + j], j = 0 .. N-1, are the indices of the N first elements of row r in this total order over its
+ *                non-NaN elements: larger x_i = float(logits[r][i]) first, compared as floats (+0 and -0 are equal), equal values by
+ *                lower index first.  NaN elements are never listed; -inf elements are ordinary candidates and come last, in index
+ *                order.  The order is exact: ids carry no tolerance.
+ *   2. padding   a row with fewer than N non-NaN elements (V < N included) ends in ids of -1 with log-probabilities of NaN.
+ *   3. values    top_logprobs[r * N + j] = (x_id - M) - log S with the M and log S of the row's logprob (cc_logprob_rows, item 3):
+ *                bit-identical to cc_logprob_rows called with that id as the row's target.  Hence the classes: a NaN anywhere in the
+ *                row makes every listed value NaN while the ids stay the order's; a +inf gives NaN; a -inf candidate under a finite
+ *                maximum gives -inf.
+ *   4. target    when the row's target has 0 <= rank[r] < N, top_logprobs[r * N + rank[r]] has the bits of logprob[r]: position
+ *                `rank` of the order is the first element of the target's tie group.
+ *   5. determinism  item 6 of cc_logprob_rows, word for word, for all five results: a pure function of the row and its target, the
+ *                same bits in eager launches and under hipGraph replay, alone or as row r of T, at any alignment of the row's base.
+ *                No atomics on global memory and no tickets.
+ * Two launches, as cc_logprob_rows: the (128, T) grid additionally leaves each slice's N first elements of the order in the
+ * workspace (the whole top-N may sit in one slice), as 64-bit keys that no two elements share — round j takes the largest key below
+ * round j-1's pick, so nothing is marked as taken — and the per-row fold merges the 128 lists the same way and writes the results.
+ * Never synchronises, never allocates, stream-capturable; `workspace` (cc_logprob_topn_workspace_bytes, under 4 MB, 16-byte aligned)
+ * needs no initialisation: nothing is read that the call did not write.  CC_ERR_BAD_ARG before any launch: a NULL logits / top_ids /
+ * top_logprobs / workspace, N < 1, N > CC_LOGPROB_MAX_TOPN, and cc_logprob_rows' refusals for T, V, row_stride, dtype and alignment.
+ * CC_ERR_WORKSPACE: a workspace shorter than cc_logprob_topn_workspace_bytes(); a bad argument is named before the workspace. */
+#define CC_LOGPROB_MAX_TOPN 20
+size_t cc_logprob_topn_workspace_bytes(void);
+int cc_logprob_topn(const void* logits, int32_t T, int32_t V, int64_t row_stride, int32_t dtype, const int32_t* targets,
+                    const int32_t* fallback, int32_t N, float* logprob, float* lse, int32_t* rank, int32_t* top_ids,
+                    float* top_logprobs, void* workspace, size_t workspace_bytes, cc_stream_t stream);
+
 /* Token-history penalties and a logit bias in FRONT of the sampling tail: HF / vLLM's repetition_penalty, the OpenAI API's
  * frequency_penalty / presence_penalty / logit_bias.  Unlike every other stage of the tail they depend on what has been fed so far, so
  * the history lives on the DEVICE: prompt_count[V] and gen_count[V] (int32: how often each token has been an input) and gen_start[1]
