@@ -76,6 +76,9 @@ SIGNATURES = {
     "cc_logprob_topn": (C.c_int, [_vp, _i32, _i32, C.c_int64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "cc_token_counts_add": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp]),
     "cc_logits_penalize": (C.c_int, [_vp, _vp, _i32, _i32, C.c_int64, _i32, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _vp, _vp]),
+    "cc_token_history_write": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp]),
+    "cc_logits_constrain": (C.c_int, [_vp, _vp, _i32, _i32, C.c_int64, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp,
+                                      _i32, _vp]),
     "cc_gemv_fused": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
     "cc_gemv_fused_multi": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     "cc_w12_geometry": (C.c_int, [_i32, _i32, _i32, _vp]),
@@ -209,6 +212,7 @@ DEVICE_ONLY = {"cc_error_string", "cc_device_info", "cc_decode_step_single_launc
                "cc_logprob_rows_workspace_bytes", "cc_logprob_rows",  # per-token log-probabilities: float64 torch.log_softmax and the fp32 twin of the contract (tests/logprob_twin.py)
                "cc_logprob_topn_workspace_bytes", "cc_logprob_topn",  # the N best alternatives of a row: the float64 order and values (tests/logprob_topn_twin.py)
                "cc_token_counts_add", "cc_logits_penalize",  # token-history penalties: the fp32 torch twin of the contract (tests/penalty_twin.py)
+               "cc_token_history_write", "cc_logits_constrain",  # n-gram blocking, banned sequences, minimum length: the plain-Python twin (tests/constraint_twin.py)
                # the fused quantised cache's ring and hybrid steps: their checker is the same policy's 16-bit step on the dequantised values
                "cc_decode_step_heavy_hitter_ring_quant", "cc_decode_step_hybrid_quant_rc", "cc_decode_step_hybrid_quant_single_launch",
                # inter-GPU transport: no CPU twin (the oracle of the all-reduce is torch.distributed's)

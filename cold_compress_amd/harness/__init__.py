@@ -3,6 +3,7 @@ from .generation import (GraphedDecoder, TokenScores, TokenTopScores, apply_patt
                          generate, greedy, load_model, negotiate_graphed_decoder, normalize_cache_length, perplexity, prefill, sample, setup_caches,
                          token_logprobs, token_top_logprobs)
 from .penalties import LogitPenalties  # noqa: F401
+from .constraints import LogitConstraints  # noqa: F401
 from .model import CONFIGS, ModelArgs, Transformer, find_multiple  # noqa: F401
 from .quantize import (WeightOnlyInt4Linear, WeightOnlyInt4QuantHandler, WeightOnlyInt8Linear,  # noqa: F401
                        WeightOnlyInt8QuantHandler)

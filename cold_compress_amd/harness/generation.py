@@ -11,6 +11,7 @@ from typing import NamedTuple
 import torch
 
 from .model import Transformer, find_multiple
+from .constraints import LogitConstraints, active as _active_constraints  # noqa: F401
 from .penalties import LogitPenalties, active as _active_penalties  # noqa: F401
 
 
@@ -340,19 +341,35 @@ def _scored(logits, next_token, temperature, top_k, seed, input_pos, top_p, min_
     return (idx_next if next_token is None else next_token), scores
 
 
+def _constrained(constraints, rows, chosen_from, tokens, pos):
+    """The rows a token is chosen from behind `constraints` (a LogitConstraints; None or a neutral one: `chosen_from` as it is):
+    the penalties' output `chosen_from` constrained in place, or else the model's own `rows` constrained into a new tensor (the scores
+    keep reading `rows`).  The two stages commute exactly — every penalty step maps -inf to -inf and a +inf bias is refused — so
+    penalties first, constraints second is only the cheaper order."""
+    con = _active_constraints(constraints)
+    if con is None:
+        return chosen_from
+    if chosen_from is not None:
+        return con.apply(chosen_from, tokens, pos, out=chosen_from)
+    return con.apply(rows, tokens, pos)
+
+
 def prefill(model, x, input_pos, next_token=None, temperature=None, top_k=None, seed=0, top_p=None, min_p=None, logprobs=False,
-            penalties=None, top_logprobs=None, **_):
+            penalties=None, top_logprobs=None, constraints=None, **_):
     """ref: generation_utils.py:145-160 — the causal mask is implicit in the HIP prefill kernel.  `temperature` None: greedy;
     otherwise the token is drawn at the last prompt position (sample), behind the top_k / top_p / min_p filters.  `logprobs`: the
     second result is the token's TokenScores, taken from the last row, instead of that row's probabilities.  `penalties` (a
     LogitPenalties whose `reset` has counted this prompt): the token is chosen from the penalised last row and the probabilities are
-    that row's; the scores stay the model's own.  `top_logprobs` (with `logprobs`): TokenTopScores with that many alternatives."""
+    that row's; the scores stay the model's own.  `top_logprobs` (with `logprobs`): TokenTopScores with that many alternatives.
+    `constraints` (a LogitConstraints whose `reset` has stored this prompt): the token is chosen from the constrained last row,
+    behind the penalties."""
     top_logprobs = _check_top_logprobs(dict(logprobs=logprobs, top_logprobs=top_logprobs))
     logits = model(x, input_pos, mask=None, is_prefill=True)
     pen = _active_penalties(penalties)
     chosen_from = None
     if pen is not None:  # (the prompt is already counted: this row adds nothing)
         chosen_from = pen.apply(logits[:, -1:])
+    chosen_from = _constrained(constraints, logits[:, -1:], chosen_from, None, input_pos[-1:])  # (the prompt is already in the history)
     if logprobs:
         return _scored(logits, next_token, temperature, top_k, seed, input_pos[-1:], top_p, min_p, chosen_from=chosen_from,
                        top_logprobs=top_logprobs)
@@ -364,15 +381,18 @@ def prefill(model, x, input_pos, next_token=None, temperature=None, top_k=None, 
 
 
 def decode_one_token(model, x, input_pos, next_token=None, attn_top_k=1.0, temperature=None, top_k=None, seed=0, top_p=None, min_p=None,
-                     logprobs=False, score_target=None, penalties=None, top_logprobs=None, **_):
+                     logprobs=False, score_target=None, penalties=None, top_logprobs=None, constraints=None, **_):
     """ref: generation_utils.py:163-178.  `temperature` None: greedy; otherwise the token is drawn at `input_pos` (sample).
     `logprobs`: the second result is the token's TokenScores instead of the row's probabilities (_scored).  `penalties`: the step's
     input `x` at `input_pos` is counted (both read from device memory) and the token is chosen from the penalised row.
-    `top_logprobs` (with `logprobs`): TokenTopScores with that many alternatives of the model's own row."""
+    `top_logprobs` (with `logprobs`): TokenTopScores with that many alternatives of the model's own row.  `constraints`: the step's
+    input `x` is stored at `input_pos` in the positional history (both read from device memory) and the token is chosen from the
+    constrained row, behind the penalties."""
     top_logprobs = _check_top_logprobs(dict(logprobs=logprobs, top_logprobs=top_logprobs))
     logits = model(x, input_pos, is_prefill=False, attn_top_k=attn_top_k)
     pen = _active_penalties(penalties)
     chosen_from = pen.apply(logits[:, -1:], x, input_pos) if pen is not None else None
+    chosen_from = _constrained(constraints, logits[:, -1:], chosen_from, x, input_pos)
     if logprobs:
         return _scored(logits, next_token, temperature, top_k, seed, input_pos, top_p, min_p, score_target, chosen_from=chosen_from,
                        top_logprobs=top_logprobs)
@@ -395,17 +415,22 @@ class GraphedDecoder:
     one more: the captured step holds the addresses of its buffers and advances its counts from `self.tok` / `self.pos`; objects
     compare by identity, so the same object reused across generations does not capture again.  `top_logprobs` (with `logprobs`) is
     the last: the captured step then ends with cc_logprob_topn in place of cc_logprob_rows and `out_probs` is a TokenTopScores of
-    static tensors, `out_top_ids` and `out_top_logprobs` among them; another width captures again."""
+    static tensors, `out_top_ids` and `out_top_logprobs` among them; another width captures again.  `constraints` (a LogitConstraints;
+    None or a neutral one: none) is compared by identity like `penalties`: the captured step holds the addresses of its positional
+    history and stores `self.tok` at `self.pos` in it.  The warm-up steps store positions at and behind the captured one, which the
+    replays write again before anything reads them, so capture() has nothing of it to put back."""
 
-    _SETTINGS = ("temperature", "top_k", "seed", "top_p", "min_p", "logprobs", "penalties", "top_logprobs")
+    _SETTINGS = ("temperature", "top_k", "seed", "top_p", "min_p", "logprobs", "penalties", "top_logprobs", "constraints")
     _LOGPROBS = 5  # (index of `logprobs` in the settings)
     _PENALTIES = 6  # (index of `penalties`: compared after normalisation)
+    _CONSTRAINTS = 8  # (index of `constraints`: likewise)
 
     def __init__(self, model, warmup=2, temperature=None, top_k=None, seed=0, top_p=None, min_p=None, logprobs=False, penalties=None,
-                 top_logprobs=None):
+                 top_logprobs=None, constraints=None):
         self.model = model
         top_logprobs = _check_top_logprobs(dict(logprobs=logprobs, top_logprobs=top_logprobs))
-        self.sampling = (temperature, top_k, seed, top_p, min_p, logprobs, _active_penalties(penalties), top_logprobs)
+        self.sampling = (temperature, top_k, seed, top_p, min_p, logprobs, _active_penalties(penalties), top_logprobs,
+                         _active_constraints(constraints))
         dev = model.output.weight.device
         self.tok = torch.zeros((1, 1), dtype=torch.int32, device=dev)
         self.pos = torch.zeros((1,), dtype=torch.int32, device=dev)
@@ -473,6 +498,7 @@ class GraphedDecoder:
     def __call__(self, model, x, input_pos, next_token=None, **kw):
         sampling = tuple(kw.get(k, d) for k, d in zip(self._SETTINGS, self.sampling))
         sampling = sampling[:self._PENALTIES] + (_active_penalties(sampling[self._PENALTIES]),) + sampling[self._PENALTIES + 1:]
+        sampling = sampling[:self._CONSTRAINTS] + (_active_constraints(sampling[self._CONSTRAINTS]),) + sampling[self._CONSTRAINTS + 1:]
         if sampling != self.sampling:  # (carried by value, like what _cache_epoch watches: capture again)
             self.sampling = sampling
             self.graph = None
@@ -734,9 +760,14 @@ def decode_n_tokens(model, cur_token, input_pos, decode_one_token, num_new_token
     `penalties` (ours; default None: this loop as it was): a LogitPenalties whose counts hold the prompt; every step counts its input
     token and chooses from the penalised row (a block in one call over its T rows).  Launches behind a set status word do nothing to
     the caches but their penalise launches still count their garbage inputs: a rewind rebuilds the counts from the inputs of the
-    steps that stay committed before the failed token runs again, and so does every retry."""
+    steps that stay committed before the failed token runs again, and so does every retry.
+    `constraints` (ours; default None: this loop as it was): a LogitConstraints whose history holds the prompt; every step stores its
+    input token at its position and chooses from the constrained row, behind the penalties (a block in one call over its T rows).  A
+    rewind needs nothing here: the garbage launches stored positions past the failed token's, and those are stored again, in order,
+    before any step reads them."""
     new_tokens, new_probs, incs = [], [], []
     pen = _active_penalties(kw.get("penalties"))
+    con = _active_constraints(kw.get("constraints"))
     logprobs = bool(kw.get("logprobs", False))
     top_n = _check_top_logprobs(kw)
     recover = kw.pop("recover", None)
@@ -794,6 +825,8 @@ def decode_n_tokens(model, cur_token, input_pos, decode_one_token, num_new_token
         own = logits  # (the model's own rows: what logprobs scores)
         if pen is not None:
             logits = pen.apply(logits, idx, pos)
+        if con is not None:  # (in place on the penalties' output; the model's own rows stay as they are)
+            logits = con.apply(logits, idx, pos, out=logits if pen is not None else None)
         if logprobs:
             n_forced = min(T, len(prefix) - k)  # T or T - 1: only the last step of a block may be a free one
             targets = torch.full((T,), -1, dtype=torch.int32, device=logits.device)
@@ -879,7 +912,11 @@ def generate(model, prompt, prefill, decode_one_token, max_new_tokens, next_toke
     ORIGINAL prompt length on count as generated (a teacher-forced continuation included).  The returned probability rows are the
     penalised distribution's; `logprobs` keeps scoring under the model's own.  `top_logprobs=n` (ours, with `logprobs=True`, 1..20):
     the second result is TokenTopScores — the two vectors, and per token the n most likely tokens of the model's own row with their
-    log-probabilities; a ValueError before anything runs for an n outside 1..20 or without `logprobs=True`."""
+    log-probabilities; a ValueError before anything runs for an n outside 1..20 or without `logprobs=True`.
+    `constraints=LogitConstraints(...)` (ours): n-gram blocking, banned sequences and a minimum number of new tokens on every row a
+    token is chosen from, behind the penalties, with the token history on the device by position; the object is reset with the tokens
+    that are prefilled and the same `gen_start` as the penalties.  A ValueError before the prefill when the prompt and the new tokens
+    do not fit its `max_positions`."""
     _check_top_logprobs(kw)
     prompt_length = prompt.size(0)
     device, dtype = prompt.device, prompt.dtype
@@ -914,6 +951,12 @@ def generate(model, prompt, prefill, decode_one_token, max_new_tokens, next_toke
     pen = _active_penalties(kw.get("penalties"))
     if pen is not None:
         pen.reset(prompt, gen_start)
+    con = _active_constraints(kw.get("constraints"))
+    if con is not None:
+        if prompt_length + max_new_tokens > con.max_positions:
+            raise ValueError(f"generate: {prompt_length} prompt tokens and {max_new_tokens} new ones do not fit the constraints' "
+                             f"max_positions = {con.max_positions}")
+        con.reset(prompt, gen_start)
     sync()
     t0 = time.perf_counter()
     ret = prefill(model, prompt.view(1, -1), input_pos, next_token=next_token, **kw)

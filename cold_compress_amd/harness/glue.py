@@ -4,7 +4,7 @@ These are NOT part of the cache/attention hot path — they are the
 (ref: model.py:317-327, 375-387, 442-443, 452-457, 507-519), which the reference leaves to ~45 eager elementwise
 launches per layer or to torch.compile.  On device tensors they call the C ABI (`cc_add_rmsnorm`, `cc_qkv_rope`,
 `cc_silu_mul`, `cc_gemv_fused`, `cc_gemv_fused_multi` and its int8 / MXFP4 forms, `cc_softmax_argmax`, `cc_sample_topk`, `cc_sample_nucleus`, `cc_logprob_rows`, `cc_logprob_topn`,
-`cc_token_counts_add`, `cc_logits_penalize`); CPU tensors raise — there is no host path in the package (the
+`cc_token_counts_add`, `cc_logits_penalize`, `cc_token_history_write`, `cc_logits_constrain`); CPU tensors raise — there is no host path in the package (the
 CPU model-wiring test brings its own eager twins: tests/host_glue.py).
 """
 import ctypes as C
@@ -556,4 +556,70 @@ def logits_penalize(logits_2d, prompt_count, gen_count, gen_start, tokens=None, 
     y = x if inplace else torch.empty((T, stride), dtype=x.dtype, device=x.device)[:, :V]  # (one row stride serves both sides)
     _abi.call("cc_logits_penalize", _p(x), _p(y), T, V, int(stride), _DT[x.dtype], _p(prompt_count), _p(gen_count), _p(tokens), _p(pos),
               _p(gen_start), float(repetition_penalty), float(frequency_penalty), float(presence_penalty), _p(bias), _stream())
+    return logits_2d if inplace else y
+
+
+CONSTRAIN_MAX_BW_TOKENS = 4096  # (CC_CONSTRAIN_MAX_BW_TOKENS)
+CONSTRAIN_SLICE = 1024  # (CC_CONSTRAIN_SLICE: candidate starts per workgroup of the ban pass)
+
+
+def _i32_ok(what, name, t, n=None):
+    if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and (n is None or t.numel() == n)):
+        raise _abi.ColdCompressError(f"{what}: {name} must be a contiguous int32 device tensor{'' if n is None else f' of {n} elements'}, "
+                                     f"got {t.dtype} {tuple(t.shape)} on {t.device}")
+
+
+def token_history_write(hist, tokens, first_pos=0):
+    """hist[first_pos + i] = tokens[i] for the positions inside the history (int32 DEVICE tensors; first_pos a host int): the prompt
+    of cc_logits_constrain's positional history in one launch (cc_token_history_write; include/coldcompress.h has the contract)."""
+    _i32_ok("token_history_write", "hist", hist)
+    _i32_ok("token_history_write", "tokens", tokens)
+    _abi.call("cc_token_history_write", _p(hist), hist.numel(), _p(tokens), tokens.numel(), int(first_pos), _stream())
+
+
+def logits_constrain(logits_2d, hist, gen_start, tokens, pos, ngram=0, ngram_from_gen=False, min_new_tokens=0, term_ids=None,
+                     bw_tokens=None, bw_offsets=None, out=None):
+    """n-gram blocking, banned sequences and a minimum length on T <= 4 rows of logits: every banned element becomes -inf, every other
+    keeps its bits, and the rows' input tokens are stored into the positional history (cc_logits_constrain; include/coldcompress.h has
+    the contract).  logits_2d: [T, V] (or one row [V]) on the device; a view with a row stride is passed as it is.  hist: int32 [cap],
+    gen_start: int32 [1], pos: int32, at least one element (row t is at position pos[0] + t), tokens: int32 [T] or None (the prefill's
+    row) — all DEVICE tensors the kernel reads, so a captured step advances.  term_ids: int32 device tensor or None; bw_tokens /
+    bw_offsets: the banned sequences back to back and their n + 1 offsets, or None.  out: None (a new contiguous tensor) or `logits_2d`
+    itself (in place).  -> out."""
+    if not logits_2d.is_cuda:
+        _host(logits_2d, "logits_constrain logits")
+    x = logits_2d.view(1, -1) if logits_2d.dim() == 1 else logits_2d
+    if x.dim() != 2 or x.dtype not in _DT:
+        raise _abi.ColdCompressError(f"logits_constrain: logits must be [T, V] in float32 / bfloat16 / float16, got {x.dtype} {tuple(x.shape)}")
+    T, V = x.shape
+    inplace = out is not None
+    if inplace and out is not logits_2d:
+        raise _abi.ColdCompressError("logits_constrain: out must be None or the logits tensor itself")
+    if V > 1 and x.stride(1) != 1 or (T > 1 and x.stride(0) < V):
+        if inplace:
+            raise _abi.ColdCompressError("logits_constrain: in place needs rows of unit element stride that do not overlap")
+        x = x.contiguous()
+    stride = x.stride(0) if T > 1 else V
+    _i32_ok("logits_constrain", "hist", hist)
+    _i32_ok("logits_constrain", "gen_start", gen_start, 1)
+    _i32_ok("logits_constrain", "pos", pos)
+    if pos.numel() < 1:
+        raise _abi.ColdCompressError("logits_constrain: pos must hold the first row's position")
+    if tokens is not None:
+        _i32_ok("logits_constrain", "tokens", tokens, T)
+    if term_ids is not None:
+        _i32_ok("logits_constrain", "term_ids", term_ids)
+    if (bw_tokens is None) != (bw_offsets is None):
+        raise _abi.ColdCompressError("logits_constrain: bw_tokens and bw_offsets come together")
+    n_bw = 0
+    if bw_tokens is not None:
+        _i32_ok("logits_constrain", "bw_tokens", bw_tokens)
+        _i32_ok("logits_constrain", "bw_offsets", bw_offsets)
+        n_bw = bw_offsets.numel() - 1
+        if n_bw < 0 or bw_tokens.numel() > CONSTRAIN_MAX_BW_TOKENS:
+            raise _abi.ColdCompressError(f"logits_constrain: bw_offsets needs n + 1 elements and bw_tokens at most {CONSTRAIN_MAX_BW_TOKENS}")
+    y = x if inplace else torch.empty((T, stride), dtype=x.dtype, device=x.device)[:, :V]  # (one row stride serves both sides)
+    _abi.call("cc_logits_constrain", _p(x), _p(y), T, V, int(stride), _DT[x.dtype], _p(hist), hist.numel(), _p(tokens), _p(pos),
+              _p(gen_start), int(ngram), int(bool(ngram_from_gen)), int(min_new_tokens), _p(term_ids),
+              0 if term_ids is None else term_ids.numel(), _p(bw_tokens), _p(bw_offsets), n_bw, _stream())
     return logits_2d if inplace else y

@@ -1091,6 +1091,50 @@ int cc_logits_penalize(const void* logits, void* out, int32_t T, int32_t V, int6
                        float repetition_penalty, float frequency_penalty, float presence_penalty, const float* bias,
                        cc_stream_t stream);
 
+/* Sequence rules in FRONT of the sampling tail: HF's no_repeat_ngram_size, bad_words_ids and min_new_tokens.  They need the ORDER of
+ * what has been fed, so the state is positional: hist[cap] (device int32), hist[q] = the input token at position q, and gen_start[1]
+ * (device int32: positions from it on are generated).  A row computed at position p predicts the token at p + 1; its history is
+ * s[0 .. p].  A step at position p writes hist[p] and reads hist only in FRONT of its own position, so launches behind a failed step
+ * (which write positions past it, written again in order before they are read) leave nothing to put back: no rebuild, no snapshot.
+ *
+ * cc_token_history_write: hist[first_pos + i] = tokens[i] (device int32 [n]; first_pos: a host int) wherever that position lies in
+ * [0, cap): the prompt in one launch.  n == 0: CC_OK without a launch.  A NULL or misaligned hist / tokens (tokens with n > 0),
+ * cap <= 0, n < 0: CC_ERR_BAD_ARG.
+ *
+ * cc_logits_constrain: logits and out are T rows of V elements of the model dtype (`dtype`), row t at + t * row_stride elements,
+ * 1 <= T <= CC_GEMV_MULTI_MAX_T; out may be logits itself (in place) and must share nothing with it otherwise (the input rows are
+ * then left as they were).  pos: device int32, pos[0] is read: row t is at position p = pos[0] + t.  tokens: device int32 [T], the
+ * rows' input tokens, or NULL (the prefill's row: its history is in hist up to p).  Element j of the history of every row of the
+ * launch is s[j] = hist[j] for j < pos[0] (for every j with tokens NULL) and tokens[j - pos[0]] otherwise, so a pattern may straddle
+ * the block's start or lie inside the block.  An element that a rule bans becomes -inf of the dtype whatever it held (NaN included);
+ * every other element keeps its bits; a banned id outside [0, V) bans nothing and no address is formed from it.  Row t, 0 <= p < cap:
+ *   ngram = n > 0:       for i in i0 .. p - n + 1 with s[i .. i+n-2] == s[p-n+2 .. p]: ban s[i+n-1]      (n = 1: every token seen)
+ *                        i0 = 0, or max(*gen_start, 0) with ngram_from_gen != 0 (n-grams wholly in the generated part)
+ *   min_new_tokens = m:  while p + 1 - *gen_start < m: ban term_ids[0 .. n_term-1]
+ *   banned sequences:    sequence b = bw_tokens[bw_offsets[b] .. bw_offsets[b+1] - 1] (device int32; bw_offsets [n_bw + 1], ascending
+ *                        from 0; 1 .. CC_CONSTRAIN_MAX_NGRAM tokens each, CC_CONSTRAIN_MAX_BW_TOKENS in all) of length k + 1 bans its last
+ *                        token when k == 0, or when k <= p + 1 and s[p-k+1 .. p] equals its first k
+ * A row at a position outside [0, cap) is copied unchanged.  The launch also stores hist[pos[0] + t] = tokens[t] for the positions
+ * inside [0, cap) (tokens NULL: nothing).  At most two launches on `stream`, no workspace, no atomics (threads that ban one element
+ * store the same value), no waits between workgroups: a copy of the rows when out != logits (16 bytes at a time where a row's base
+ * is 16-byte aligned, element by element where not), and the ban pass, whose grid covers (CC_CONSTRAIN_SLICE candidate starts i, row)
+ * and is sized from cap, so a captured launch serves every later position.  Never synchronises, never allocates, capturable.
+ * Before any launch, every CC_ERR_BAD_ARG before CC_ERR_UNSUPPORTED — CC_ERR_BAD_ARG: a NULL logits / out / hist / pos / gen_start,
+ * T outside 1 .. CC_GEMV_MULTI_MAX_T, V <= 0, row_stride < V, cap <= 0, ngram outside 0 .. CC_CONSTRAIN_MAX_NGRAM, min_new_tokens < 0,
+ * n_term outside 0 .. CC_CONSTRAIN_MAX_TERMINATORS (or NULL term_ids with n_term > 0), n_bw outside 0 .. CC_CONSTRAIN_MAX_BW (or a NULL
+ * bw_tokens / bw_offsets with n_bw > 0), a misaligned pointer, out overlapping logits without being it; CC_ERR_UNSUPPORTED: a dtype
+ * that is none of CC_DT_F32 / CC_DT_BF16 / CC_DT_F16. */
+#define CC_CONSTRAIN_MAX_NGRAM 32
+#define CC_CONSTRAIN_MAX_TERMINATORS 64
+#define CC_CONSTRAIN_MAX_BW 1024
+#define CC_CONSTRAIN_MAX_BW_TOKENS 4096
+#define CC_CONSTRAIN_SLICE 1024
+int cc_token_history_write(int32_t* hist, int32_t cap, const int32_t* tokens, int32_t n, int32_t first_pos, cc_stream_t stream);
+int cc_logits_constrain(const void* logits, void* out, int32_t T, int32_t V, int64_t row_stride, int32_t dtype, int32_t* hist,
+                        int32_t cap, const int32_t* tokens, const int32_t* pos, const int32_t* gen_start, int32_t ngram,
+                        int32_t ngram_from_gen, int32_t min_new_tokens, const int32_t* term_ids, int32_t n_term,
+                        const int32_t* bw_tokens, const int32_t* bw_offsets, int32_t n_bw, cc_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * One-shot sum all-reduce over the GPUs of ONE node, for the decode-size messages of tensor parallelism.
  * ref: tp.py:134-138, 156-160 (`all_reduce(sum)` of the wo and FFN outputs: 2 * dim bytes, 8-16 KiB, twice per layer).
