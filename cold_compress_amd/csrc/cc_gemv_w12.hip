@@ -23,9 +23,20 @@
 // tied to the (RB, CU) it was packed for (cc_w12_geometry).  Built and tested: K <= 16384; measured faster than the dense kernel and
 // therefore on by default in the harness: the pair and the LM-head classes at K <= 4096 only (cc_w12_geometry's fifth word).
 //
+// A second code layout, "planar" (layout id 1; the one above is 0), keeps chunk index, records, overflow rule and dense fallback and
+// splits a weight by BYTES instead of by fields, so that one operation decodes four weights.  With `base` even and B = base / 2:
+//   dword 0, 1 : byte k = the low byte of bf16 weight k resp. 4 + k as it is (exponent bit 0 in bit 7, the mantissa below)
+//   dword 2    : byte k = sign of weight k << 7 | ((exponent >> 1) - B) of weight 4 + k << 4 | sign of weight 4 + ((k + 3) & 3) << 3
+//                | ((exponent >> 1) - B) of weight k      (the sign of weight 4 + k sits in bit 3 of byte (k + 1) & 3)
+// Decode: mask 0x87878787 and add B to all four bytes at once (no carries: B + 7 <= 127) gives the high bytes of weights 0 .. 3; the
+// same on the dword rotated right by 4 gives those of weights 4 .. 7; four v_perm interleave high and low bytes.  Nine operations
+// per chunk against 24.  The layout of a packed copy travels in bits 8 .. 15 of the `rb` word (include/coldcompress.h).
+//
 // Packer (cc_w12_pack, once per tensor): exponent histogram -> the window of 16 that covers most weights -> codes and records.
 #include <cstdio>
 #include <cstdlib>
+#include <mutex>
+#include <unordered_map>
 
 #include "cc_common.h"
 #include "cc_gemv_core.h"
@@ -43,8 +54,10 @@ struct GemvW12Args {
   const uint32_t* P3;
   const uint32_t* R;    // records [row groups, phases, 4 waves][8]
   const uint32_t* R3;
-  uint32_t bw, bw3;     // base << 7 | base << 23
+  uint32_t bw, bw3;     // layout 0: base << 7 | base << 23; planar: base / 2 in every byte
 };
+
+constexpr int kW12Planar = 1;  // layout ids
 
 typedef unsigned int u32x3_t __attribute__((ext_vector_type(3)));
 
@@ -52,7 +65,15 @@ __device__ __forceinline__ uint32_t w12_pair(uint32_t sm, uint32_t sel, uint32_t
   const uint32_t t = (__builtin_amdgcn_perm(sm, sm, sel) & 0x807f807fu) | bw;
   return (((ex >> (4 * j)) & 0x000f000fu) << 7) + t;
 }
+template <int LAY>
 __device__ __forceinline__ uint4 w12_decode(u32x3_t q, uint32_t bw) {
+  if constexpr (LAY == kW12Planar) {
+    const uint32_t ha = (q.z & 0x87878787u) + bw;
+    const uint32_t hb = (__builtin_amdgcn_alignbit(q.z, q.z, 4) & 0x87878787u) + bw;  // rotate right by 4
+    // (v_perm: selector bytes 0 .. 3 name the second source, 4 .. 7 the first)
+    return make_uint4(__builtin_amdgcn_perm(ha, q.x, 0x05010400u), __builtin_amdgcn_perm(ha, q.x, 0x07030602u),
+                      __builtin_amdgcn_perm(hb, q.y, 0x05010400u), __builtin_amdgcn_perm(hb, q.y, 0x07030602u));
+  }
   return make_uint4(w12_pair(q.x, 0x01010000u, q.z, 0, bw), w12_pair(q.x, 0x03030202u, q.z, 1, bw),
                     w12_pair(q.y, 0x01010000u, q.z, 2, bw), w12_pair(q.y, 0x03030202u, q.z, 3, bw));
 }
@@ -76,7 +97,7 @@ __device__ __forceinline__ uint4 w12_patch(uint4 d, uint32_t rec, int cnt, int t
   return d;
 }
 
-template <bool SWIGLU, int RB, int CU, int XS>
+template <int LAY, bool SWIGLU, int RB, int CU, int XS>
 __global__ __launch_bounds__(kW12Threads) void gemv_w12_kernel(GemvW12Args a) {
   const int N = a.g.N, nch = a.g.K / 8;
   const int nstep = ((nch + 63) / 64 + kW12Waves - 1) / kW12Waves;
@@ -90,27 +111,31 @@ __global__ __launch_bounds__(kW12Threads) void gemv_w12_kernel(GemvW12Args a) {
   auto issue = [&](int r0, int s0) {
     tr0 = r0;
     ts0 = s0;
-#pragma unroll
-    for (int u = 0; u < CU; u++) {
-      const int c = ((s0 + u) * kW12Waves + wave) * 64 + lane;
-      const bool cin = (s0 + u < nstep) && c < nch;
-#pragma unroll
-      for (int r = 0; r < RB; r++) {
-        const bool in = cin && (r0 + r < N);
-        const size_t off = ((size_t)(r0 + r) * nch + c) * 3;
-        const u32x3_t z = {0u, 0u, 0u};
-        q[r][u] = in ? __builtin_nontemporal_load(reinterpret_cast<const u32x3_t*>(a.P + off)) : z;
-        if (SWIGLU) q3[r][u] = in ? __builtin_nontemporal_load(reinterpret_cast<const u32x3_t*>(a.P3 + off)) : z;
-      }
-    }
+    // The record is requested FIRST and every code load is unconditional, in the order gemv_body consumes the chunks: the waits
+    // then count down load by load (record, chunk 0, chunk 1, ...) and the decode of a chunk runs under the loads behind it.  With
+    // the record last, or with loads skipped under a branch, every chunk waits for the whole tile.  A chunk outside the matrix
+    // reads the nearest chunk inside it (row and column clamped) and is decoded without the base: exponents <= 15, finite, and it
+    // meets a zero of x (columns) or a row that is never stored, so the sums keep their bits.
     const size_t at = (((size_t)(r0 / RB) * nph + s0 / CU) * kW12Waves + wave) * 8 + (lane & 7);
     rec = a.R[at];
     if (SWIGLU) rec3 = a.R3[at];
+#pragma unroll
+    for (int u = 0; u < CU; u++) {
+      const int c = ((s0 + u) * kW12Waves + wave) * 64 + lane;
+      const int cc = c < nch ? c : nch - 1;
+#pragma unroll
+      for (int r = 0; r < RB; r++) {
+        const int rr = r0 + r < N ? r0 + r : N - 1;
+        const size_t off = ((size_t)rr * nch + cc) * 3;
+        q[r][u] = __builtin_nontemporal_load(reinterpret_cast<const u32x3_t*>(a.P + off));
+        if (SWIGLU) q3[r][u] = __builtin_nontemporal_load(reinterpret_cast<const u32x3_t*>(a.P3 + off));
+      }
+    }
   };
   auto chunk = [&](u32x3_t code, uint32_t bw, uint32_t rc, const uint4* dense, int r, int u) {
     const int c = ((ts0 + u) * kW12Waves + wave) * 64 + lane;
     const bool in = (ts0 + u < nstep) && c < nch && (tr0 + r < N);
-    uint4 d = w12_decode(code, in ? bw : 0u);  // (outside the matrix: zero codes and no base decode to zeros, the dense kernel's fill)
+    uint4 d = w12_decode<LAY>(code, in ? bw : 0u);  // (outside the matrix: no base, see issue; zero codes decode to zeros)
     const uint32_t cnt = __builtin_amdgcn_readlane(rc, 0);
     if (cnt != 0u) {  // wave-uniform
       if (cnt == kW12Overflow) {
@@ -127,6 +152,9 @@ __global__ __launch_bounds__(kW12Threads) void gemv_w12_kernel(GemvW12Args a) {
 }
 
 // ---- launch geometry.  The starting point is cc_gemv.hip's pick_cfg (the same loads in flight per lane, each a quarter shorter).
+//      Both layouts take it: for planar, w2 at 2 x 4 on 512 / 1024 workgroups measured 27.1 / 27.6 us against 28.1 at 4 x 4 and 20.6
+//      dense (with the record still requested last: DESIGN.md §2.17), and wo / wqkv already run the dense kernel's own geometry;
+//      that instantiation is not built.
 static GvCfg pick_w12_cfg(int N, int K, bool swiglu) {
   static int env_rb = -1, env_cu = -1, env_cap = 2048;
   if (env_rb < 0) {  // tuning hook: CC_GEMV_W12_CFG="RB,CU[,max workgroups]"
@@ -160,19 +188,40 @@ static int w12_xs(int K) {
   return nstep <= 2 ? 2 : nstep <= 8 ? 8 : 0;  // (rows beyond 8 steps per wave, K > 16384, are not served: CC_ERR_UNSUPPORTED)
 }
 
-static bool w12_cfg_built(bool swiglu, int xs, int rb, int cu) {
+static bool w12_cfg_built(int layout, bool swiglu, int xs, int rb, int cu) {
   const int key = (swiglu ? 100000 : 0) + xs * 1000 + rb * 10 + cu;
-  switch (key) {
-    case 2022: case 2042: case 8044: case 102022: case 108024: return true;
+  switch (key) {  // (the same list in both layouts)
+    case 2022: case 2042: case 8044: case 102022: case 108024: return layout == 0 || layout == kW12Planar;
     default: return false;
   }
 }
 
-template <bool SWIGLU, int RB, int CU, int XS>
+// the planar launch classes switched on by default (cc_w12_geometry): the SwiGLU pair and the LM head at K <= 4096, <true, 2, 2, 2>
+// and <false, 2, 2, 2> on 1024 workgroups — 33.2 us against 34.9 (layout 0) and 39.6 (dense), 123.7 against 134.9 and 156.3.
+// wqkv, wo and w2 lost to the dense kernel in this layout too (1.03x, 1.12x, 1.23x) and stay dense; K = 8192 is not switched on.
+static bool w12_planar_won(int nstep, bool swiglu, int N) { return nstep <= 2 && (swiglu || N >= 32768); }
+
+template <int LAY, bool SWIGLU, int RB, int CU, int XS>
 static void launch_w12_cfg(const GemvW12Args& a, hipStream_t st, int cap) {
   int blocks = (a.g.N + RB - 1) / RB;
   if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL((gemv_w12_kernel<SWIGLU, RB, CU, XS>), dim3(blocks), dim3(kW12Threads), 0, st, a);
+  hipLaunchKernelGGL((gemv_w12_kernel<LAY, SWIGLU, RB, CU, XS>), dim3(blocks), dim3(kW12Threads), 0, st, a);
+}
+
+// the layout every packed copy was written in, by the address of its codes: cc_gemv_fused_w12 refuses a copy handed in under the
+// other layout's id before it launches anything.  (Host memory only; an address packed again takes its new layout; codes that
+// cc_w12_pack of this process did not write are not known here and pass.)
+static std::mutex w12_reg_mu;
+static std::unordered_map<const void*, int> w12_reg;
+
+static void w12_register(const void* codes, int layout) {
+  std::lock_guard<std::mutex> g(w12_reg_mu);
+  w12_reg[codes] = layout;
+}
+static bool w12_layout_ok(const void* codes, int layout) {
+  std::lock_guard<std::mutex> g(w12_reg_mu);
+  const auto it = w12_reg.find(codes);
+  return it == w12_reg.end() || it->second == layout;
 }
 
 // ---- packer
@@ -188,11 +237,12 @@ __global__ __launch_bounds__(256) void w12_hist_kernel(const uint16_t* W, size_t
   if (h[threadIdx.x]) atomicAdd(&meta[kW12MetaHist + threadIdx.x], h[threadIdx.x]);
 }
 
-__global__ void w12_base_kernel(int32_t* meta, int nrec) {
+__global__ void w12_base_kernel(int32_t* meta, int nrec, int layout) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   long long best = -1;
   int base = 0;
-  for (int b = 0; b + 15 <= 255; b++) {  // base + 15 <= 255: the decode's index add never carries into the sign
+  // base + 15 <= 255: the decode's index add never carries into the sign.  Planar: even bases only (its index is exponent >> 1)
+  for (int b = 0; b + 15 <= 255; b += (layout == kW12Planar ? 2 : 1)) {
     long long s = 0;
     for (int i = 0; i < 16; i++) s += meta[kW12MetaHist + b + i];
     if (s > best) {
@@ -205,7 +255,8 @@ __global__ void w12_base_kernel(int32_t* meta, int nrec) {
 }
 
 // one wave per record: the RB x CU chunks per lane that gemv_w12_kernel's wave requests together
-__global__ __launch_bounds__(64) void w12_pack_kernel(const uint4* W, int N, int K, int RB, int CU, uint32_t* P, uint32_t* R, int32_t* meta) {
+__global__ __launch_bounds__(64) void w12_pack_kernel(const uint4* W, int N, int K, int RB, int CU, int layout, uint32_t* P, uint32_t* R,
+                                                      int32_t* meta) {
   __shared__ uint32_t rec[8];
   const int lane = threadIdx.x;
   const int nch = K / 8;
@@ -231,7 +282,14 @@ __global__ __launch_bounds__(64) void w12_pack_kernel(const uint4* W, int N, int
       const uint32_t bits = (wd[k >> 1] >> ((k & 1) * 16)) & 0xffffu;
       const int idx = (int)((bits >> 7) & 0xffu) - base;
       const bool esc = in && (idx < 0 || idx > 15);
-      if (!esc) {
+      if (!esc && layout == kW12Planar) {
+        if (in) {  // (base is even here: idx >> 1 = (exponent >> 1) - base / 2)
+          const uint32_t hi = (uint32_t)idx >> 1, sg = bits >> 15;
+          const int j = k & 3;
+          sm[k >> 2] |= (bits & 0xffu) << (j * 8);
+          ex |= k < 4 ? ((sg << 7) | hi) << (j * 8) : (hi << (j * 8 + 4)) | (sg << (((j + 1) & 3) * 8 + 3));
+        }
+      } else if (!esc) {
         sm[k >> 2] |= (((bits >> 8) & 0x80u) | (bits & 0x7fu)) << ((k & 3) * 8);
         ex |= (uint32_t)(in ? idx : 0) << ((k & 1) * 16 + (k >> 1) * 4);
       }
@@ -261,20 +319,32 @@ __global__ __launch_bounds__(64) void w12_pack_kernel(const uint4* W, int N, int
 
 }  // namespace
 
+// (the layout id travels in bits 8 .. 15 of a word whose low byte keeps its old meaning: 0 = the first layout, as before)
+static inline int w12_layout_of(int32_t word) { return (word >> 8) & 0xff; }
+
 extern "C" int cc_w12_geometry(int32_t N, int32_t K, int32_t swiglu, int32_t* out) {
-  if (!out || N <= 0 || K <= 0) return CC_ERR_BAD_ARG;
+  const int layout = w12_layout_of(swiglu);
+  const bool pair = (swiglu & 0xff) != 0;
+  if (!out || N <= 0 || K <= 0 || (swiglu >> 16) != 0 || (layout != 0 && layout != kW12Planar)) return CC_ERR_BAD_ARG;
   if (K % 8 || (size_t)K * 2 > 64 * 1024) return CC_ERR_UNSUPPORTED;
-  const GvCfg c = pick_w12_cfg(N, K, swiglu != 0);
+  const GvCfg c = pick_w12_cfg(N, K, pair);
   const int xs = w12_xs(K);
-  if (xs == 0 || c.cu > xs || c.cap <= 0 || !w12_cfg_built(swiglu != 0, xs, c.rb, c.cu)) return CC_ERR_UNSUPPORTED;
+  if (xs == 0 || c.cu > xs || c.cap <= 0 || !w12_cfg_built(layout, pair, xs, c.rb, c.cu)) return CC_ERR_UNSUPPORTED;
   out[0] = c.rb;
   out[1] = c.cu;
   out[2] = xs;
   out[3] = c.cap;
+  const int nstep = ((K / 8 + 63) / 64 + kW12Waves - 1) / kW12Waves;
+  if (layout == kW12Planar) {
+    // planar: the launch classes that MEASURED faster than both the dense kernel and the first layout, by more than the dense
+    // kernel's own spread (profiles/w12_planar_gemv.jsonl), in the regime measured: a grid that is full
+    const bool full = (long long)N >= (long long)c.rb * c.cap;
+    out[4] = (full && w12_planar_won(nstep, pair, N)) ? 1 : 0;
+    return CC_OK;
+  }
   // the launch classes that MEASURED faster than the dense kernel (the SwiGLU pair and the LM head at K = 4096,
   // <true, 2, 2, 2> and <false, 2, 2, 2> with 1024 workgroups); every other class is served but stays dense by default
-  const int nstep = ((K / 8 + 63) / 64 + kW12Waves - 1) / kW12Waves;
-  out[4] = (nstep <= 2 && (swiglu != 0 || N >= 32768)) ? 1 : 0;
+  out[4] = (nstep <= 2 && (pair || N >= 32768)) ? 1 : 0;
   return CC_OK;
 }
 
@@ -283,6 +353,9 @@ extern "C" size_t cc_w12_meta_words(void) { return kW12MetaHist + 256; }
 extern "C" int cc_w12_pack(const void* W, int32_t N, int32_t K, int32_t rb, int32_t cu, void* codes, void* records, void* meta,
                            cc_stream_t stream) {
   CC_ENTRY();
+  const int layout = w12_layout_of(rb);
+  if ((rb >> 16) != 0 || (layout != 0 && layout != kW12Planar)) return CC_ERR_BAD_ARG;
+  rb &= 0xff;
   if (!W || !codes || !records || !meta || N <= 0 || K <= 0 || rb <= 0 || cu <= 0 || rb * cu > 64) return CC_ERR_BAD_ARG;
   if (K % 8 || (size_t)K * 2 > 64 * 1024) return CC_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
@@ -297,10 +370,11 @@ extern "C" int cc_w12_pack(const void* W, int32_t N, int32_t K, int32_t rb, int3
   int hb = (int)((n + 256 * 64 - 1) / (256 * 64));
   if (hb > 2048) hb = 2048;
   hipLaunchKernelGGL(w12_hist_kernel, dim3(hb), dim3(256), 0, st, reinterpret_cast<const uint16_t*>(W), n, m);
-  hipLaunchKernelGGL(w12_base_kernel, dim3(1), dim3(64), 0, st, m, (int)nrec);
-  hipLaunchKernelGGL(w12_pack_kernel, dim3((unsigned)nrec), dim3(64), 0, st, reinterpret_cast<const uint4*>(W), N, K, rb, cu,
+  hipLaunchKernelGGL(w12_base_kernel, dim3(1), dim3(64), 0, st, m, (int)nrec, layout);
+  hipLaunchKernelGGL(w12_pack_kernel, dim3((unsigned)nrec), dim3(64), 0, st, reinterpret_cast<const uint4*>(W), N, K, rb, cu, layout,
                      reinterpret_cast<uint32_t*>(codes), reinterpret_cast<uint32_t*>(records), m);
   CC_LAUNCH_CHECK();
+  w12_register(codes, layout);
   return CC_OK;
 }
 
@@ -309,15 +383,20 @@ extern "C" int cc_gemv_fused_w12(const void* codes, const void* records, int32_t
                                  const void* norm_w, float eps, void* h_out, const void* bias, const void* freqs, int32_t rope_rows,
                                  int32_t head_dim, void* y, int32_t N, int32_t K, int32_t dtype, cc_stream_t stream) {
   CC_ENTRY();
+  const int layout = w12_layout_of(rb);
+  if ((rb >> 16) != 0 || (layout != 0 && layout != kW12Planar)) return CC_ERR_BAD_ARG;
+  rb &= 0xff;
   if (!codes || !records || !W || !x || !y || N <= 0 || K <= 0 || !cc_dt_ok(dtype)) return CC_ERR_BAD_ARG;
   if ((W3 != nullptr) != (codes3 != nullptr) || (W3 != nullptr) != (records3 != nullptr)) return CC_ERR_BAD_ARG;
   if (base < 0 || base > 240 || (W3 && (base3 < 0 || base3 > 240))) return CC_ERR_BAD_ARG;
+  if (layout == kW12Planar && ((base & 1) || (W3 && (base3 & 1)))) return CC_ERR_BAD_ARG;
+  if (!w12_layout_ok(codes, layout) || (codes3 && !w12_layout_ok(codes3, layout))) return CC_ERR_BAD_ARG;  // packed in the other layout
   if ((delta || h_out) && !norm_w) return CC_ERR_BAD_ARG;
   if (freqs && (W3 || rope_rows < 0 || rope_rows > N || head_dim <= 0 || (head_dim & 1) || (rope_rows % head_dim))) return CC_ERR_BAD_ARG;
   if (W3 && bias) return CC_ERR_BAD_ARG;
   if (dtype != CC_DT_BF16) return CC_ERR_UNSUPPORTED;
   int32_t geo[5];
-  const int rc = cc_w12_geometry(N, K, W3 != nullptr, geo);
+  const int rc = cc_w12_geometry(N, K, (W3 != nullptr ? 1 : 0) | (layout << 8), geo);
   if (rc != CC_OK) return rc;
   if (geo[0] != rb || geo[1] != cu) return CC_ERR_BAD_ARG;  // the records were laid out for another launch geometry
   GemvW12Args a;
@@ -326,16 +405,26 @@ extern "C" int cc_gemv_fused_w12(const void* codes, const void* records, int32_t
   a.P3 = reinterpret_cast<const uint32_t*>(codes3);
   a.R = reinterpret_cast<const uint32_t*>(records);
   a.R3 = reinterpret_cast<const uint32_t*>(records3);
-  a.bw = ((uint32_t)base << 7) | ((uint32_t)base << 23);
-  a.bw3 = ((uint32_t)base3 << 7) | ((uint32_t)base3 << 23);
+  if (layout == kW12Planar) {
+    a.bw = (uint32_t)(base >> 1) * 0x01010101u;
+    a.bw3 = (uint32_t)(base3 >> 1) * 0x01010101u;
+  } else {
+    a.bw = ((uint32_t)base << 7) | ((uint32_t)base << 23);
+    a.bw3 = ((uint32_t)base3 << 7) | ((uint32_t)base3 << 23);
+  }
   hipStream_t st = (hipStream_t)stream;
-  const int key = (W3 ? 100000 : 0) + geo[2] * 1000 + rb * 10 + cu;
+  const int key = layout * 1000000 + (W3 ? 100000 : 0) + geo[2] * 1000 + rb * 10 + cu;
   switch (key) {  // (w12_cfg_built's list)
-    case 2022: launch_w12_cfg<false, 2, 2, 2>(a, st, geo[3]); break;
-    case 2042: launch_w12_cfg<false, 4, 2, 2>(a, st, geo[3]); break;
-    case 8044: launch_w12_cfg<false, 4, 4, 8>(a, st, geo[3]); break;
-    case 102022: launch_w12_cfg<true, 2, 2, 2>(a, st, geo[3]); break;
-    case 108024: launch_w12_cfg<true, 2, 4, 8>(a, st, geo[3]); break;
+    case 2022: launch_w12_cfg<0, false, 2, 2, 2>(a, st, geo[3]); break;
+    case 2042: launch_w12_cfg<0, false, 4, 2, 2>(a, st, geo[3]); break;
+    case 8044: launch_w12_cfg<0, false, 4, 4, 8>(a, st, geo[3]); break;
+    case 102022: launch_w12_cfg<0, true, 2, 2, 2>(a, st, geo[3]); break;
+    case 108024: launch_w12_cfg<0, true, 2, 4, 8>(a, st, geo[3]); break;
+    case 1002022: launch_w12_cfg<kW12Planar, false, 2, 2, 2>(a, st, geo[3]); break;
+    case 1002042: launch_w12_cfg<kW12Planar, false, 4, 2, 2>(a, st, geo[3]); break;
+    case 1008044: launch_w12_cfg<kW12Planar, false, 4, 4, 8>(a, st, geo[3]); break;
+    case 1102022: launch_w12_cfg<kW12Planar, true, 2, 2, 2>(a, st, geo[3]); break;
+    case 1108024: launch_w12_cfg<kW12Planar, true, 2, 4, 8>(a, st, geo[3]); break;
     default: return CC_ERR_UNSUPPORTED;
   }
   CC_LAUNCH_CHECK();

@@ -92,17 +92,21 @@ class W12Packed:
     """The lossless 12-bit packed copy of one dense bf16 weight (cc_w12_pack; format: include/coldcompress.h).  `codes` uint32
     [N, K / 8, 3], `records` uint32 [records, 8], `base` the first exponent of the window, (`rb`, `cu`, `xs`, `cap`) the launch
     geometry it was packed for (the records follow `rb` and `cu`); `n_overflow` records hold more than 7 escapes (their tiles are
-    read from the dense tensor), `n_escapes` weights lie outside the window."""
-    __slots__ = ("codes", "records", "base", "rb", "cu", "xs", "cap", "n_records", "n_overflow", "n_escapes")
+    read from the dense tensor), `n_escapes` weights lie outside the window.  `layout`: 0 (sign + mantissa bytes and 4-bit exponent
+    indices) or W12_PLANAR (low bytes and a dword of high-byte fields; `base` is even); a copy is tied to it as to (`rb`, `cu`)."""
+    __slots__ = ("codes", "records", "base", "rb", "cu", "xs", "cap", "n_records", "n_overflow", "n_escapes", "layout")
+
+
+W12_PLANAR = 1  # layout ids (include/coldcompress.h): they travel in bits 8 .. 15 of the rb / swiglu words
 
 
 W12_MAX_OVERFLOW = 0.01  # a tensor with more overflowing records than this share stays on cc_gemv_fused
 _W12_MARGIN = 1 << 30  # free device memory kept beyond a packed copy
-# (data_ptr, _version, shape, device, swiglu) -> (W12Packed, or None: refused, unsupported or no room, and not tried again for this
+# (data_ptr, _version, shape, device, swiglu, layout) -> (W12Packed, or None: refused, unsupported or no room, and not tried again for this
 # version of the weight; weak reference to the weight: while it lives its storage does, so the address cannot have been given to
 # another tensor)
 _w12_cache = {}
-_w12_geo = {}  # (N, K, swiglu) -> cc_w12_geometry's answer
+_w12_geo = {}  # (N, K, swiglu, layout) -> cc_w12_geometry's answer
 _w12_drops = 0  # moves whenever a packed copy is dropped: a captured graph may still hold its address (w12_epoch)
 _w12_warned = False
 
@@ -111,13 +115,14 @@ def w12_enabled():
     return os.environ.get("CC_W12", "1") != "0"
 
 
-def w12_geometry(N, K, swiglu=False):
-    """(RB, CU, input chunks per lane, most workgroups, faster) of the packed GEMV's launch for this shape and form, or None:
-    unsupported.  `faster`: 1 when that launch class measured faster than the dense kernel, else 0."""
-    key = (int(N), int(K), bool(swiglu))
+def w12_geometry(N, K, swiglu=False, layout=0):
+    """(RB, CU, input chunks per lane, most workgroups, faster) of the packed GEMV's launch for this shape, form and code layout, or
+    None: unsupported.  `faster`: 1 when that launch class measured faster than the dense kernel (layout 0) resp. than the dense
+    kernel and layout 0 (W12_PLANAR), else 0."""
+    key = (int(N), int(K), bool(swiglu), int(layout))
     if key not in _w12_geo:
         out = (C.c_int32 * 5)()
-        ok = _abi.lib()["cc_w12_geometry"](key[0], key[1], int(key[2]), out) == _abi.CC_OK
+        ok = _abi.lib()["cc_w12_geometry"](key[0], key[1], int(key[2]) | key[3] << 8, out) == _abi.CC_OK
         _w12_geo[key] = tuple(out) if ok else None
     return _w12_geo[key]
 
@@ -127,12 +132,12 @@ def w12_nbytes(N, K, rb, cu):
     return N * K * 3 // 2 + -(-N // rb) * -(-nstep // cu) * 4 * 32
 
 
-def w12_pack(weight, swiglu=False, refuse=True):
-    """Pack a dense bf16 [N, K] device tensor for the launch geometry of its shape (`swiglu`: as one of the W / W3 pair) ->
+def w12_pack(weight, swiglu=False, refuse=True, layout=0):
+    """Pack a dense bf16 [N, K] device tensor for the launch geometry of its shape (`swiglu`: as one of the W / W3 pair) in `layout` ->
     W12Packed, or None when the shape is unsupported or (`refuse`) more than W12_MAX_OVERFLOW of the records overflow.
     Synchronises (reads the packer's counts back): not for use under stream capture."""
     N, K = weight.shape
-    geo = w12_geometry(N, K, swiglu)
+    geo = w12_geometry(N, K, swiglu, layout)
     if geo is None or weight.dtype != torch.bfloat16 or not (weight.is_cuda and weight.is_contiguous()) or N * K >= 1 << 31:
         return None
     rb, cu = geo[0], geo[1]
@@ -142,10 +147,11 @@ def w12_pack(weight, swiglu=False, refuse=True):
     p.codes = torch.empty((N, K // 8 * 3), dtype=torch.int32, device=weight.device)
     p.records = torch.empty((nrec, 8), dtype=torch.int32, device=weight.device)
     meta = torch.empty((int(_abi.lib()["cc_w12_meta_words"]()),), dtype=torch.int32, device=weight.device)
-    _abi.call("cc_w12_pack", _p(weight), N, K, rb, cu, _p(p.codes), _p(p.records), _p(meta), _stream())
+    _abi.call("cc_w12_pack", _p(weight), N, K, rb | layout << 8, cu, _p(p.codes), _p(p.records), _p(meta), _stream())
     m = meta[:4].tolist()
     p.base, p.n_records, p.n_overflow, p.n_escapes = m
     p.rb, p.cu, p.xs, p.cap = geo[:4]
+    p.layout = layout
     if refuse and p.n_overflow > W12_MAX_OVERFLOW * p.n_records:
         return None
     return p
@@ -157,16 +163,20 @@ def _w12_drop(key):
         _w12_drops += 1
 
 
-def _w12_get(weight, swiglu, force=False):
+def _w12_get(weight, swiglu, force=False, layout=None):
     """The packed copy of `weight`, built at its first eager use; None: take the plain path (a launch class that did not measure
     faster than the dense kernel, unless `force`; under capture before a copy exists; refused by the packer; unsupported shape; no
-    room).  Keyed on the storage and its version counter: an in-place change of the weight drops the copy."""
+    room).  `layout` None: planar where its launch class measured faster than the dense kernel and layout 0, else layout 0.  Keyed
+    on the storage, its version counter and the layout: an in-place change of the weight drops the copy."""
     global _w12_warned
     N, K = weight.shape
-    geo = w12_geometry(N, K, swiglu)
+    if layout is None:
+        planar = w12_geometry(N, K, swiglu, W12_PLANAR)
+        layout = W12_PLANAR if (planar is not None and planar[4]) else 0
+    geo = w12_geometry(N, K, swiglu, layout)
     if geo is None or not (force or geo[4]):
         return None
-    key = (weight.data_ptr(), weight._version, tuple(weight.shape), weight.device, swiglu)
+    key = (weight.data_ptr(), weight._version, tuple(weight.shape), weight.device, swiglu, layout)
     hit = _w12_cache.get(key)
     if hit is not None and hit[1]() is not None:
         return hit[0]
@@ -178,7 +188,7 @@ def _w12_get(weight, swiglu, force=False):
     free = torch.cuda.mem_get_info(weight.device)[0] + torch.cuda.memory_reserved(weight.device) - torch.cuda.memory_allocated(weight.device)
     p = None
     if free >= w12_nbytes(N, K, geo[0], geo[1]) + _W12_MARGIN:
-        p = w12_pack(weight, swiglu)
+        p = w12_pack(weight, swiglu, layout=layout)
     elif not _w12_warned:
         _w12_warned = True
         warnings.warn("cold_compress_amd: not enough free device memory for the 12-bit packed weight copies; the remaining dense "
@@ -268,13 +278,15 @@ def gemv_fused(weight, x, w3=None, delta=None, norm_weight=None, eps=1e-5, h_out
     y = torch.empty((N,), dtype=weight.dtype, device=weight.device)
     if w12 and weight.dtype == torch.bfloat16 and w12_enabled() and (w3 is None or w3.dtype == torch.bfloat16):
         # the lossless 12-bit packed copies of the weights: the same bits from three quarters of the bytes (cc_gemv_fused_w12).
-        # w12=True: where that launch class measured faster than the dense kernel; w12="force": wherever the kernel serves the shape
-        force = w12 == "force"
-        pk = _w12_get(weight, w3 is not None, force)
-        pk3 = _w12_get(w3, True, force) if (w3 is not None and pk is not None) else None
+        # w12=True: where that launch class measured faster than the dense kernel, in the layout that measured fastest there;
+        # w12="force" / "force-planar": wherever the kernel serves the shape, in layout 0 / the planar layout
+        force = w12 in ("force", "force-planar")
+        lay = {"force": 0, "force-planar": W12_PLANAR}.get(w12)
+        pk = _w12_get(weight, w3 is not None, force, lay)
+        pk3 = _w12_get(w3, True, force, lay) if (w3 is not None and pk is not None) else None
         if pk is not None and (w3 is None or pk3 is not None):
             _abi.call("cc_gemv_fused_w12", _p(pk.codes), _p(pk.records), pk.base, _p(pk3.codes) if pk3 else None,
-                      _p(pk3.records) if pk3 else None, pk3.base if pk3 else 0, pk.rb, pk.cu, _p(weight), _p(w3), _p(xc), _p(dc),
+                      _p(pk3.records) if pk3 else None, pk3.base if pk3 else 0, pk.rb | pk.layout << 8, pk.cu, _p(weight), _p(w3), _p(xc), _p(dc),
                       _p(norm_weight), float(eps), _p(h_out), _p(bias), _p(fc), int(rope_rows), int(head_dim), _p(y), N, K,
                       _DT[weight.dtype], _stream())
             return y

@@ -137,7 +137,7 @@ class FeedForward(nn.Module):
             delta, norm, h_out = fused
             g = glue.gemv_fused(self.w1.weight, x, w3=self.w3.weight, delta=delta, norm_weight=norm.weight, eps=norm.eps, h_out=h_out,
                                 w12=True, **{**_quant(self.w1), **_quant(self.w3, "3")})
-            return glue.gemv_fused(self.w2.weight, g, **_quant(self.w2)).view(1, 1, -1)
+            return glue.gemv_fused(self.w2.weight, g, w12=True, **_quant(self.w2)).view(1, 1, -1)
         return self.w2(glue.silu_mul(self.w1(x), self.w3(x)))
 
 
@@ -202,9 +202,9 @@ class Attention(nn.Module):
                 # ONE launch for norm + wqkv + RoPE + update_kv + attention + update_state: the cache's K / V rows stream in the
                 # shadow of the projection's weights (q / k / v bit-identical to the two launches below)
                 y = cache.decode_step_qkv(self.wqkv.weight, self.wqkv.bias, x, delta, norm.weight, norm.eps, h_out, freqs_cis, input_pos, HQ)
-                return glue.gemv_fused(self.wo.weight, y, **_quant(self.wo)).view(1, 1, -1)
+                return glue.gemv_fused(self.wo.weight, y, w12=True, **_quant(self.wo)).view(1, 1, -1)
             qkv = glue.gemv_fused(self.wqkv.weight, x, delta=delta, norm_weight=norm.weight, eps=norm.eps, h_out=h_out,
-                                  bias=self.wqkv.bias, freqs=freqs_cis, rope_rows=(HQ + H) * D, head_dim=D, **_quant(self.wqkv))
+                                  bias=self.wqkv.bias, freqs=freqs_cis, rope_rows=(HQ + H) * D, head_dim=D, w12=True, **_quant(self.wqkv))
             q = qkv[: HQ * D].view(1, HQ, 1, D)
             k = qkv[HQ * D: (HQ + H) * D].view(1, H, 1, D)
             v = qkv[(HQ + H) * D:].view(1, H, 1, D)
@@ -222,7 +222,7 @@ class Attention(nn.Module):
             cache.update_kv(input_pos, k, v, True, input_ids=input_ids)
             cache.update_state(input_pos, k, v, True, attn, input_ids=input_ids)
         if fused is not None:
-            return glue.gemv_fused(self.wo.weight, y, **_quant(self.wo)).view(1, 1, -1)
+            return glue.gemv_fused(self.wo.weight, y, w12=True, **_quant(self.wo)).view(1, 1, -1)
         y = y.transpose(1, 2).contiguous().view(bsz, seqlen, self.dim)
         return self.wo(y)
 

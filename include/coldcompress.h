@@ -813,7 +813,22 @@ int cc_gemv_fused_multi(const void* W, const void* W3, const void* x, const void
  * cc_gemv_fused_w12: cc_gemv_fused's arguments behind the packed copy of W (and of W3, when W3 != NULL) and the (rb, cu) they were
  *             packed for; CC_ERR_BAD_ARG when that is not cc_w12_geometry's answer for this call.  W and W3 stay arguments: tiles
  *             whose record overflowed are read from them.  dtype: CC_DT_BF16 (others: CC_ERR_UNSUPPORTED).  A plain grid, no
- *             atomics; arguments are validated before any launch: an error writes nothing. */
+ *             atomics; arguments are validated before any launch: an error writes nothing.
+ *
+ * A packed copy exists in one of two code LAYOUTS.  The layout id travels in bits 8 .. 15 of the `rb` word of cc_w12_pack and
+ * cc_gemv_fused_w12 and of the `swiglu` word of cc_w12_geometry (the low byte keeps its meaning; higher bits must be 0; an id other
+ * than 0 or 1: CC_ERR_BAD_ARG).  Id 0 is the layout above.  Id 1, "planar", keeps chunk index, records, overflow rule and the
+ * dense fallback and changes the 12 bytes of a chunk, with e the 8-bit exponent, s the sign, `base` EVEN and B = base / 2:
+ *   dword 0, 1  byte k = the low byte of bf16 weight k resp. 4 + k as it is (e & 1 in bit 7, the mantissa below)
+ *   dword 2     byte k = s of weight k << 7 | ((e >> 1) - B) of weight 4 + k << 4 | s of weight 4 + ((k + 3) & 3) << 3 |
+ *               ((e >> 1) - B) of weight k — the sign of weight 4 + k sits in bit 3 of byte (k + 1) & 3
+ * In-window is base <= e < base + 16 as before; cc_w12_pack searches even bases only for it, and cc_gemv_fused_w12 rejects an odd
+ * base.  The kernel decodes a chunk in nine operations (mask 0x87878787 and a bytewise add of B on dword 2 and on dword 2 rotated
+ * right by 4 give the eight high bytes; four byte permutes interleave them with the low bytes) against 24 for layout 0.
+ * cc_w12_geometry answers per layout: its own (RB, CU, chunks, workgroups) and, as out[4], whether that layout's launch class
+ * measured faster than cc_gemv_fused AND than layout 0 on MI355X, in the regime measured (N >= RB x workgroups: a full grid).
+ * A copy is tied to its layout as to (rb, cu): cc_w12_pack notes the layout by the address of `codes` (host memory, this
+ * process), and cc_gemv_fused_w12 returns CC_ERR_BAD_ARG, before any launch, for codes handed in under the other id. */
 int cc_w12_geometry(int32_t N, int32_t K, int32_t swiglu, int32_t* out);
 size_t cc_w12_meta_words(void);
 int cc_w12_pack(const void* W, int32_t N, int32_t K, int32_t rb, int32_t cu, void* codes, void* records, void* meta,
