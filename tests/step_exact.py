@@ -1,4 +1,5 @@
 """Known-answer inputs for the fused decode steps (decode_attn_split_mfma_kernel in all its instantiations, its two-launch twin, the
+VALU streaming pass decode_attn_split_kernel<T, D, RT> that serves every fp32 cache and every 16-bit head_dim below 128, the
 combine kernel; csrc/cc_attn_decode.hip, cc_attn_decode_kernels.h) and for the three-call sequence they replace.  A helper, not a
 test: tests/test_step_exact_host.py holds the oracle's twins to these answers on the CPU, through the real cache classes, and shows
 that the comparison has teeth (FAULTS below); tests/test_gpu_step_exact.py holds the kernels to them on the device.  CPU tensors only.
@@ -9,8 +10,9 @@ the rounded-score table and the dtype spacing only.  The drivers at the end (mak
 touches cold_compress_amd.
 
 A. SELECTOR REPLAYS.  Token t (its position) has the +-1 code word of t over nbits = ceil(log2(T + steps)) bits as its key, each bit
-   repeated D // nbits times, the remaining dimensions +1 (prefill_exact.code_words).  Query head j is amp * code(sel[j]), amp = 128
-   (256 for the fp32 / D = 16 case, where 128 leaves a gap of 128 only; fp32 holds 256 * 16 exactly).  Every q . k is amp * n with an
+   repeated D // nbits times, the remaining dimensions +1 (prefill_exact.code_words).  Query head j is amp * code(sel[j]); amp starts at
+   128 and doubles while the measured gap is below GAP_MIN and amp * D < 16384 (128 at D = 128; 256 or 512 at small head dims, where
+   few repeats of a code bit and a large scale leave 128 a gap of 128 only).  Every q . k is amp * n with an
    integer |n| <= D: exact in fp32 in any order, exact in bf16, exact and finite in fp16.  The dtype-rounded score of the selected key
    exceeds every other live key's by `gap`, MEASURED per case and asserted >= 150: exp(x - M) is then 0 in fp32 under any rounding or
    flush mode, every unselected probability is +0, the softmax sum is 1 and the selected probability is 1.  So, per step:
@@ -28,7 +30,8 @@ A. SELECTOR REPLAYS.  Token t (its position) has the +-1 code word of t over nbi
    pos, mask, K, V, cache_cts, num, denom, attn_counter and key_norm are compared as bit patterns after every step.
    What the simulator chooses is described at Sim._select and Case._seed_history.
 
-B. RAMP STEPS.  One decode_step from a hand-set state.  Small integer entries plus one "position" dimension, scale 2^-3: every
+B. RAMP STEPS (16-bit dtypes; D = 128, and 64 / 32 / 16 behind the VALU pass).  One decode_step from a hand-set state.  Small integer
+   entries plus one "position" dimension, scale 2^-3 at every D: every
    rounded score is ONE value on the device and here.  Reference: ramp_reference, a float64 evaluation of the contract.  Bounds:
    y: 1e-3 + 2 ulp_of(dtype) max|y_ref|; history increment per element: mean over the group's heads of step(p_ref) + step(gm_ref)
    (step = the dtype's spacing there, the smallest subnormal at 0).  ONE derived widening: the decode kernels' exponentials
@@ -65,7 +68,7 @@ def bits(t):
 
 
 # ------------------------------------------------------------------------------------------------ the launch plan, mirrored
-# plan() copies these lines of csrc: when one changes, update the mirror and the case table of DESIGN 2.18.
+# plan() copies these lines of csrc: when one changes, update the mirror and the case tables of DESIGN 2.18 and 2.23.
 MIRRORED_LINES = {
     "cc_attn_decode.hip": [
         "constexpr int kMaxSplit = 512;", "constexpr int kNW = 4;", "constexpr int kU = 4;",
@@ -135,10 +138,9 @@ class Case:
         self.R = HQ // H
         assert self.R * H == HQ
         self.T = S if fill == "brim" else S - 3 if fill == "minus3" else (70 if S >= 130 else 20)
-        self.id = f"{policy}-{DT_NAME[dt]}-H{H}-HQ{HQ}-S{S}-{fill}-{hist}"
+        self.id = f"{policy}-{DT_NAME[dt]}-H{H}-HQ{HQ}-S{S}-{fill}-{hist}" + (f"-D{D}" if D != 128 else "")
         self.g, self.w = (0 if policy == "full" else G_TOK), W_REC
         self.Hp = H if policy in ("hh", "l2") else 1
-        self.amp = 128 if D == 128 else 256
         self.scale = P.default_scale(D)
         self.plan = plan(HQ, H, S, D, dt, policy)
         L = self.L = self.T + steps
@@ -162,25 +164,33 @@ class Case:
         v = torch.where(v.abs() < 2.0 ** -6, torch.copysign(torch.tensor(2.0 ** -6), v), v)
         self.v_all = v.to(dt)
         self.gm_table = _gm_table(self.R, dt)
+        # amp: 128, doubled while the measured gap is below GAP_MIN and the largest product still doubles within 16384 (128 at D = 128)
+        self.amp = 128
+        while self._gap() < GAP_MIN and self.amp * D < 16384:
+            self.amp *= 2
         self._measure()
         self._seed_history(rng)
 
-    def _measure(self):
-        """The gap on the dtype-rounded scores, and the exactness the construction rests on."""
-        D, rep, amp, dt = self.D, self.rep, self.amp, self.dt
-        n = D - 2 * rep * np.arange(0, self.nb + 1)  # q . k / amp by Hamming distance
-        assert amp * D < (1 << 24) and amp * D <= 16384
-        for m in range(-D, D + 1):  # amp * n exact in the dtype
-            assert float(torch.tensor(float(amp * m), dtype=torch.float64).to(dt)) == float(amp * m)
+    def _gap(self):
+        """The dtype-rounded score of the selected key minus the largest one of any other key, at the present amp."""
+        n = self.D - 2 * self.rep * np.arange(0, self.nb + 1)  # q . k / amp by Hamming distance
         top = None
         rest = []
         for e in sorted(set(self.e.reshape(-1).tolist())):
-            sc = P.rounded_scores(n * 2.0 ** -e, amp, self.scale, dt)
+            sc = P.rounded_scores(n * 2.0 ** -e, self.amp, self.scale, self.dt)
             assert np.isfinite(sc).all()
             if e == 0:
                 top, sc = sc[0], sc[1:]
             rest.append(sc)
-        self.gap = float(top - np.concatenate(rest).max())
+        return float(top - np.concatenate(rest).max())
+
+    def _measure(self):
+        """The gap on the dtype-rounded scores, and the exactness the construction rests on."""
+        D, amp, dt = self.D, self.amp, self.dt
+        assert amp * D < (1 << 24) and amp * D <= 16384
+        for m in range(-D, D + 1):  # amp * n exact in the dtype
+            assert float(torch.tensor(float(amp * m), dtype=torch.float64).to(dt)) == float(amp * m)
+        self.gap = self._gap()
         assert self.gap >= GAP_MIN, (self.id, self.gap)
         assert bool((self.v_all.double().abs() >= 2.0 ** -6).all()) and bool(torch.isfinite(self.v_all.double()).all())
         if self.policy == "l2":  # norm roundings are unique: four fp32 ulps either way round to the same dtype value
@@ -233,8 +243,8 @@ class Case:
 
 # the one-fault mutants of the simulator (tests/test_step_exact_host.py shows which cases reject each)
 FAULTS = ("stale_k", "stale_v", "tie_high", "tie_chunk", "recent_gt", "global_off", "denom_live", "no_zero", "stale_hist", "head_mod",
-          "drop_last", "no_rescale", "masked_weight", "cts_skip")
-_ATTN_FAULTS = ("stale_k", "stale_v", "head_mod", "drop_last", "no_rescale", "masked_weight")
+          "drop_last", "no_rescale", "masked_weight", "cts_skip", "dup_tail")
+_ATTN_FAULTS = ("stale_k", "stale_v", "head_mod", "drop_last", "no_rescale", "masked_weight", "dup_tail")
 
 
 def attend_dense(q, K, V, mask, scale, dt, rps, R, fault=None):
@@ -262,6 +272,10 @@ def attend_dense(q, K, V, mask, scale, dt, rps, R, fault=None):
                 parts.append((lo, hi, None, torch.ones(hi - lo, dtype=torch.float64)))
             else:
                 parts.append((lo, hi, m, torch.exp(x - m)))
+            if fault == "dup_tail" and hi - lo < rps and m != float("-inf"):
+                # the VALU pass loads the rows past the end of a ragged split as copies of its last row (clamped to row_end - 1):
+                # here one such copy carries weight — it enters l and O, and no slot's probability
+                parts.append((hi - 1, hi, m, torch.exp(x[-1:] - m)))
         M = max(m for _, _, m, _ in parts if m is not None)
         Lsum, O = 0.0, torch.zeros(D, dtype=torch.float64)
         ws = []
@@ -270,7 +284,7 @@ def attend_dense(q, K, V, mask, scale, dt, rps, R, fault=None):
             ws.append(w)
             Lsum += w * float(e.sum())
             O += w * (e @ V[h, lo:hi])
-        for (lo, hi, m, e), w in zip(parts, ws):
+        for (lo, hi, m, e), w in list(zip(parts, ws))[::-1]:  # (last to first: dup_tail's copy is overwritten by the row itself)
             p[j, lo:hi] = w * e / Lsum
         y[j] = O / Lsum
     p = _rnd(p, dt)
@@ -372,6 +386,8 @@ class Sim:
             live_last = np.nonzero(ok[last0:])[0]
             ll = last0 + int(live_last[-1]) if len(live_last) else -1
             pairs = [(15, 16), (63, 64), (127, 128), (rps - 1, rps), (last0 - 1, ll), (0, S - 1), (c.T - 2, c.T - 1), (2 * rps - 1, 2 * rps)]
+            if pl["nt"] == 0 and rps > pl["rpi"]:  # the VALU pass with several iterations of its row loop per split: their boundary
+                pairs.append((pl["rpi"] - 1, pl["rpi"]))
             cand = [s for pr in pairs for s in pr if 0 <= s < S and ok[s]]
             every = np.nonzero(ok)[0]
             assert len(every), (c.id, i, h)
@@ -468,11 +484,41 @@ ROW_WIDE = [(16, 64, 1280), (16, 128, 1290)]
 ROW_TILES = [(8, 32, 4160), (8, 32, 16448), (8, 64, 32832)]
 ROW_L2 = [(2, 4, 130), (8, 32, 200), (16, 64, 1280)]
 FILLS = ("brim", "minus3", "sparse")
-# (H, HQ, S) -> (waves, tiles per wave in the single launch (0: two launches only), the XCD-L2 transport possible)
-INTENDED = {(2, 2, 67): (4, 1, False), (2, 4, 130): (4, 1, False), (3, 12, 130): (4, 1, False), (1, 8, 200): (4, 1, False),
-            (8, 32, 200): (4, 1, True), (8, 64, 130): (4, 1, True), (16, 64, 1280): (8, 1, True), (16, 128, 1290): (8, 1, True),
-            (8, 32, 4160): (4, 2, True), (8, 32, 16448): (4, 5, True), (8, 64, 32832): (4, 9, True), (4, 28, 130): (4, 0, False),
-            (2, 4, 77): (4, 0, False)}
+# the VALU streaming pass (decode_attn_split_kernel<T, D, RT, 4, 4> + decode_attn_combine_kernel): every fp32 cache and every 16-bit
+# cache with head_dim 16 / 32 / 64; two launches only.  (policy, dtype, H, HQ, S, D), one row per (dtype, D), RT = 4, 2, 1
+VALU_SHAPES = [
+    ("hh", BF, 2, 8, 130, 64), ("rg", BF, 3, 6, 67, 64), ("hh", BF, 32, 32, 2100, 64),
+    ("hh", HF, 2, 8, 8300, 64), ("full", HF, 2, 12, 130, 64), ("hh", HF, 2, 14, 130, 64),
+    ("hh", BF, 4, 48, 67, 32), ("rg", BF, 3, 6, 67, 32), ("hh", BF, 2, 2, 258, 32),
+    ("hh", HF, 2, 8, 258, 32), ("hh", HF, 2, 4, 258, 32), ("full", HF, 1, 7, 130, 32),
+    ("hh", BF, 2, 8, 515, 16), ("full", BF, 2, 4, 515, 16), ("hh", BF, 1, 1, 2200, 16),
+    ("rg", HF, 1, 4, 67, 16), ("hh", HF, 3, 6, 67, 16), ("rg", HF, 2, 2, 77, 16),
+    ("hh", F32, 16, 128, 600, 128), ("full", F32, 1, 8, 35, 128), ("rg", F32, 3, 6, 67, 128), ("hh", F32, 2, 2, 27, 128),
+    ("hh", F32, 2, 8, 130, 64), ("full", F32, 3, 6, 61, 64), ("hh", F32, 1, 7, 130, 64),
+    ("hh", F32, 2, 8, 130, 32), ("rg", F32, 3, 6, 258, 32), ("hh", F32, 2, 2, 67, 32),
+    ("hh", F32, 2, 8, 258, 16), ("rg", F32, 3, 6, 67, 16), ("hh", F32, 2, 4, 77, 16), ("hh", F32, 1, 3, 515, 16),
+]
+# (element size, D, H, HQ, S) -> (waves, tiles per wave in the single launch (0: two launches only), the XCD-L2 transport possible)
+INTENDED = {(2, 128) + k: v for k, v in {
+    (2, 2, 67): (4, 1, False), (2, 4, 130): (4, 1, False), (3, 12, 130): (4, 1, False), (1, 8, 200): (4, 1, False),
+    (8, 32, 200): (4, 1, True), (8, 64, 130): (4, 1, True), (16, 64, 1280): (8, 1, True), (16, 128, 1290): (8, 1, True),
+    (8, 32, 4160): (4, 2, True), (8, 32, 16448): (4, 5, True), (8, 64, 32832): (4, 9, True), (4, 28, 130): (4, 0, False)}.items()}
+INTENDED.update({(4 if dt == F32 else 2, D, H, HQ, S): (4, 0, False) for (_, dt, H, HQ, S, D) in VALU_SHAPES})
+
+
+def intended(dt, D, H, HQ, S):
+    return INTENDED[(4 if dt == F32 else 2, D, H, HQ, S)]
+
+
+def valu_geometry(dt, D):
+    """What decode_attn_split_kernel<T, D, RT, 4, 4> derives from sizeof(T) and D: VEC elements per 16-byte load, LPR lanes per
+    row, RPW rows per wave load, rpi rows per workgroup iteration, NP pieces of the row-group partials, NG row groups to merge."""
+    es = 4 if dt == F32 else 2
+    vec = 16 // es
+    lpr = D // vec
+    rpw = 64 // lpr
+    return dict(es=es, vec=vec, lpr=lpr, rpw=rpw, rpi=rpw * 16, np=2 if es == 2 else 1, ng=4 * rpw,
+                passes={rt: -(-rt * 4 // lpr) for rt in (1, 2, 4)})
 
 
 def shape_list():
@@ -486,13 +532,14 @@ def shape_list():
                 out.append((pol, dt, H, HQ, S, 128))
         for (H, HQ, S) in ROW_L2:
             out.append(("l2", dt, H, HQ, S, 128))
-    out.append(("hh", F32, 2, 4, 77, 16))
-    return out
+    return out + VALU_SHAPES
 
 
 def shape_id(t):
     pol, dt, H, HQ, S, D = t
-    return f"{pol}-{DT_NAME[dt]}-{H}-{HQ}-{S}"
+    if D == 128 and dt != F32 or t == ("hh", F32, 2, 4, 77, 16):  # (the ids from before the VALU table)
+        return f"{pol}-{DT_NAME[dt]}-{H}-{HQ}-{S}"
+    return f"{pol}-{DT_NAME[dt]}-{H}-{HQ}-{S}-D{D}"
 
 
 def cases_of(t, steps=None):
@@ -616,6 +663,10 @@ def run_replay(c, form, dev, put=None, sync=None, dense=False, full_kv_every_ste
 RAMP_SCALE = 2.0 ** -3
 RAMP_VARIANTS = ("up", "down", "new_max", "last_live", "steep")
 RAMP_SHAPES = ROW_4WAVE + ROW_WIDE + ROW_TILES
+# (H, HQ, S, D): the VALU pass at 16-bit head dims 64 / 32 / 16 — its only cases with fractional softmax weights (the rescale across
+# two iterations of the row loop, the LDS merge of up to 128 row groups with different maxima).  The scale stays RAMP_SCALE, passed
+# explicitly (it is the default scale at D = 64 only); keys in {-1, 0, 1} plus the position dimension fit any D >= 2
+RAMP_VALU_SHAPES = [(2, 8, 130, 64), (32, 32, 2100, 64), (3, 6, 67, 32), (2, 8, 515, 16)]
 
 
 class RampCase:
@@ -633,13 +684,12 @@ class RampCase:
 
     policy, hist = "hh", "ramp"
 
-    def __init__(self, dt, H, HQ, S, variant, fill, seed=0):
-        assert variant in RAMP_VARIANTS and fill in ("brim", "sparse")
-        D = 128
+    def __init__(self, dt, H, HQ, S, variant, fill, seed=0, D=128):
+        assert variant in RAMP_VARIANTS and fill in ("brim", "sparse") and D >= 2
         self.dt, self.H, self.HQ, self.S, self.D, self.variant, self.fill = dt, H, HQ, S, D, variant, fill
         self.R, self.Hp, self.g, self.w, self.scale = HQ // H, H, G_TOK, W_REC, RAMP_SCALE
         self.T = T = S if fill == "brim" else (70 if S >= 130 else 20)
-        self.id = f"ramp-{DT_NAME[dt]}-H{H}-HQ{HQ}-S{S}-{variant}-{fill}"
+        self.id = f"ramp-{DT_NAME[dt]}-H{H}-HQ{HQ}-S{S}-{variant}-{fill}" + (f"-D{D}" if D != 128 else "")
         self.plan = plan(HQ, H, S, D, dt)
         rng = np.random.default_rng(4241 * seed + 17 * S + HQ + 5 * RAMP_VARIANTS.index(variant) + (fill == "sparse"))
         k = rng.integers(-1, 2, (H, T + 1, D)).astype(np.float32)
@@ -721,8 +771,8 @@ def ramp_reference(c):
 
 
 def ramp_cases(shape, dt, variant):
-    H, HQ, S = shape
-    return [RampCase(dt, H, HQ, S, variant, fill, seed=n) for n, fill in enumerate(("brim", "sparse"))]
+    H, HQ, S, D = tuple(shape) + ((128,) if len(shape) == 3 else ())
+    return [RampCase(dt, H, HQ, S, variant, fill, seed=n, D=D) for n, fill in enumerate(("brim", "sparse"))]
 
 
 def check_ramp(c, kv, y, where):

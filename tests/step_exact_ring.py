@@ -10,7 +10,8 @@ shares no code with the kernels, the oracle or tests/attn_ref.py.  From tests/st
 float64 evaluation of the attention contract the small cases are held to), GAP_MIN, ULP and MIRRORED_LINES; from
 tests/prefill_exact.py the code words and the rounded-score table.  The drivers at the end are the only users of cold_compress_amd.
 
-INPUTS (the selector construction of step_exact, section A).  Keys are +-1 code words, queries 128 x a code word, D = 128; the gap
+INPUTS (the selector construction of step_exact, section A).  Keys are +-1 code words, queries 128 x a code word, D = 128 (64 and 32
+in the two ring replays of RING_VALU_SHAPES, which run behind the VALU streaming pass instead of the matrix-core kernel); the gap
 between the dtype-rounded score of a matching key and of any other key is measured per case and asserted >= GAP_MIN, so every
 non-matching probability is +0.  New here:
   poison     every slot a head does not see (hybrid: at or beyond cache_cts[h]; ring policy: the empty slots) holds the code word of
@@ -108,22 +109,24 @@ def _rnd_np(x, dt):
 class _Case:
     """What both families share: code words, V rows, the measured gap, the group-mean table."""
 
-    def _common(self, dt, H, HQ, S, steps, L, seed):
-        self.dt, self.H, self.HQ, self.S, self.D, self.steps, self.L = dt, H, HQ, S, 128, steps, L
+    def _common(self, dt, H, HQ, S, steps, L, seed, D=128):
+        self.dt, self.H, self.HQ, self.S, self.D, self.steps, self.L = dt, H, HQ, S, D, steps, L
         self.R = HQ // H
         assert self.R * H == HQ and 8 <= steps <= 24
-        self.g, self.amp, self.scale = G_TOK, 128, P.default_scale(128)
-        self.plan = plan(HQ, H, S, 128, dt)
+        self.g, self.amp, self.scale = G_TOK, 128, P.default_scale(D)
+        self.plan = plan(HQ, H, S, D, dt)
         self.nb = P.nbits_for(L)
-        codes, self.rep = P.code_words(L, 128)
+        codes, self.rep = P.code_words(L, D)
         self.codes = codes.astype(np.float32)
         gen = torch.Generator().manual_seed(131 * seed + S + 7 * H)
-        v = torch.randn(H, L, 128, generator=gen, dtype=torch.float32)
+        v = torch.randn(H, L, D, generator=gen, dtype=torch.float32)
         v = torch.where(v.abs() < 2.0 ** -6, torch.copysign(torch.tensor(2.0 ** -6), v), v)
         self.v_all = v.to(dt)
         a = self.v_all.double().abs()
         assert bool((a >= 2.0 ** -6).all()) and bool((a < 16.0).all())  # exponents in [-6, 3]: the two-hot sum is exact in fp32
-        n = 128 - 2 * self.rep * np.arange(0, self.nb + 1)
+        n = D - 2 * self.rep * np.arange(0, self.nb + 1)
+        for m in range(-D, D + 1):  # amp * n exact in the dtype
+            assert float(torch.tensor(float(self.amp * m), dtype=torch.float64).to(dt)) == float(self.amp * m)
         sc = P.rounded_scores(n, self.amp, self.scale, dt)
         assert np.isfinite(sc).all()
         self.gap = float(sc[0] - sc[1:].max())
@@ -269,13 +272,13 @@ class RingCase(_Case):
 
     family = "ring"
 
-    def __init__(self, dt, H, HQ, S, W, fill, steps=12, seed=0):
+    def __init__(self, dt, H, HQ, S, W, fill, steps=12, seed=0, D=128):
         assert fill in ("brim", "minus3", "sparse")
         self.W, self.fill, self.n = W, fill, seed
-        self.id = f"ring-{DT_NAME[dt]}-H{H}-HQ{HQ}-S{S}-W{W}-{fill}"
+        self.id = f"ring-{DT_NAME[dt]}-H{H}-HQ{HQ}-S{S}-W{W}-{fill}" + (f"-D{D}" if D != 128 else "")
         self.T = T = S if fill == "brim" else S - 3 if fill == "minus3" else 70
         self.p0 = T
-        self._common(dt, H, HQ, S, steps, T + steps, seed=seed + 1)
+        self._common(dt, H, HQ, S, steps, T + steps, seed=seed + 1, D=D)
         self.w = W_REC
         rng = np.random.default_rng(7919 * seed + 31 * S + 3 * H + HQ + W)
         self.ctr0 = W - 5
@@ -694,6 +697,9 @@ def make_sim(c, fault=None, dense=False):
 HYB_SHAPES = {(2, 4, 130): (4, 0, False), (4, 28, 130): (4, 0, False), (3, 12, 130): (4, 1, False), (1, 8, 200): (4, 1, False),
               (8, 32, 200): (4, 1, True), (8, 64, 130): (4, 1, True), (16, 64, 1280): (8, 1, True), (8, 32, 4160): (4, 2, True)}
 RING_SHAPES = [(2, 4, 130, 8), (4, 28, 130, 33), (8, 32, 200, 33), (16, 64, 1280, 8)]  # (H, HQ, S, W): always two launches
+# the ring policy behind the VALU streaming pass (decode_attn_split_kernel; there the ring-specific part is the ring_col word block
+# (0, 0, 0) writes, the rest is the combine pass): (dtype, H, HQ, S, W, D)
+RING_VALU_SHAPES = [(BF, 2, 4, 130, 8, 64), (HF, 4, 28, 130, 33, 32)]
 N_STATES = 3
 
 
@@ -703,20 +709,25 @@ def shape_list():
     for dt in (BF, HF):
         out += [("hyb", dt, H, HQ, S, W_HYB) for (H, HQ, S) in HYB_SHAPES]
         out += [("ring", dt, H, HQ, S, W) for (H, HQ, S, W) in RING_SHAPES]
-    return out
+    return out + [("ring", dt, H, HQ, S, W, D) for (dt, H, HQ, S, W, D) in RING_VALU_SHAPES]
+
+
+def unpack(t):
+    """-> (family, dt, H, HQ, S, W, D): the entries from before the VALU shapes carry no D (128)."""
+    return tuple(t) + ((128,) if len(t) == 6 else ())
 
 
 def shape_id(t):
-    fam, dt, H, HQ, S, W = t
-    return f"{fam}-{DT_NAME[dt]}-{H}-{HQ}-{S}-W{W}"
+    fam, dt, H, HQ, S, W, D = unpack(t)
+    return f"{fam}-{DT_NAME[dt]}-{H}-{HQ}-{S}-W{W}" + (f"-D{D}" if D != 128 else "")
 
 
 def cases_of(t, steps=None):
-    fam, dt, H, HQ, S, W = t
+    fam, dt, H, HQ, S, W, D = unpack(t)
     st = steps or (16 if S <= 300 else 12)
     if fam == "hyb":
         return [HybCase(dt, H, HQ, S, n + (3 if dt == HF else 0), steps=st) for n in range(N_STATES)]
-    return [RingCase(dt, H, HQ, S, W, fill, steps=st, seed=n + (3 if dt == HF else 0)) for n, fill in enumerate(("brim", "minus3", "sparse"))]
+    return [RingCase(dt, H, HQ, S, W, fill, steps=st, seed=n + (3 if dt == HF else 0), D=D) for n, fill in enumerate(("brim", "minus3", "sparse"))]
 
 
 def intended_single_launch(c):

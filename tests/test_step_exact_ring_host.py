@@ -34,8 +34,8 @@ def test_mirrored_lines_are_the_source(fname):
 def test_every_shape_lands_on_its_intended_path():
     seen = set()
     for t in E.shape_list():
-        fam, dt, H, HQ, S, W = t
-        pl = E.plan(HQ, H, S, 128, dt)
+        fam, dt, H, HQ, S, W, D = E.unpack(t)
+        pl = E.plan(HQ, H, S, D, dt)
         R = HQ // H
         if fam == "hyb":
             nw, nt, xl2 = E.HYB_SHAPES[(H, HQ, S)]
@@ -43,9 +43,12 @@ def test_every_shape_lands_on_its_intended_path():
             assert (pl["xl2"] and nt > 0) == xl2
             seen.add((nw, nt, xl2, R))
         assert pl["n_split"] > 1 or S <= pl["rows_per_split"]
+        if D != 128:  # the VALU streaming pass: two launches only, a ragged last split (two rows at D = 64; the only one at D = 32)
+            assert fam == "ring" and pl["nt"] == 0 and pl["nw"] == 4 and S % pl["rows_per_split"] == {64: 2, 32: 130}[D], (t, pl)
     assert {r for _, _, _, r in seen} >= {2, 4, 7, 8}
     assert {(w, n, x) for w, n, x, _ in seen} >= {(4, 0, False), (4, 1, False), (4, 1, True), (8, 1, True), (4, 2, True)}
-    assert {W for (_, _, _, _, _, W) in E.shape_list()} >= {8, 33, 400} and (33 * 2) % 16 != 0  # 66-byte ring rows: the unaligned branch
+    assert {E.unpack(t)[5] for t in E.shape_list()} >= {8, 33, 400} and (33 * 2) % 16 != 0  # 66-byte ring rows: the unaligned branch
+    assert {(E.unpack(t)[1], E.unpack(t)[6]) for t in E.shape_list()} >= {(BF, 64), (HF, 32)}
 
 
 # ------------------------------------------------------------------------------------------------ the constructions
@@ -116,6 +119,9 @@ def test_the_replays_visit_what_they_claim():
         family[t[0]] |= notes
         assert twohot > 0, t
         miss = want[t[0]] - notes - anywhere
+        fam, dt, H, HQ, S, W, D = E.unpack(t)
+        if E.plan(HQ, H, S, D, dt)["n_split"] == 1:
+            miss -= {"different_splits"}
         if t[2] >= 8:  # (over the shape's three start states; the shapes with one to four heads hold fewer policies at a time)
             assert not miss, (t, miss)
             if t[0] == "hyb":
@@ -147,7 +153,8 @@ def test_oracle_twins_return_the_answers(monkeypatch, oracle, shape):
 def _mutant_cases():
     out = []
     for t in (("hyb", BF, 2, 4, 130, 400), ("hyb", HF, 3, 12, 130, 400), ("hyb", BF, 8, 32, 200, 400), ("hyb", HF, 8, 64, 130, 400),
-              ("hyb", BF, 4, 28, 130, 400), ("ring", BF, 2, 4, 130, 8), ("ring", HF, 4, 28, 130, 33), ("ring", BF, 8, 32, 200, 33)):
+              ("hyb", BF, 4, 28, 130, 400), ("ring", BF, 2, 4, 130, 8), ("ring", HF, 4, 28, 130, 33), ("ring", BF, 8, 32, 200, 33),
+              ("ring", BF, 2, 4, 130, 8, 64), ("ring", HF, 4, 28, 130, 33, 32)):
         out += E.cases_of(t)
     return out
 
