@@ -16,23 +16,24 @@ import numpy as np
 LEVELS = 15
 
 
-def row_params(x):
-    """(scale, mn, inv) float32 per row of x (last axis): the contract's row grid."""
+def row_params(x, levels=LEVELS):
+    """(scale, mn, inv) float32 per row of x (last axis): the contract's row grid.  levels: 15 (this format) or 255 (the uint8
+    grid of cache_quant_mode="fused": the same arithmetic, one code per byte; tests/kv_quant_twin.py)."""
     x = np.asarray(x, np.float32)
     mn, mx = x.min(axis=-1), x.max(axis=-1)
     rng = np.maximum(np.float32(mx - mn), np.float32(1e-6)).astype(np.float32)
     with np.errstate(over="ignore", divide="ignore"):
-        scale = (rng / np.float32(LEVELS)).astype(np.float32)
-        inv = (np.float32(LEVELS) / rng).astype(np.float32)
+        scale = (rng / np.float32(levels)).astype(np.float32)
+        inv = (np.float32(levels) / rng).astype(np.float32)
     return scale, mn.astype(np.float32), inv
 
 
-def quant_codes(x):
-    """(codes uint8 in [0, 15] like x, scale [rows], mn [rows])."""
+def quant_codes(x, levels=LEVELS):
+    """(codes uint8 in [0, levels] like x, scale [rows], mn [rows])."""
     x = np.asarray(x, np.float32)
-    scale, mn, inv = row_params(x)
+    scale, mn, inv = row_params(x, levels)
     t = ((x - mn[..., None]).astype(np.float32) * inv[..., None]).astype(np.float32)
-    q = np.clip(np.rint(t), 0, LEVELS)
+    q = np.clip(np.rint(t), 0, levels)
     return q.astype(np.uint8), scale, mn
 
 

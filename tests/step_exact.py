@@ -36,12 +36,21 @@ B. RAMP STEPS (16-bit dtypes; D = 128, and 64 / 32 / 16 behind the VALU pass).  
    y: 1e-3 + 2 ulp_of(dtype) max|y_ref|; history increment per element: mean over the group's heads of step(p_ref) + step(gm_ref)
    (step = the dtype's spacing there, the smallest subnormal at 0).  ONE derived widening: the decode kernels' exponentials
    (fast_exp and exp_nonpos of csrc/cc_attn_decode_kernels.h) end in __builtin_amdgcn_exp2f, v_exp_f32, which returns 0 for a
-   result below the smallest normal fp32: a probability p_ref < 2^-126 may be off by its whole value.  Everything else is equality."""
+   result below the smallest normal fp32: a probability p_ref < 2^-126 may be off by its whole value.  Everything else is equality.
+
+C. THE FUSED QUANTISED CACHES (Case(quant=...): cache_quant_mode fused / fp8 / uint4 / mxfp4).  Family A over the images:
+   keys are code words of which some rows are scaled by 2^-1 / 2^-2 under every policy (their round trip through the format is the
+   identity, asserted; only full-scale rows are selected), values are block-scaled Gaussian rows whose ROUND TRIP through the numpy
+   twin of the format (tests/kv_quant_twin.py) is what attention reads: the selected probability is still exactly 1 and y is the
+   twin's round trip of one V row.  The simulator keeps, beside the dequantised K and V, the K and V images and the [H, S, 4]
+   parameter words; an insert writes the twin's image and words of k_new / v_new, and the same step's attention reads their round
+   trip.  Images and words are compared as bit patterns after every step.  The three-call form does not exist over the images."""
 import math
 
 import numpy as np
 import torch
 
+import kv_quant_twin as Q
 import prefill_exact as P
 
 BF, HF, F32 = torch.bfloat16, torch.float16, torch.float32
@@ -49,6 +58,7 @@ DT_NAME = {BF: "bf16", HF: "f16", F32: "f32"}
 ULP = {F32: 1e-5, BF: 2.0 ** -8, HF: 2.0 ** -11}  # the suite's unit roundoff
 G_TOK, W_REC = 4, 5  # global tokens / recent window of every replay (full: 0 global tokens)
 GAP_MIN = 150.0
+POISON_V = 2.0 ** 14  # quantised sparse fills: every channel of the dead slots' V rows (the previous generation's data, as in 2.22)
 POLICY_NAME = {"hh": "heavy_hitter", "rg": "recent_global", "full": "full", "l2": "l2"}
 
 
@@ -132,26 +142,29 @@ class Case:
     """One replay: the prompt state (k_all / v_all [H, T + steps, D] of dt: the rows of EVERY token, prompt and decode), the seeded
     heavy-hitter history, the l2 key scales, and the measured gap."""
 
-    def __init__(self, policy, dt, H, HQ, S, D, fill, steps=12, hist="zeros", seed=0):
+    def __init__(self, policy, dt, H, HQ, S, D, fill, steps=12, hist="zeros", seed=0, quant=None):
         assert policy in POLICY_NAME and fill in ("brim", "minus3", "sparse") and 12 <= steps <= 24
         self.policy, self.dt, self.H, self.HQ, self.S, self.D, self.fill, self.steps, self.hist, self.seed = policy, dt, H, HQ, S, D, fill, steps, hist, seed
+        self.quant = quant  # None, or the image format of the fused quantised cache (section C of DESIGN 2.24): kv_quant_twin.FORMATS
+        assert quant is None or (quant in Q.FORMATS and policy in ("hh", "rg", "full") and D == 128 and dt in (BF, HF) and (HQ // H) in (4, 8))
         self.R = HQ // H
         assert self.R * H == HQ
         self.T = S if fill == "brim" else S - 3 if fill == "minus3" else (70 if S >= 130 else 20)
-        self.id = f"{policy}-{DT_NAME[dt]}-H{H}-HQ{HQ}-S{S}-{fill}-{hist}" + (f"-D{D}" if D != 128 else "")
+        self.id = f"{policy}-{DT_NAME[dt]}-H{H}-HQ{HQ}-S{S}-{fill}-{hist}" + (f"-D{D}" if D != 128 else "") + (f"-{quant}" if quant else "")
         self.g, self.w = (0 if policy == "full" else G_TOK), W_REC
         self.Hp = H if policy in ("hh", "l2") else 1
         self.scale = P.default_scale(D)
-        self.plan = plan(HQ, H, S, D, dt, policy)
+        self.plan = quant_plan(HQ, H, S, dt) if quant else plan(HQ, H, S, D, dt, policy)
         L = self.L = self.T + steps
         self.nb = P.nbits_for(L)
         codes, self.rep = P.code_words(L, D)
         self.codes = codes.astype(np.float32)  # [L, D] of +-1
         rng = np.random.default_rng(7919 * seed + 31 * S + 3 * H + HQ)
         # l2: some key rows scaled by 2^-1 or 2^-2, differently in every head (the norm maximum runs over all heads); decode tokens
-        # of head h are scaled where (step + h) % 4 == 3
+        # of head h are scaled where (step + h) % 4 == 3.  quant: the same under every policy, so that K's row parameters differ
+        # from slot to slot and a stale K scale is visible
         self.e = np.zeros((H, L), np.int64)
-        if policy == "l2":
+        if policy == "l2" or quant:
             for h in range(H):
                 u = rng.random(L)
                 lo = 0.25 + 0.4 * (h % 3) / 2.0  # share of scaled rows: 25 %, 45 %, 65 %
@@ -162,7 +175,19 @@ class Case:
         gen = torch.Generator().manual_seed(131 * seed + S + 7 * H)
         v = torch.randn(H, L, D, generator=gen, dtype=torch.float32)
         v = torch.where(v.abs() < 2.0 ** -6, torch.copysign(torch.tensor(2.0 ** -6), v), v)
+        if quant:  # block b (32 channels) of token t times 2^(3 ((t + b) % 4) - 4): 2^-4 .. 2^5, every block of a row another power.
+            # (Steps of 3, not 2: the largest of 32 Gaussians lies in (0.75, 6], three binades, so with steps of 2 two neighbouring
+            # blocks can meet in one MXFP4 exponent and a row of 20 000 ends up with 2 distinct scale bytes; with 3 there are always 4.)
+            tb = (np.arange(L)[:, None] + np.arange(D // 32)[None, :]) % 4
+            v = v * torch.from_numpy(2.0 ** (3.0 * tb - 4.0)).to(torch.float32).repeat_interleave(32, dim=1)[None]
+            # every row holds all four block factors, so a ROW parameter is that of 8 max|N(0, 1)| for every token: FP8's power of two
+            # would be 2^-3 .. 2^-1 everywhere, and on the uint8 / uint4 grid two neighbours now and then share a bf16 minimum and
+            # maximum.  Odd tokens times 16: consecutive tokens' V parameters differ in every format (asserted in _quantise)
+            v = v * torch.from_numpy(16.0 ** (np.arange(L) % 2)).to(torch.float32)[None, :, None]
         self.v_all = v.to(dt)
+        self.k_deq, self.v_deq = self.k_all, self.v_all  # what attention reads: the rows themselves, or their round trip
+        if quant:
+            self._quantise()
         self.gm_table = _gm_table(self.R, dt)
         # amp: 128, doubled while the measured gap is below GAP_MIN and the largest product still doubles within 16384 (128 at D = 128)
         self.amp = 128
@@ -170,6 +195,32 @@ class Case:
             self.amp *= 2
         self._measure()
         self._seed_history(rng)
+
+    def _quantise(self):
+        """The twin's images, row parameters and round trips of every token's rows, and what the construction rests on."""
+        fmt, dt = self.quant, self.dt
+        self.k_img, self.k_par, kb = Q.round_trip(self.k_all, dt, fmt)
+        self.v_img, self.v_par, vb = Q.round_trip(self.v_all, dt, fmt)
+        assert np.array_equal(kb, bits(self.k_all)), (self.id, "the round trip of a key row is not the identity")
+        self.v_deq = Q.to_tensor(vb, dt)
+        assert bool(torch.isfinite(self.v_deq.double()).all())
+        for h in range(self.H):  # the selected V row is known by its bits: the round-tripped rows of a head are pairwise distinct
+            assert len({r.tobytes() for r in vb[h]}) == self.L, (self.id, h)
+        self.changed = float((vb != bits(self.v_all)).mean())
+        assert self.changed > 0.5, (self.id, self.changed)
+        if fmt == "mxfp4":  # every row carries at least 3 distinct scale bytes
+            sb = Q.MX.scale_bytes(self.v_par[..., 0])
+            assert min(len(set(r.tolist())) for r in sb.reshape(-1, sb.shape[-1])) >= 3, self.id
+        assert bool((self.v_par[:, 1:] != self.v_par[:, :-1]).any(axis=-1).all()), (self.id, "consecutive tokens share their V parameters")
+        assert len({tuple(r) for r in self.k_par[0].tolist()}) >= 3  # (K: one parameter pair per scale 1, 1 / 2, 1 / 4)
+        # dead slots hold what the class's own prefill leaves there (KVCache._prefill_update, fused branch: the model-dtype staging
+        # pair is zeroed, the prompt's rows land in slots [0, T), then EVERY row of the staging pair goes through cc_kv_quant_rows):
+        # the image and parameters of an all-zero row; and the previous generation's V data the driver puts there in the sparse fill
+        z = torch.zeros(1, self.D, dtype=dt)
+        self.zero_img, self.zero_par, zb = Q.round_trip(z, dt, fmt)
+        assert not zb.any()
+        self.poison_img, self.poison_par, pb = Q.round_trip(torch.full((1, self.D), POISON_V, dtype=dt), dt, fmt)
+        assert np.array_equal(pb, bits(torch.full((1, self.D), POISON_V, dtype=dt)))
 
     def _gap(self):
         """The dtype-rounded score of the selected key minus the largest one of any other key, at the present amp."""
@@ -192,7 +243,8 @@ class Case:
             assert float(torch.tensor(float(amp * m), dtype=torch.float64).to(dt)) == float(amp * m)
         self.gap = self._gap()
         assert self.gap >= GAP_MIN, (self.id, self.gap)
-        assert bool((self.v_all.double().abs() >= 2.0 ** -6).all()) and bool(torch.isfinite(self.v_all.double()).all())
+        lo = 2.0 ** -10 if self.quant else 2.0 ** -6  # (quant: the block factors reach down to 2^-4)
+        assert bool((self.v_all.double().abs() >= lo).all()) and bool(torch.isfinite(self.v_all.double()).all())
         if self.policy == "l2":  # norm roundings are unique: four fp32 ulps either way round to the same dtype value
             for e in (0, 1, 2):
                 x = np.float32(np.sqrt(np.float32(self.D * 4.0 ** -e)))
@@ -245,6 +297,17 @@ class Case:
 FAULTS = ("stale_k", "stale_v", "tie_high", "tie_chunk", "recent_gt", "global_off", "denom_live", "no_zero", "stale_hist", "head_mod",
           "drop_last", "no_rescale", "masked_weight", "cts_skip", "dup_tail")
 _ATTN_FAULTS = ("stale_k", "stale_v", "head_mod", "drop_last", "no_rescale", "masked_weight", "dup_tail")
+# ... and of the quantised cases (Case.quant; tests/test_step_exact_quant_host.py):
+#   stale_kparam / stale_vparam  the insert writes the image but keeps the slot's old K / V parameters
+#   no_quant_new                 this step's attention reads the unrounded new token
+#   nibble_swap                  the inserted rows' nibbles are swapped (4-bit formats)
+#   block_scale0                 every block is decoded with block 0's scale (MXFP4)
+#   poison_live                  masked_weight, seen through the poisoned V rows of the dead slots (sparse fill)
+QUANT_FAULTS = ("stale_kparam", "stale_vparam", "no_quant_new", "nibble_swap", "block_scale0", "poison_live")
+
+
+def quant_faults_of(fmt):
+    return tuple(f for f in QUANT_FAULTS if (f != "nibble_swap" or fmt in Q.FOUR_BIT) and (f != "block_scale0" or fmt == "mxfp4"))
 
 
 def attend_dense(q, K, V, mask, scale, dt, rps, R, fault=None):
@@ -297,8 +360,8 @@ class Sim:
     hold the one-hot answers to it."""
 
     def __init__(self, c, fault=None, dense=False):
-        assert fault is None or fault in FAULTS
-        self.c, self.fault, self.dense = c, fault, dense or fault in _ATTN_FAULTS
+        assert fault is None or fault in FAULTS or (c.quant and fault in quant_faults_of(c.quant))
+        self.c, self.fault, self.dense = c, fault, dense or fault in _ATTN_FAULTS or fault in QUANT_FAULTS
         H, S, D, T = c.H, c.S, c.D, c.T
         self.pos = np.full((c.Hp, S), -1, np.int32)
         self.pos[:, :T] = np.arange(T, dtype=np.int32)
@@ -307,7 +370,17 @@ class Sim:
         self.cts = np.array([T], np.int32)
         self.K = torch.zeros(H, S, D, dtype=c.dt)
         self.V = torch.zeros(H, S, D, dtype=c.dt)
-        self.K[:, :T], self.V[:, :T] = c.k_all[:, :T], c.v_all[:, :T]
+        self.K[:, :T], self.V[:, :T] = c.k_deq[:, :T], c.v_deq[:, :T]
+        if c.quant:  # K and V above are the DEQUANTISED values (what attention reads); beside them the images and the parameter words
+            Db = Q.image_width(D, c.quant)
+            self.Kimg = np.tile(c.zero_img.reshape(1, 1, Db), (H, S, 1))
+            self.Vimg = self.Kimg.copy()
+            self.par = np.tile(Q.qparams(c.zero_par, c.zero_par).reshape(1, 1, 4), (H, S, 1))
+            self.Kimg[:, :T], self.Vimg[:, :T] = c.k_img[:, :T], c.v_img[:, :T]
+            self.par[:, :T] = Q.qparams(c.k_par[:, :T], c.v_par[:, :T])
+            if c.fill == "sparse":  # the driver overwrites the dead slots' V image and V parameters (poison_cache); K is left alone
+                self.Vimg[:, T:], self.par[:, T:, 2:], self.V[:, T:] = c.poison_img[0], c.poison_par[0], POISON_V
+        self.scaled = bool(c.e.any())  # some key rows are scaled (l2; every quantised case): only full-scale rows are selected
         self.num, self.den, self.ctr = c.num0.copy(), c.den0.copy(), 0
         self.pre = None  # (num, denom) as they stood before the latest history update (the stale_hist mutant scores on them)
         self.norm = np.zeros((H, S), np.float64)
@@ -368,7 +441,7 @@ class Sim:
         inserted in this very step (where the policy lets it be selected); otherwise heads 0 and 1 of a group take the two sides of a
         boundary — slots 15/16 (a wave's tile), 63/64, 127/128 (workgroups of the 4- and the 8-wave plan), the two sides of a split
         boundary, the row before the last split and the LAST LIVE slot of the (partly filled) last split, the cache's first and last
-        slot — and the other heads seeded live slots, i.e. other splits.  l2: full-scale slots only.  heavy_hitter with planted
+        slot — and the other heads seeded live slots, i.e. other splits.  Cases with scaled key rows (l2, quant): full-scale slots only.  heavy_hitter with planted
         pairs: not the planted slots (their tie must survive until they are evicted)."""
         c = self.c
         S, R, pl = c.S, c.R, c.plan
@@ -379,7 +452,7 @@ class Sim:
         for h in range(c.H):
             row = self.pos[h if c.Hp > 1 else 0]
             ok = self.mask[h] == 1
-            if c.policy == "l2":
+            if self.scaled:
                 ok = ok & (c.e[h][np.maximum(row, 0)] == 0)
             for s in self.planted[h]:
                 ok[s] = False
@@ -416,6 +489,27 @@ class Sim:
         assert (sel >= 0).all()
         return sel, slots
 
+    def _insert_images(self, h, s, p):
+        """The insert writes the twin's image and words of k_new / v_new; "the inserted token is attended to through its image in
+        the step that inserts it" (include/coldcompress.h, fused quantised KV cache): K / V hold the round trip from this step on."""
+        c, f = self.c, self.fault
+        ki, vi, kp, vp = c.k_img[h, p], c.v_img[h, p], c.k_par[h, p], c.v_par[h, p]
+        if f == "nibble_swap":
+            ki, vi = Q.swap_nibbles(ki), Q.swap_nibbles(vi)
+        if f == "stale_kparam":
+            kp = self.par[h, s, :2].copy()
+        if f == "stale_vparam":
+            vp = self.par[h, s, 2:].copy()
+        self.Kimg[h, s], self.Vimg[h, s], self.par[h, s, :2], self.par[h, s, 2:] = ki, vi, kp, vp
+        if f in ("nibble_swap", "stale_kparam", "stale_vparam"):
+            with np.errstate(all="ignore"):
+                self.K[h, s] = Q.to_tensor(Q.decode(ki[None], kp[None], c.dt, c.quant), c.dt)[0]
+                self.V[h, s] = Q.to_tensor(Q.decode(vi[None], vp[None], c.dt, c.quant), c.dt)[0]
+
+    def images(self):
+        """The images and the [H, S, 4] parameter words as the cache classes hold them."""
+        return dict(k_img=self.Kimg, v_img=self.Vimg, qparams=self.par)
+
     # ---- one step
     def step(self, i):
         """-> dict(p, q [HQ, D], k1, v1 [H, D] of dt, y [HQ, D] of dt (the answer), idx [Hp], sel, slots)."""
@@ -433,7 +527,9 @@ class Sim:
             s = idx[hp(h)]
             if c.policy == "hh" and f != "no_zero":
                 self.num[h, s], self.den[h, s] = 0.0, 0
-            self.K[h, s], self.V[h, s] = k1[h], v1[h]
+            self.K[h, s], self.V[h, s] = c.k_deq[h, p], c.v_deq[h, p]
+            if c.quant:
+                self._insert_images(h, s, p)
             self.mask[h, s] = 1
             self.planted[h].discard(s)
             if c.policy == "l2":
@@ -449,16 +545,35 @@ class Sim:
             assert c.e[j // R, sel[j]] == 0  # l2: a full-scale key (the gap argument is untouched by the scaled rows)
         # the answers: one-hot probabilities
         y = torch.stack([self.V[j // R, slots[j]] for j in range(c.HQ)])
+        if c.quant:  # a round trip may return -0 (MXFP4 keeps the sign of what it rounds to zero): O = 1 x (-0) + 0 x ... is +0
+            y = (y.double() + 0.0).to(c.dt)
         cnt = np.zeros((H, c.S), np.int64)
         np.add.at(cnt, (np.arange(c.HQ) // R, slots), 1)
         gm = c.gm_table[cnt]
         if self.dense:
             Kd = (Kold if f == "stale_k" else self.K).double()
             Vd = (Vold if f == "stale_v" else self.V).double()
-            yd, _, gmd = attend_dense(q.double(), Kd, Vd, torch.from_numpy(self.mask.astype(bool)), c.scale, c.dt, c.plan["rows_per_split"], R, f)
-            if f is None:
+            if f == "no_quant_new":
+                Kd, Vd = Kd.clone(), Vd.clone()
+                for h in range(H):
+                    Kd[h, idx[hp(h)]], Vd[h, idx[hp(h)]] = k1[h].double(), v1[h].double()
+            if f == "block_scale0":
+                Vd = Q.to_tensor(Q.decode(self.Vimg, self.par[..., 2:], c.dt, c.quant, block0=True), c.dt).double()
+            if c.quant and f is None:  # the simulator's own books agree: K and V are the decoded images
+                for img, w, t in ((self.Kimg, self.par[..., :2], self.K), (self.Vimg, self.par[..., 2:], self.V)):
+                    assert np.array_equal(Q.decode(img, w, c.dt, c.quant), bits(t)), (c.id, i)
+            with np.errstate(all="ignore"):
+                yd, _, gmd = attend_dense(q.double(), Kd, Vd, torch.from_numpy(self.mask.astype(bool)), c.scale, c.dt, c.plan["rows_per_split"], R,
+                                          "masked_weight" if f == "poison_live" else f)
+            if f is None and c.quant:
+                # (an element that is +-0 in the selected V row: the float64 evaluation multiplies +0 probabilities by negative
+                # values and may return -0, where an accumulator that starts at +0 returns +0: zeros are compared by value)
+                ydt, zero = yd.to(c.dt), (y == 0).numpy()
+                assert np.array_equal(bits(ydt)[~zero], bits(y)[~zero]) and bool((ydt.double().numpy()[zero] == 0).all()), (c.id, i)
+                assert np.array_equal(gmd.numpy(), gm), (c.id, i)
+            elif f is None:
                 assert np.array_equal(bits(yd.to(c.dt)), bits(y)) and np.array_equal(gmd.numpy(), gm), (c.id, i)
-            y, gm = yd.to(c.dt), gmd.numpy()
+            y, gm = ((yd + 0.0) if c.quant else yd).to(c.dt), gmd.numpy()  # (quant: -0 -> +0, as in the answers above)
         if c.policy == "hh":
             self.pre = (self.num.copy(), self.den.copy())
             self.num += gm
@@ -542,6 +657,54 @@ def shape_id(t):
     return f"{pol}-{DT_NAME[dt]}-{H}-{HQ}-{S}-D{D}"
 
 
+# ------------------------------------------------------------------------------------------------ C. the quantised caches
+# (H, HQ, S): the plain step of cc_decode_step_quant over the images; every image format, bf16 and f16, forms "two" and "one"
+QUANT_SHAPES = [(3, 12, 130), (1, 8, 200), (8, 32, 200), (8, 64, 130), (16, 64, 1280), (16, 128, 1290), (4, 16, 5120), (4, 32, 5120),
+                (8, 32, 4160)]
+QUANT_ALL_POLICIES = [(3, 12, 130), (8, 32, 200), (16, 64, 1280), (4, 32, 5120)]  # rg and full as well as hh
+INTENDED.update({(2, 128, 4, 16, 5120): (8, 1, False), (2, 128, 4, 32, 5120): (8, 1, False)})
+MIRRORED_QUANT_LINES = {"cc_attn_decode.hip": [
+    "if (nt != 1) return nullptr; // as 8: one tile per wave",
+    "if (kind != 0 && kind != 8 && kind != kQbFp8 && kind != kQbU4 && kind != kQbMx4 && kind != -1) return nullptr;",
+    "if (kind == 208) { // hybrid over uint8 images: 4 or 8 query heads per kv head; one tile per wave or up to eight",
+    "if (hyb) { // as 208: one tile per wave or up to eight",
+]}
+
+
+def quant_plan(HQ, H, S, dt):
+    """plan() for the plain step over the images: the single launch exists with one tile per wave only (one_kernel, kind 8;
+    one_kernel_img), over the memory hand-off or the XCD-L2 transport (one_kernel_xl2), 4 or 8 query heads per kv head."""
+    pl = plan(HQ, H, S, 128, dt)
+    assert pl["rt"] in (4, 8) and HQ // H == pl["rt"]
+    pl["nt"] = 1 if pl["nt"] == 1 else 0
+    return pl
+
+
+def quant_shape_list():
+    """-> [(policy, dt, H, HQ, S, fmt)]: one entry per parametrised test; each runs its three fill levels."""
+    out = []
+    for fmt in Q.FORMATS:
+        for dt in (BF, HF):
+            out += [("hh", dt, H, HQ, S, fmt) for (H, HQ, S) in QUANT_SHAPES]
+            out += [(pol, dt, H, HQ, S, fmt) for pol in ("rg", "full") for (H, HQ, S) in QUANT_ALL_POLICIES]
+    return out
+
+
+def quant_shape_id(t):
+    pol, dt, H, HQ, S, fmt = t
+    return f"{fmt}-{pol}-{DT_NAME[dt]}-{H}-{HQ}-{S}"
+
+
+def quant_cases_of(t, steps=None):
+    """The three fill levels of one quantised shape (cases_of's alternation of the planted pairs and the runs of zeros)."""
+    pol, dt, H, HQ, S, fmt = t
+    out = []
+    for n, fill in enumerate(FILLS):
+        hist = "pairs" if (n + (dt == HF)) % 2 == 0 else "zeros"
+        out.append(Case(pol, dt, H, HQ, S, 128, fill, steps=steps or (16 if S <= 300 else 12), hist=hist, seed=n + 1, quant=fmt))
+    return out
+
+
 def cases_of(t, steps=None):
     """The three fill levels of one shape.  The planted pairs and the runs of zeros alternate over the fill levels and the dtypes."""
     pol, dt, H, HQ, S, D = t
@@ -558,10 +721,12 @@ def make_cache(c, dev):
     import cold_compress_amd.cache as cache
 
     cls, rk = cache.get_cache_constructor(POLICY_NAME[c.policy])
-    kw = dict(max_cache_length=c.S, global_tokens=c.g, max_seq_length=4 * c.S + 64, cache_bits=None, history_window_size=1,
-              recent_window=c.w, attn_thresholding=False)
+    quant = getattr(c, "quant", None)
+    kw = dict(max_cache_length=c.S, global_tokens=c.g, max_seq_length=4 * c.S + 64, cache_bits=Q.cache_bits(quant) if quant else None,
+              history_window_size=1, recent_window=c.w, attn_thresholding=False)
+    extra = dict(cache_quant_mode=quant) if quant else {}
     with torch.device(dev):
-        return cls(1, c.H, c.D, c.dt, **{k: kw[k] for k in rk})
+        return cls(1, c.H, c.D, c.dt, **{k: kw[k] for k in rk}, **extra)
 
 
 def seed_cache(kv, c, dev):
@@ -575,6 +740,16 @@ def seed_cache(kv, c, dev):
     if c.policy == "hh":
         kv.attn_history_num[0, :, :, 0] = torch.from_numpy(c.num0).to(dev)
         kv.attn_history_denom[0] = torch.from_numpy(c.den0).to(dev)
+    if getattr(c, "quant", None) and c.fill == "sparse":
+        poison_cache(kv, c, dev)
+
+
+def poison_cache(kv, c, dev):
+    """Stale images: the dead slots' V image and V parameters become those of a row of POISON_V in every channel (the previous
+    generation's data; a masked slot that carried weight would show at once).  K is left alone; the answers do not change."""
+    T = c.T
+    kv.v_cache_q[0, :, T:] = torch.from_numpy(c.poison_img[0]).to(dev)
+    kv.kv_qparams.view(torch.int32)[0, :, T:, 2:] = torch.from_numpy(c.poison_par[0].view(np.int32)).to(dev)
 
 
 def read_cache(kv, c):
@@ -624,6 +799,9 @@ def run_replay(c, form, dev, put=None, sync=None, dense=False, full_kv_every_ste
     seed_cache(kv, c, dev)
     sync()
     n = compare_small(kv, sim, f"{c.id} [{form}] after prefill")
+    if c.quant:
+        assert form in ("two", "one"), "the fused quantised caches decode through decode_step() only"
+        return kv, n + _replay_quant(c, form, dev, kv, sim, put, sync)
     mk, mv = sim.K.clone().to(dev), sim.V.clone().to(dev)
     small_kv = c.H * c.S * c.D <= (1 << 19) if full_kv_every_step is None else full_kv_every_step
     itype = torch.int32 if c.dt == F32 else torch.int16
@@ -657,6 +835,45 @@ def run_replay(c, form, dev, put=None, sync=None, dense=False, full_kv_every_ste
                 assert np.array_equal(bits(got), bits(own)), f"{where}: {name} cache against the simulator's own copy"
             n += got.numel()
     return kv, n
+
+
+def compare_images(kv, sim, where, dev, dequant=False):
+    """The images and the [H, S, 4] parameter words against the simulator's, bit for bit; dequant: also the device's own decode of
+    its images (cc_kv_dequant_rows) against the simulator's dequantised K and V.  -> elements compared."""
+    n = 0
+    exp = sim.images()
+    for name, got, e in (("K image", kv.k_cache_q[0], exp["k_img"]), ("V image", kv.v_cache_q[0], exp["v_img"]),
+                         ("qparams words", kv.kv_qparams[0].view(torch.int32), exp["qparams"].view(np.int32))):
+        if not torch.equal(got, torch.from_numpy(e).to(dev)):
+            a, b = bits(got), bits(e)
+            raise AssertionError(f"{where}: {name}: {_first_diff(a, b)}")
+        n += got.numel()
+    if dequant:
+        k, v = kv.dequantized_kv()
+        for name, got, own in (("K", k[0], sim.K), ("V", v[0], sim.V)):
+            a, b = bits(got), bits(own)
+            assert np.array_equal(a, b), f"{where}: dequantised {name}: {_first_diff(a, b)}"
+            n += a.size
+    return n
+
+
+def _replay_quant(c, form, dev, kv, sim, put, sync):
+    """The steps of a quantised replay (run_replay): y and the small buffers as in 16 bits, and the images and parameter words after
+    every step.  -> elements compared exactly."""
+    n = compare_images(kv, sim, f"{c.id} [{form}] after prefill", dev, dequant=True)
+    for i in range(c.steps):
+        st = sim.step(i)
+        where = f"{c.id} [{form}] step {i}"
+        p = torch.tensor([st["p"]], dtype=torch.int32, device=dev)
+        q = put("q", st["q"]).view(1, c.HQ, 1, c.D)
+        k1 = put("k_new", st["k1"]).view(1, c.H, 1, c.D)
+        v1 = put("v_new", st["v1"]).view(1, c.H, 1, c.D)
+        y = kv.decode_step(q, k1, v1, p)
+        sync()
+        a, b = bits(y).reshape(-1), bits(st["y"]).reshape(-1)
+        assert np.array_equal(a, b), f"{where}: y: {_first_diff(a, b)} (heads select slots {st['slots'].tolist()}, insert at {st['idx']})"
+        n += a.size + compare_small(kv, sim, where) + compare_images(kv, sim, where, dev, dequant=(i == c.steps - 1))
+    return n
 
 
 # ------------------------------------------------------------------------------------------------ B. ramp steps

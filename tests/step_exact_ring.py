@@ -57,10 +57,15 @@ attn_counter are compared as bit patterns after every step; the whole ring after
 One mutant of the issue's list is EQUIVALENT under the contract and is asserted to be so instead of rejected: "the decision reads the
 NEW num_punc" — num_punc enters the budget of punctuation-flag heads only, and on the one step that bumps it those heads append
 unconditionally (first link of the chain).  Its neighbour that is NOT equivalent stands in for it: the decision reads a STALE num_punc
-(the previous punctuation step's bump not yet visible: the hazard of a ticket-ordered write racing the next prologue)."""
+(the previous punctuation step's bump not yet visible: the hazard of a ticket-ordered write racing the next prologue).
+
+Over the fused quantised caches (HybCase / RingCase(quant=...)): V rows as in step_exact section C, attention reads
+their round trip through tests/kv_quant_twin.py; the keys stay unscaled code words; the poison is the image of a row of 2^14; no
+two-hot step is planted; images and parameter words are compared after every step (decode_step only: two launches, hybrid also one)."""
 import numpy as np
 import torch
 
+import kv_quant_twin as Q
 import prefill_exact as P
 from step_exact import BF, DT_NAME, GAP_MIN, HF, MIRRORED_LINES, NEXT_KEY_CHUNK, ULP, _first_diff, attend_dense, bits, plan  # noqa: F401
 
@@ -109,8 +114,12 @@ def _rnd_np(x, dt):
 class _Case:
     """What both families share: code words, V rows, the measured gap, the group-mean table."""
 
-    def _common(self, dt, H, HQ, S, steps, L, seed, D=128):
+    def _common(self, dt, H, HQ, S, steps, L, seed, D=128, quant=None):
         self.dt, self.H, self.HQ, self.S, self.D, self.steps, self.L = dt, H, HQ, S, D, steps, L
+        self.quant = quant  # None, or the image format of the fused quantised cache (kv_quant_twin.FORMATS; DESIGN 2.24)
+        assert quant is None or (quant in Q.FORMATS and D == 128 and (HQ // H) in (4, 8))
+        if quant:
+            self.id += f"-{quant}"
         self.R = HQ // H
         assert self.R * H == HQ and 8 <= steps <= 24
         self.g, self.amp, self.scale = G_TOK, 128, P.default_scale(D)
@@ -121,9 +130,29 @@ class _Case:
         gen = torch.Generator().manual_seed(131 * seed + S + 7 * H)
         v = torch.randn(H, L, D, generator=gen, dtype=torch.float32)
         v = torch.where(v.abs() < 2.0 ** -6, torch.copysign(torch.tensor(2.0 ** -6), v), v)
+        if quant:  # step_exact.Case's V rows: block b of token t times 2^(3 ((t + b) % 4) - 4), odd tokens times 16
+            tb = (np.arange(L)[:, None] + np.arange(D // 32)[None, :]) % 4
+            v = v * torch.from_numpy(2.0 ** (3.0 * tb - 4.0)).to(torch.float32).repeat_interleave(32, dim=1)[None]
+            v = v * torch.from_numpy(16.0 ** (np.arange(L) % 2)).to(torch.float32)[None, :, None]
         self.v_all = v.to(dt)
+        self.v_deq = self.v_all  # what attention reads: the rows themselves, or their round trip
         a = self.v_all.double().abs()
-        assert bool((a >= 2.0 ** -6).all()) and bool((a < 16.0).all())  # exponents in [-6, 3]: the two-hot sum is exact in fp32
+        # exponents in [-6, 3]: the two-hot sum is exact in fp32.  (quant: the round trips reach down to +-0 and up to 2^11, the sum
+        # of two of them need not be a float32 — the quantised replays plant no two-hot step, _SimBase._pick_dup)
+        assert quant or (bool((a >= 2.0 ** -6).all()) and bool((a < 16.0).all()))
+        if quant:
+            self.v_img, self.v_par, vb = Q.round_trip(self.v_all, dt, quant)
+            self.v_deq = Q.to_tensor(vb, dt)
+            assert bool(torch.isfinite(self.v_deq.double()).all()) and float(self.v_deq.double().abs().max()) < POISON_V
+            for h in range(H):
+                assert len({r.tobytes() for r in vb[h]}) == L, (self.id, h)
+            assert float((vb != bits(self.v_all)).mean()) > 0.5, self.id
+            assert bool((self.v_par[:, 1:] != self.v_par[:, :-1]).any(axis=-1).all()), self.id
+            rows = torch.from_numpy(self.codes).to(dt)  # the keys: unscaled code words, one parameter pair for all of them
+            self.k_img_tok, self.k_par_tok, kb = Q.round_trip(rows, dt, quant)
+            assert np.array_equal(kb, bits(rows)), (self.id, "the round trip of a key row is not the identity")
+            self.poison_img, self.poison_par, pb = Q.round_trip(torch.full((1, D), POISON_V, dtype=dt), dt, quant)
+            assert np.array_equal(pb, bits(torch.full((1, D), POISON_V, dtype=dt)))
         n = D - 2 * self.rep * np.arange(0, self.nb + 1)
         for m in range(-D, D + 1):  # amp * n exact in the dtype
             assert float(torch.tensor(float(self.amp * m), dtype=torch.float64).to(dt)) == float(self.amp * m)
@@ -193,11 +222,11 @@ class HybCase(_Case):
     family, W = "hyb", W_HYB
     KINDS = ("at", "below", "full", "few", "tile", "split")
 
-    def __init__(self, dt, H, HQ, S, n, steps=12):
+    def __init__(self, dt, H, HQ, S, n, steps=12, quant=None):
         self.n = n
         self.id = f"hyb-{DT_NAME[dt]}-H{H}-HQ{HQ}-S{S}-st{n}"
         p0 = self.p0 = S + 40  # the first decode position: the prompt was longer than the cache
-        self._common(dt, H, HQ, S, steps, p0 + steps, seed=n + 1)
+        self._common(dt, H, HQ, S, steps, p0 + steps, seed=n + 1, quant=quant)
         rng = np.random.default_rng(7919 * n + 31 * S + 3 * H + HQ)
         self.rows = policy_rows(S)
         self.strat = np.array([(h + 3 * n) % len(STRATEGIES) for h in range(H)], np.int64)
@@ -272,13 +301,13 @@ class RingCase(_Case):
 
     family = "ring"
 
-    def __init__(self, dt, H, HQ, S, W, fill, steps=12, seed=0, D=128):
+    def __init__(self, dt, H, HQ, S, W, fill, steps=12, seed=0, D=128, quant=None):
         assert fill in ("brim", "minus3", "sparse")
         self.W, self.fill, self.n = W, fill, seed
         self.id = f"ring-{DT_NAME[dt]}-H{H}-HQ{HQ}-S{S}-W{W}-{fill}" + (f"-D{D}" if D != 128 else "")
         self.T = T = S if fill == "brim" else S - 3 if fill == "minus3" else 70
         self.p0 = T
-        self._common(dt, H, HQ, S, steps, T + steps, seed=seed + 1, D=D)
+        self._common(dt, H, HQ, S, steps, T + steps, seed=seed + 1, D=D, quant=quant)
         self.w = W_REC
         rng = np.random.default_rng(7919 * seed + 31 * S + 3 * H + HQ + W)
         self.ctr0 = W - 5
@@ -326,7 +355,15 @@ class _SimBase:
         self.K = c.key_rows(self.kpos.reshape(-1)).view(H, S, c.D).clone()
         self.V = torch.full((H, S, c.D), POISON_V, dtype=c.dt)
         hs, ss = np.nonzero(live)
-        self.V[hs, ss] = c.v_all[hs, self.pos[hs, ss].astype(np.int64)]
+        self.V[hs, ss] = c.v_deq[hs, self.pos[hs, ss].astype(np.int64)]
+        if c.quant:  # K and V above are the DEQUANTISED values; beside them the images and the [H, S, 4] parameter words.  POISON_V
+            # "goes through the twin": the dead slots hold the image of a row of 2^14 under its own parameters
+            Db = Q.image_width(c.D, c.quant)
+            self.Kimg = c.k_img_tok[self.kpos]
+            self.Vimg = np.tile(c.poison_img.reshape(1, 1, Db), (H, S, 1))
+            vpar = np.tile(c.poison_par.reshape(1, 1, 2), (H, S, 1))
+            self.Vimg[hs, ss], vpar[hs, ss] = c.v_img[hs, self.pos[hs, ss].astype(np.int64)], c.v_par[hs, self.pos[hs, ss].astype(np.int64)]
+            self.par = Q.qparams(c.k_par_tok[self.kpos], vpar)
         self.ring, self.den, self.ctr = c.ring0.copy(), c.den0.copy(), int(c.ctr0)
         self.wsum = self.ring.sum(axis=2, dtype=np.float64)
         self.planted = [set(x) for x in c.planted]
@@ -367,6 +404,8 @@ class _SimBase:
         """A token live in head h (one slot holds its code word, not `new`, not planted), placed relative to the slot `new`:
         the same 16-row tile, another tile of the same split, an earlier split, a later split — in turn."""
         c = self.c
+        if c.quant:  # (the two-hot y is one bit pattern only while V1 + V2 is exact in fp32: see _Case._common)
+            return None
         rps = c.plan["rows_per_split"]
         ok = self.mask[h] == 1
         ok[new] = False
@@ -446,6 +485,8 @@ class _SimBase:
             if n == 2:
                 self.n_twohot += 1
             y[j] = Vd[h, m].sum(dim=0) / n
+            if c.quant:  # a round trip may hold -0; 1 x (-0) + 0 x ... is +0
+                y[j] += 0.0
             if n <= 2:
                 half[h, m] += 2 // n
             else:
@@ -485,6 +526,17 @@ class _SimBase:
             self.notes.add("counter_wraps")
         if f is None and c.S <= 300:
             assert np.array_equal(self.wsum, self.ring.sum(axis=2, dtype=np.float64)), c.id
+
+    def _write(self, h, s, k1, tok, p):
+        """The insert: the token's rows — over the images their round trip, the image and the parameter words."""
+        c = self.c
+        self.K[h, s], self.V[h, s] = k1[h], c.v_deq[h, p]
+        if c.quant:
+            self.Kimg[h, s], self.Vimg[h, s] = c.k_img_tok[tok], c.v_img[h, p]
+            self.par[h, s, :2], self.par[h, s, 2:] = c.k_par_tok[tok], c.v_par[h, p]
+
+    def images(self):
+        return dict(k_img=self.Kimg, v_img=self.Vimg, qparams=self.par)
 
     def buffers(self):
         return dict(pos=self.pos, mask=self.mask, cache_cts=self.cts, denom=self.den, counter=np.array([self.ctr], np.int64), wsum=self.wsum_dt())
@@ -572,7 +624,7 @@ class HybSim(_SimBase):
                 self.wsum[h, s], self.den[h, s] = 0.0, 0
                 self.ring[h, s] = 0.0
             if not (kind == "drop" and f == "drop_unwritten"):
-                self.K[h, s], self.V[h, s] = k1[h], v1[h]
+                self._write(h, s, k1, toks[h], p)
                 self.pos[h, s], self.kpos[h, s] = p, toks[h]
                 if is_punc:
                     self.punc[h, s] = 1
@@ -663,7 +715,7 @@ class RingSim(_SimBase):
             self.den[h, s] = 0
             if f != "ring_row_kept":
                 self.ring[h, s], self.wsum[h, s] = 0.0, 0.0
-            self.K[h, s], self.V[h, s] = k1[h], v1[h]
+            self._write(h, s, k1, toks[h], p)
             self.pos[h, s], self.kpos[h, s], self.mask[h, s] = p, toks[h], 1
             self.planted[h].discard(s)
             if dup_slot[h] is not None:
@@ -730,10 +782,56 @@ def cases_of(t, steps=None):
     return [RingCase(dt, H, HQ, S, W, fill, steps=st, seed=n + (3 if dt == HF else 0), D=D) for n, fill in enumerate(("brim", "minus3", "sparse"))]
 
 
+# ---- over the images: cc_decode_step_heavy_hitter_ring_quant (two launches) and cc_decode_step_hybrid_quant_rc
+QUANT_RING_SHAPES = [(8, 32, 200, 33), (16, 64, 1280, 8), (1, 8, 200, 8)]
+# (H, HQ, S) -> (waves, tiles per wave of the single launch): HYB_SHAPES with 4 or 8 query heads per kv head, and two more
+QUANT_HYB_SHAPES = {(3, 12, 130): (4, 1), (1, 8, 200): (4, 1), (8, 32, 200): (4, 1), (8, 64, 130): (4, 1), (16, 64, 1280): (8, 1),
+                    (8, 32, 4160): (4, 2), (16, 128, 1290): (8, 1), (8, 64, 4160): (4, 2)}
+
+
+def quant_hybrid_plan(HQ, H, S, dt):
+    """plan() for the hybrid step over the images (one_kernel_img, one_kernel kind 208): one launch with one tile per wave at 4 or 8
+    waves, or up to eight tiles per wave at 4 waves; never the XCD-L2 transport (one_kernel_xl2 knows no hybrid image kernel)."""
+    pl = plan(HQ, H, S, 128, dt)
+    assert pl["rt"] in (4, 8) and HQ // H == pl["rt"]
+    if not (pl["nt"] == 1 or (pl["nw"] == 4 and 1 < pl["nt"] <= 8)):
+        pl["nt"] = 0
+    return pl
+
+
+def quant_shape_list():
+    """-> [(family, dt, H, HQ, S, W, fmt)]"""
+    out = []
+    for fmt in Q.FORMATS:
+        for dt in (BF, HF):
+            out += [("hyb", dt, H, HQ, S, W_HYB, fmt) for (H, HQ, S) in QUANT_HYB_SHAPES]
+            out += [("ring", dt, H, HQ, S, W, fmt) for (H, HQ, S, W) in QUANT_RING_SHAPES]
+    return out
+
+
+def quant_shape_id(t):
+    fam, dt, H, HQ, S, W, fmt = t
+    return f"{fmt}-{fam}-{DT_NAME[dt]}-{H}-{HQ}-{S}-W{W}"
+
+
+def quant_cases_of(t, steps=None, states=None):
+    """Hybrid: the three start states; ring: the three fill levels (cases_of's, over the images)."""
+    fam, dt, H, HQ, S, W, fmt = t
+    st = steps or (16 if S <= 300 else 12)
+    off = 3 if dt == HF else 0
+    if fam == "hyb":
+        return [HybCase(dt, H, HQ, S, n + off, steps=st, quant=fmt) for n in (range(N_STATES) if states is None else states)]
+    return [RingCase(dt, H, HQ, S, W, fill, steps=st, seed=n + off, quant=fmt) for n, fill in enumerate(("brim", "minus3", "sparse"))]
+
+
 def intended_single_launch(c):
     """The hybrid step has a single-launch form where the plan has one and HQ / H is 4 or 8 with at most eight tiles; rings run two."""
     if c.family != "hyb":
         return False
+    if c.quant:
+        pl = quant_hybrid_plan(c.HQ, c.H, c.S, c.dt)
+        assert (pl["nw"], pl["nt"]) == QUANT_HYB_SHAPES[(c.H, c.HQ, c.S)], (c.id, pl)
+        return pl["nt"] > 0
     nw, nt, _ = HYB_SHAPES[(c.H, c.HQ, c.S)]
     assert (c.plan["nw"], c.plan["nt"] if c.R in (4, 8) else 0) == (nw, nt), (c.id, c.plan)
     return nt > 0
@@ -743,16 +841,27 @@ def intended_single_launch(c):
 def make_cache(c, dev):
     import cold_compress_amd.cache as cache
 
+    quant = getattr(c, "quant", None)
+    bits_ = Q.cache_bits(quant) if quant else None
+    extra = dict(cache_quant_mode=quant) if quant else {}
     if c.family == "hyb":
         cls, rk = cache.get_cache_constructor("hybrid")
-        kw = dict(max_cache_length=c.S, max_seq_length=c.S, cache_bits=None, global_tokens=c.g, token_ids=TOKEN_IDS, min_recovery_frac=0.9,
+        kw = dict(max_cache_length=c.S, max_seq_length=c.S, cache_bits=bits_, global_tokens=c.g, token_ids=TOKEN_IDS, min_recovery_frac=0.9,
                   hybrid_strategies=STRATEGIES)
     else:
         cls, rk = cache.get_cache_constructor("heavy_hitter")
-        kw = dict(max_cache_length=c.S, global_tokens=c.g, max_seq_length=4 * c.S + 64, cache_bits=None, history_window_size=c.W,
+        kw = dict(max_cache_length=c.S, global_tokens=c.g, max_seq_length=4 * c.S + 64, cache_bits=bits_, history_window_size=c.W,
                   recent_window=c.w, attn_thresholding=False)
     with torch.device(dev):
-        return cls(1, c.H, c.D, c.dt, **{k: kw[k] for k in rk})
+        return cls(1, c.H, c.D, c.dt, **{k: kw[k] for k in rk}, **extra)
+
+
+def _put_images(kv, sim, dev, lo=0):
+    """Slots [lo, S) of the cache's images and parameter words <- the simulator's."""
+    im = sim.images()
+    kv.k_cache_q[0, :, lo:] = torch.from_numpy(im["k_img"][:, lo:]).to(dev)
+    kv.v_cache_q[0, :, lo:] = torch.from_numpy(im["v_img"][:, lo:]).to(dev)
+    kv.kv_qparams.view(torch.int32)[0, :, lo:] = torch.from_numpy(im["qparams"][:, lo:].view(np.int32)).to(dev)
 
 
 def seed_cache(kv, c, sim, dev):
@@ -770,8 +879,17 @@ def seed_cache(kv, c, sim, dev):
         kv.punc_mask[0] = torch.from_numpy(c.punc0.astype(bool)).to(dev)
         kv.num_special.fill_(NSP0)
         kv.num_punc.fill_(NPU0)
-        kv.k_cache.copy_(sim.K[None])
-        kv.v_cache.copy_(sim.V[None])
+        if c.quant:
+            _put_images(kv, sim, dev)
+        else:
+            kv.k_cache.copy_(sim.K[None])
+            kv.v_cache.copy_(sim.V[None])
+    elif c.quant:  # the prompt's UNROUNDED rows through the class's own prefill (which quantises them); the poison as images
+        T = c.T
+        ip = torch.arange(T, device=dev)
+        kv.update_kv(ip, sim.K[None, :, :T].contiguous().to(dev), c.v_all[None, :, :T].contiguous().to(dev), True)
+        if T < S:
+            _put_images(kv, sim, dev, lo=T)
     else:
         T = c.T
         ip = torch.arange(T, device=dev)
@@ -838,7 +956,12 @@ def run_replay(c, form, dev, put=None, sync=None, dense=False, kv=None, steps=No
     seed_cache(kv, c, sim, dev)
     sync()
     n = compare_small(kv, sim, f"{c.id} [{form}] start state")
-    mk, mv = sim.K.clone().to(dev), sim.V.clone().to(dev)
+    if c.quant:
+        from step_exact import compare_images
+
+        assert form in ("two", "one"), "the fused quantised caches decode through decode_step() only"
+        n += compare_images(kv, sim, f"{c.id} [{form}] start state", dev, dequant=True)
+    mk, mv = (None, None) if c.quant else (sim.K.clone().to(dev), sim.V.clone().to(dev))
     small_kv = c.H * c.S * c.D <= (1 << 19)
     hyb = c.family == "hyb"
     for i in range(steps or c.steps):
@@ -862,10 +985,13 @@ def run_replay(c, form, dev, put=None, sync=None, dense=False, kv=None, steps=No
         a, b = bits(y).reshape(-1), bits(st["y"]).reshape(-1)
         assert np.array_equal(a, b), f"{where}: y: {_first_diff(a, b)} (heads select slots {st['slots'].tolist()}, insert at {st['idx']}: {st['kinds']})"
         n += a.size + compare_small(kv, sim, where)
+        last = i == (steps or c.steps) - 1
+        if c.quant:  # the images and the parameter words after every step; the device's decode of them after the last
+            n += compare_images(kv, sim, where, dev, dequant=last)
+            continue
         for h in range(c.H):
             if not (st["kinds"][h] == "drop" and sim.fault == "drop_unwritten"):
                 mk[h, st["idx"][h]], mv[h, st["idx"][h]] = k1[0, h, 0], v1[0, h, 0]
-        last = i == (steps or c.steps) - 1
         for name, got, mir, own in (("K", kv.k_cache[0], mk, sim.K), ("V", kv.v_cache[0], mv, sim.V)):
             assert torch.equal(got.view(torch.int16), mir.view(torch.int16)), f"{where}: {name} cache"
             if small_kv or last:
