@@ -491,9 +491,6 @@ static Plan make_plan_w(int HQ, int H, int S, int D, int dtype, bool wide_allowe
       wide_max = e ? atol(e) : 256;
     }
     if (tiles >= 1280 && (long)H * ((S + 127) / 128) <= wide_max) p.nw = 8;
-#if CC_V_NW16
-    if (p.nw == 8 && p.rt == 4 && tiles >= 2048 && g_wide_enabled.load(std::memory_order_relaxed) == 2) p.nw = 16;  // (A/B: see CC_V_NW16)
-#endif
   }
   const int rpi = rows_per_iter(D, dtype, p.nw);
   // ~512 workgroups (two per CU, all resident at once): one tile per workgroup up to S = 64 * 64 rows per kv
@@ -535,15 +532,15 @@ template <typename T, bool L2, bool HYB, int QB, int NSUB, int NW = kNW>
 static int launch_mfma_rt(const SplitArgs& a, int rt, dim3 grid, dim3 block, hipStream_t st) {
   if constexpr (sizeof(T) == 2) {
     switch (rt) {
-      case 8: hipLaunchKernelGGL((decode_attn_split_mfma_kernel<T, 8, NW, L2, false, HYB, QB, NSUB>), grid, block, 0, st, CC_LEAD_ARGS(a) a); break;
-      case 4: hipLaunchKernelGGL((decode_attn_split_mfma_kernel<T, 4, NW, L2, false, HYB, QB, NSUB>), grid, block, 0, st, CC_LEAD_ARGS(a) a); break;
+      case 8: hipLaunchKernelGGL((decode_attn_split_mfma_kernel<T, 8, NW, L2, false, HYB, QB, NSUB>), grid, block, 0, st, a); break;
+      case 4: hipLaunchKernelGGL((decode_attn_split_mfma_kernel<T, 4, NW, L2, false, HYB, QB, NSUB>), grid, block, 0, st, a); break;
       case 2:
         if constexpr (QB != 0 || NW != kNW) return CC_ERR_UNSUPPORTED;
-        else hipLaunchKernelGGL((decode_attn_split_mfma_kernel<T, 2, NW, L2, false, HYB, QB, NSUB>), grid, block, 0, st, CC_LEAD_ARGS(a) a);
+        else hipLaunchKernelGGL((decode_attn_split_mfma_kernel<T, 2, NW, L2, false, HYB, QB, NSUB>), grid, block, 0, st, a);
         break;
       default:
         if constexpr (QB != 0 || NW != kNW) return CC_ERR_UNSUPPORTED;
-        else hipLaunchKernelGGL((decode_attn_split_mfma_kernel<T, 1, NW, L2, false, HYB, QB, NSUB>), grid, block, 0, st, CC_LEAD_ARGS(a) a);
+        else hipLaunchKernelGGL((decode_attn_split_mfma_kernel<T, 1, NW, L2, false, HYB, QB, NSUB>), grid, block, 0, st, a);
         break;
     }
     return CC_OK;
@@ -650,9 +647,9 @@ static size_t base_workspace_bytes(const Plan& p, int HQ, int H, int S, int D, i
 // The answer is cached PER KERNEL: every instantiation has the same function type, so a cache keyed by the argument's type
 // (a `static` inside a template over the type) would be ONE cache for all of them — the first kernel asked would answer for
 // the fused-quant and multi-tile instantiations too, which keep fewer workgroups resident.
-static int one_capacity(void (*kernel)(CC_LEAD_TYPES SplitArgs), int threads) {
+static int one_capacity(void (*kernel)(SplitArgs), int threads) {
   struct Entry {
-    void (*k)(CC_LEAD_TYPES SplitArgs);
+    void (*k)(SplitArgs);
     int cap;
   };
   // readers take no lock: an entry is complete before the count that makes it visible is published (release / acquire); two
@@ -680,7 +677,7 @@ static int one_capacity(void (*kernel)(CC_LEAD_TYPES SplitArgs), int threads) {
   }
   return cap;
 }
-typedef void (*OneKernel)(CC_LEAD_TYPES SplitArgs);
+typedef void (*OneKernel)(SplitArgs);
 // The single-launch kernel that serves (query heads per kv head rt, tiles per wave nt, kind), or null.  kind: 0 = 16-bit cache
 // (heavy hitter / head-constant policies), 8 = fused quantised cache, -1 = l2, 200 = hybrid, 208 = hybrid over uint8 images;
 // kQbFp8 / 200 + kQbFp8 = the same two over FP8 images, kQbU4 / 200 + kQbU4 over 4-bit images, kQbMx4 / 200 + kQbMx4 over MXFP4 images (lean
@@ -715,9 +712,6 @@ static OneKernel one_kernel(int rt, int nt, int kind, bool full, int nw = kNW) {
   if (kind == kQbFp8 || kind == 200 + kQbFp8) return one_kernel_img<T, kQbFp8>(rt, nt, kind != kQbFp8, full, nw);
   if (kind == kQbU4 || kind == 200 + kQbU4) return one_kernel_img<T, kQbU4>(rt, nt, kind != kQbU4, full, nw);
   if (kind == kQbMx4 || kind == 200 + kQbMx4) return one_kernel_img<T, kQbMx4>(rt, nt, kind != kQbMx4, full, nw);
-#if CC_V_NW16
-  if (nw == 16) return (rt == 4 && nt == 1 && kind == 0 && !full) ? decode_attn_split_mfma_kernel<T, 4, 16, false, true, false, 0, 1, 1, false> : nullptr;
-#endif
   if (nw == 8) {  // ONE 8-wave workgroup per CU: 4 or 8 query heads per kv head, one tile per wave (make_plan)
 #define CC_ONE_W(RT_, L2_, QB_, FULL_) decode_attn_split_mfma_kernel<T, RT_, 8, L2_, true, false, QB_, 1, 1, FULL_>
 #define CC_ONE_WH(RT_, FULL_) decode_attn_split_mfma_kernel<T, RT_, 8, false, true, true, 0, 1, 1, FULL_>
@@ -808,9 +802,6 @@ template <typename T>
 static OneKernel one_kernel_xl2(int rt, int nt, int kind, bool full, int nw) {
 #define CC_ONE_X(RT_, NW_, L2_, QB_, FULL_) decode_attn_split_mfma_kernel<T, RT_, NW_, L2_, true, false, QB_, 1, 1, FULL_, true>
 #define CC_ONE_XM(RT_, HYB_, NT_) decode_attn_split_mfma_kernel<T, RT_, kNW, false, true, HYB_, 0, 1, NT_, false, true>
-#if CC_V_NW16
-  if (nw == 16) return (rt == 4 && nt == 1 && kind == 0 && !full) ? CC_ONE_X(4, 16, false, 0, false) : nullptr;
-#endif
   if ((rt != 4 && rt != 8) || (nw != 4 && nw != 8)) return nullptr;
   if (nt > 1 || kind == 200) {  // several tiles per wave (4-wave workgroups) and the hybrid cache's steps: lean instantiations only
     if (full || nt > kOneMaxTiles) return nullptr;
@@ -900,9 +891,7 @@ size_t cc_decode_attn_workspace_bytes(int32_t HQ, int32_t H, int32_t S, int32_t 
 }
 
 // kind: see one_kernel.  Returns the kernel when the shape is eligible AND all its workgroups stay resident at once, else null.
-static OneKernel one_pick(int32_t HQ, int32_t H, int32_t S, int32_t D, int32_t dtype, int kind, bool full, bool allow_xl2 = false,
-                          bool* is_xl2 = nullptr) {
-  if (is_xl2) *is_xl2 = false;
+static OneKernel one_pick(int32_t HQ, int32_t H, int32_t S, int32_t D, int32_t dtype, int kind, bool full, bool allow_xl2 = false) {
   if (HQ <= 0 || H <= 0 || HQ % H || S <= 0 || D <= 0 || !cc_dt_ok(dtype)) return nullptr;
   const Plan p = make_plan(HQ, H, S, D, dtype);
   const int nt = one_tiles(p, HQ, H, D, dtype);
@@ -910,14 +899,9 @@ static OneKernel one_pick(int32_t HQ, int32_t H, int32_t S, int32_t D, int32_t d
   // l2: every thread gathers at most three workgroups' norm maxima
   if (kind == -1 && H * p.n_split > 3 * p.nw * 64) return nullptr;
   // XL2 first: a multiple of 8 kv heads (each head's workgroups on one XCD) on a device whose dispatch order was verified
-  // (r6 A/B, CC_V_FEWXCD: 1, 2 or 4 kv heads on a grid of 8 virtual ones — every XCD must hold a head's n_split workgroups)
-  const bool virt8 = CC_V_FEWXCD != 0 && (H == 1 || H == 2 || H == 4);
-  if (allow_xl2 && ((H & 7) == 0 || virt8) && xl2_device_ok()) {
+  if (allow_xl2 && (H & 7) == 0 && xl2_device_ok()) {
     const OneKernel kx = one_kernel_xl2_dt(dtype, p.rt, nt, kind, full, p.nw);
-    if (kx && p.n_split * (virt8 ? 8 : H) <= one_capacity(kx, p.nw * 64)) {
-      if (is_xl2) *is_xl2 = true;
-      return kx;
-    }
+    if (kx && p.n_split * H <= one_capacity(kx, p.nw * 64)) return kx;
   }
   const OneKernel k = one_kernel_dt(dtype, p.rt, nt, kind, full, p.nw);
   if (!k) return nullptr;
@@ -979,7 +963,6 @@ int32_t cc_decode_step_device_single_launch(int32_t enabled) {
 }
 
 int32_t cc_decode_step_status_offset(void) { return kOneStatusWord * (int32_t)sizeof(unsigned); }
-int32_t cc_decode_step_l2_carry(void) { return CC_V_L2CARRY != 0 ? 1 : 0; }
 int32_t cc_decode_step_wait_bound_us(void) { return (int32_t)(kOneWaitTicks / 100ull); }  // (s_memrealtime: 100 ticks per microsecond)
 int32_t cc_decode_step_commit_stride(void) { return kRcStride; }
 
@@ -990,7 +973,7 @@ void cc_decode_step_set_single_launch(int32_t enabled) { g_one_enabled.store(ena
 // 8-wave workgroups (one per CU) for the plain 16-bit caches that have the tiles for them (make_plan); 0 = 4-wave workgroups
 // everywhere.  Process-wide; change it only between steps of a cache whose fused pipeline is re-seeded (prepare_decode): the
 // geometry decides which entries of a head's key row are live.
-void cc_decode_step_set_wide(int32_t enabled) { g_wide_enabled.store(enabled == 2 && CC_V_NW16 != 0 ? 2 : (enabled ? 1 : 0), std::memory_order_relaxed); }
+void cc_decode_step_set_wide(int32_t enabled) { g_wide_enabled.store(enabled ? 1 : 0, std::memory_order_relaxed); }
 
 // The L2-resident hand-off (XL2): on by default where cc_decode_step_probe_xcd verified the device; 0 = always the memory hand-off
 // (the fallback of a step that fails with it — a kernel captured into a hipGraph keeps the form it was captured with).
@@ -1142,9 +1125,6 @@ static int attn_impl(const void* q, const void* k, const void* v, const uint8_t*
     sa.H = H; sa.Hc = fs->c->Hc; sa.Hp = fs->c->Hp;
     sa.commit = fs->commit;
   }
-#if CC_V_PRELOAD
-  if (sa.nk_read > kLeadNkReadMax || H > kLeadHMax) return CC_ERR_UNSUPPORTED;  // (the packed preloaded word: 2^20 live key entries, 2047 kv heads)
-#endif
   hipStream_t st = (hipStream_t)stream;
   int rc = CC_OK;
   if (fs && fs->qkv) {
@@ -1181,10 +1161,9 @@ static int attn_impl(const void* q, const void* k, const void* v, const uint8_t*
     // there is one (a time stamp alone is not worth leaving the product kernel for)
     const bool want_full = attn_out != nullptr || sa.abl != 0;
     OneKernel kern = nullptr;
-    bool kern_xl2 = false;
     if (policy_ok && (!rh || fs->policy == 6) && !probs_out && !attn_out_needs_probs(fs, attn_out)) {
-      if (want_full || g_one_trace) kern = one_pick(HQ, H, S, D, dtype, kind, true, true, &kern_xl2);
-      if (!kern && !want_full) kern = one_pick(HQ, H, S, D, dtype, kind, false, true, &kern_xl2);
+      if (want_full || g_one_trace) kern = one_pick(HQ, H, S, D, dtype, kind, true, true);
+      if (!kern && !want_full) kern = one_pick(HQ, H, S, D, dtype, kind, false, true);
     }
     const bool one_ok = kern != nullptr;
     if (one_asked && !one_ok) return CC_ERR_UNSUPPORTED;
@@ -1204,20 +1183,12 @@ static int attn_impl(const void* q, const void* k, const void* v, const uint8_t*
           sa.ring_num = rh->num; sa.ring_acc = reinterpret_cast<unsigned long long*>(rh->acc); sa.ring_wsum = rh->wsum;
         }
       }
-#if CC_V_PRELOAD
-      // (the XL2 instantiations take their (kv head, split) from a linear block index: a 1-D grid, the head count preloaded)
-      sa.virt8 = (kern_xl2 && (H & 7) != 0) ? 1 : 0;
-      const dim3 one_grid = kern_xl2 ? dim3(p.n_split * (sa.virt8 ? 8 : H), 1, 1) : dim3(p.n_split, H, 1);
-#else
       const dim3 one_grid(p.n_split, H, 1);
-      (void)kern_xl2;
-#endif
-      hipLaunchKernelGGL(kern, one_grid, dim3(p.nw * 64), 0, st, CC_LEAD_ARGS(sa) sa);
+      hipLaunchKernelGGL(kern, one_grid, dim3(p.nw * 64), 0, st, sa);
       CC_LAUNCH_CHECK();
       return CC_OK;
     }
   }
-  if (p.nw == 16) return CC_ERR_UNSUPPORTED;  // (the 16-wave A/B geometry has no two-launch form)
   if (phases & 1) {
     switch (dtype) {
       case CC_DT_F32: rc = launch_split<float>(sa, p, H, R, D, st); break;
@@ -1254,10 +1225,6 @@ static int attn_impl(const void* q, const void* k, const void* v, const uint8_t*
     default: hipLaunchKernelGGL(decode_attn_combine_kernel<f16_t>, grid, block, lds, st, ca); break;
   }
   CC_LAUNCH_CHECK();
-  // l2: the norm record the NEXT step's single-launch form starts from (cc_common.h, cc_l2_record) — the single-launch step leaves
-  // it itself; behind the two launches a third, small one does (this is the slow route already)
-  if (CC_V_L2CARRY != 0 && fs && fs->policy == 4 && fs->next_key)  // (only the r6 A/B build's single-launch step reads it)
-    return cc_l2_record_launch(sa.key_norm, H, S, dtype, fs->input_pos, 0, fs->next_key, st);
   return CC_OK;
 }
 

@@ -6,108 +6,17 @@
 #include "cc_wacc.h"
 #include "cc_gemv_core.h"
 
-// ---- A/B switches (tools/ab_variant.sh NAME "-DCC_V_...=0"): the defaults are what the product runs.  Round 4 measured each on one
-//      box against its absence (profiles/r04_ab_step_variants.md); the switches that lost (early partial-O polls, one key per
-//      workgroup, precomputed merge factors, bulk requests moved up, longer sleeps) are gone from the source (commit a08483f has them).
-#ifndef CC_V_PRO
-#define CC_V_PRO 1      // prologue diet: unconditional key-row loads, K rows requested ahead of the mask word
-#endif
-#ifndef CC_V_LDSDMA
-#define CC_V_LDSDMA 1   // K / V tiles land in the wave's LDS slabs directly (buffer_load ... lds): no staging registers, no ds_write
-#endif
-#ifndef CC_V_EMLMT
-#define CC_V_EMLMT 0    // 1: the several-tiles-per-wave steps take the early-(m, l) order too — MEASURED A LOSS (r4, one box: S = 8192 12.3 ->
-                        // 12.8 us, 18432 21.0 -> 21.75, 32768 32.8 -> 33.9): two gathers in series and one more barrier, and per-slot passes
-                        // of 1.5+ us that a 0.4 us partial-O round trip cannot hide; kept compilable for the record
-#endif
-#ifndef CC_V_ALLLANES
-#define CC_V_ALLLANES 1 // the several-tiles-per-wave steps run the per-slot state pass on all 64 lanes (like the hybrid tail), not on 16 per tile
-#endif
-#ifndef CC_V_WORDSFIRST
-#define CC_V_WORDSFIRST 1  // the step's words (epoch, position, status, commit words) are requested at the top of the kernel
-#endif
-#ifndef CC_V_KPIN
-#define CC_V_KPIN 1  // the prologue's kernel arguments in one round of scalar loads, BEHIND the request of the step's words (0: left to the compiler, three rounds)
-#endif
-#ifndef CC_QKV_TILE_AT
-#define CC_QKV_TILE_AT 2  // QKV step: where the K / V tile is requested — 0: ahead of the weights (20.0 us per layer at C3), 1: behind the first
-                          // unit's request (20.5), 2: behind the LAST unit's request (19.1; the product) — A/B, r5, same box
-#endif
-#ifndef CC_QKV_DEPTH
-#define CC_QKV_DEPTH 2  // QKV step: 4-row weight units (8 loads per lane each) in flight per wave: 2 (18.9 us per layer at C3) or 3 (19.6) — A/B, r5
-#endif
+// ---- A/B switches: none left.  Every variant this header once carried behind a compile-time switch was decided by measurement, and
+//      the losers are gone from the source.  Round 4 (profiles/r04_ab_step_variants.md; commit a08483f has the code): early partial-O
+//      polls, one key per workgroup, precomputed merge factors, bulk requests moved up, longer sleeps.  Rounds 5 and 6
+//      (the two profiles/r06_ab_*.md hold the numbers; commit 628d474 is the last one that has the code): the early-(m, l)
+//      order for several tiles per wave, the 14-dword preloaded-argument prologue with its two-phase argument block and request
+//      orders, the V rows requested early or behind a sleep, the single-XCD virtual-head placement of few-head ranks, the l2 carried
+//      norm record, branch-free small loads, the merge factors kept in LDS, the 16-wave geometry, the QKV step's other tile
+//      placements and its depth of 3, and the switches that turned the product's own prologue diet, LDS-DMA tiles, all-lane state
+//      pass, words-first order, pinned argument loads and last-wave (M, L) fold OFF.  What is below is what the product runs.
 #ifndef CC_QKV_TRACE
 #define CC_QKV_TRACE 0  // 1 (measurement builds of cc_attn_decode_qkv.hip only): thread 0 of every workgroup stamps the phases of the QKV step
-#endif
-#ifndef CC_V_PRELOAD
-#define CC_V_PRELOAD 0  // r6 A/B (VERDICT r5 #1b, "the prologue"): 1 = the operands of the step's FIRST requests (its words, the key row, the K
-                        // rows) are leading scalar kernel arguments, preloaded into SGPRs at wave launch (-mllvm
-                        // -amdgpu-kernarg-preload-count=14; tools/probes/preload_probe shows the firmware honours it, also under graph
-                        // replay): no kernel-argument round trip in front of the first K request.  MEASURED (profiles/r06_ab_step_variants.md):
-                        // with LATE + EARLYARGS below the first K request leaves 0.46-0.59 us after a workgroup's first instruction
-                        // instead of 0.85 — and the K rows LAND when they always did (2.9 us at C3, 1.6-1.7 at one kv head): the step is
-                        // 0.05-0.1 us SLOWER at C3 / C2, 0.05 faster at C5's rank.  What bounds the first byte is not when it is asked
-                        // for (tools/probes/first_byte_probe).  Off: the r5 prologue is the product's.
-#endif
-#ifndef CC_V_LATE
-#define CC_V_LATE 1     // r6 A/B: with the preloaded arguments, the LDS-DMA steps read the rest of their argument block BEHIND the first K request
-                        // (0: left to the compiler, which puts scalar waits in front of the K request in 37 of 47 instantiations)
-#endif
-#ifndef CC_V_EARLYARGS
-#define CC_V_EARLYARGS 1  // r6 (LATE steps): the rest of the argument block is REQUESTED at the kernel's first instruction — scalar loads spelled
-                          // in assembly, which the compiler's wait-count pass does not see — and waited for once, behind the K request:
-                          // the round trip runs in the shadow of the prologue instead of behind it (0: requested behind the K request)
-#endif
-#ifndef CC_V_ORDER
-#define CC_V_ORDER 0    // r6 A/B (with PRELOAD + LATE + EARLYARGS, plain 16-bit steps): 1 = the step's SMALL requests first — words, key row, per-slot
-                        // state, q — and the bulk (K rows, mask word, V rows) behind them, all within the first ~150 instructions: nothing
-                        // the scores need queues behind 8 MB of rows, and the V rows leave ~0.4 us earlier than in the product's order
-#endif
-#ifndef CC_V_VEARLY
-#define CC_V_VEARLY 0   // r6 A/B: the V rows requested right behind the K rows (1: the steps without the XL2 placement — few-head ranks, whose
-                        // caches are latency-bound, not bandwidth-bound; 2: every LDS-DMA step).  At C3 this order lost 0.4 us (r4).
-#endif
-#ifndef CC_V_FEWXCD
-#define CC_V_FEWXCD 0   // r6 A/B: ranks with 1, 2 or 4 kv heads take the XL2 instantiations on a grid of 8 VIRTUAL heads — block b works for kv head
-                        // b % 8 when that is < H and exits otherwise: a head's workgroups share ONE XCD, its hand-off stays in that L2
-#endif
-#if CC_V_FEWXCD && !CC_V_PRELOAD
-#error "the virtual-head placement takes its head counts from the preloaded arguments"
-#endif
-#ifndef CC_V_L2CARRY
-#define CC_V_L2CARRY 0  // r6: the l2 single-launch step carries each head's norm maximum across steps (a resolved RECORD in the
-                        // key row's tail: cc_common.h, cc_l2_record) — no reduction over the head's norms and NO cross-head hand-off inside
-                        // the launch; see L2C in the kernel.  0 = the r4 / r5 exchange (one level through memory, or two with XL2).
-#endif
-#ifndef CC_V_FLATLOADS
-#define CC_V_FLATLOADS 0  // r6: in the LDS-DMA steps every small load between the key row and the V rows (mask word, per-slot state, q) is issued
-                          // by ALL lanes, unconditionally (lanes without a row / slot / head aim at a valid dummy or past a buffer's end):
-                          // behind exec-mask branches the compiler's wait-count pass could not count them, its wait for the KEY ROW became
-                          // vmcnt(8) — a wait for the K tile — and the key row's reduction, the insert decision and the commit words
-                          // (~100 instructions) ran on every wave's critical path BEHIND the K rows instead of in the two microseconds the
-                          // wave waits for them (found in the ISA while measuring the l2 cuts).  MEASURED A LOSS (same box, three rounds:
-                          // C3 8.38 -> 8.51, C2 7.53 -> 7.84, C5's rank 7.68 -> 7.87, recent_global 8.05 -> 8.23): the wait becomes exact
-                          // (vmcnt(16)) and the reduction does move up — and the V rows, no longer held back by five branches, leave
-                          // earlier and compete with the K rows, the order r4 measured at +0.1..0.4 us.  0 = the r5 form (the product).
-#endif
-#ifndef CC_V_WFACT
-#define CC_V_WFACT 0    // r6: the early-(m, l) steps keep the waves' merge factors exp(m_w - M) — computed once per (wave, head) by the lane that
-                        // merges the workgroup's (m, l) pair, between the scores and the P.V products — in LDS; the partial-O publish behind
-                        // the merge barrier reads them instead of recomputing NW maxima, subtractions and exponentials per thread (~50 of its
-                        // ~110 instructions, on every workgroup's path between the merge barrier and its partial O).  Same function, same
-                        // operands: the same bits.  0 = recompute (r5)
-#endif
-#ifndef CC_V_NW16
-#define CC_V_NW16 0     // r6 A/B: cc_decode_step_set_wide(2) plans ONE 16-wave workgroup per 256 rows (n_split 16 at S = 4096: half the partials of
-                        // the hand-off again — the move from 4 to 8 waves gained 0.4 us at C3 — on half the CUs); heavy hitter / head-constant
-                        // policies, 4 query heads per kv head, single launch only, timing experiments only (no two-launch twin of this geometry)
-#endif
-#ifndef CC_V_VDELAY
-#define CC_V_VDELAY 0   // r6 A/B: s_sleep CC_V_VDELAY (x 64 cycles) in front of the V rows' request in the LDS-DMA steps — the opposite of
-                        // CC_V_VEARLY / CC_V_FLATLOADS, which both lost by letting the V rows compete with the K rows earlier
-#endif
-#ifndef CC_V_MLW
-#define CC_V_MLW 1      // the final (M, L) fold runs on the workgroup's LAST waves (idle during the partial-O publish of the first ones)
 #endif
 
 namespace {
@@ -350,23 +259,7 @@ struct SplitArgs {
   //      pair per (head, slot) row for K and one for V — dequantised in registers on the way to the LDS slabs
   float* qparams;     // [H, S, 4]: k_scale, k_min, v_scale, v_min (FP8: 2^e_k, 0, 2^e_v, 0)
   QkvIn qkv;          // QKV instantiations only: q / k_new / v_new are null, the step computes them itself
-  int virt8;          // XL2 instantiations (r6, CC_V_FEWXCD): the grid has 8 virtual kv heads, blocks of heads >= H exit (travels in the preloaded word)
 };
-
-// PRELOAD (r6): 14 dwords — all the hardware preloads — in front of the argument block: K base, S, rows per split, the key rows, their
-// stride, (live entries | kv heads << 20), the workspace header, the position word, the commit words.  The kernel takes THESE instead of
-// the block's copies (the launcher fills both alike: cc_lead_of).
-#if CC_V_PRELOAD
-#define CC_LEAD_PARAMS const void* pl_k, int pl_S, int pl_rps, const unsigned long long* pl_key, int pl_nk, int pl_misc, unsigned* pl_hdr, const int32_t* pl_pos, int32_t* pl_commit,
-#define CC_LEAD_TYPES const void*, int, int, const unsigned long long*, int, int, unsigned*, const int32_t*, int32_t*,
-#define CC_LEAD_ARGS(sa) (sa).k, (sa).S, (sa).rows_per_split, (sa).next_key, (sa).nk, (int)((unsigned)(sa).nk_read | ((unsigned)(sa).H << 20) | ((sa).virt8 ? 0x80000000u : 0u)), (sa).one_hdr, (sa).input_pos, (sa).commit,
-constexpr int kLeadNkReadMax = (1 << 20) - 1, kLeadHMax = (1 << 11) - 1;
-#else
-#define CC_LEAD_PARAMS
-#define CC_LEAD_TYPES
-#define CC_LEAD_ARGS(sa)
-#endif
-constexpr int kLeadBytes = CC_V_PRELOAD ? 56 : 0;  // 14 dwords (pointers on 8-byte boundaries: see the parameter list)
 
 template <typename T, int D, int RT, int NW, int U>
 __global__ __launch_bounds__(NW * 64) void decode_attn_split_kernel(SplitArgs a) {
@@ -740,7 +633,7 @@ constexpr int kRcStride = 68;                  // step_commit: int32 per kv head
 // its own, and the two heads' epochs need not be equal once launches with fewer heads have run).
 constexpr int kOneMlHead = 64 * 8 * 16;        // (m, l): 64 splits x up to 8 query heads x 16 B
 constexpr int kOneOHead = 8 * 64 * 64 * 16;    // O: up to 8 query heads x 64 splits x 64 pairs x 16 B
-constexpr int kOneNmHead = 64 * 32;            // l2: one norm-maximum granule per split (r4 / r5 exchange), or two record granules per split (r6, L2C)
+constexpr int kOneNmHead = 64 * 32;            // l2: one norm-maximum granule per split
 constexpr int kOneHmBytes = 32 * 32 * 16;      // l2, two-level exchange (r4): one norm-maximum granule per kv HEAD, behind the per-split regions (the first
                                                // 32 granules; the rest of the 16 KiB was the [dest head][src head] matrix of r6's first carried-record
                                                // cut — in the history — and is unused now)
@@ -978,7 +871,7 @@ struct IntC {
 // tile's 16.8 MB stream in the shadow of the 50 MB of weights: one launch boundary, one prologue and one first-byte latency per
 // attention sub-block instead of two.  One workgroup per CU (the LDS decides that anyway): 256 registers per lane.
 template <typename T, int RT, int NW, bool L2, bool ONE = false, bool HYB = false, int QB = 0, int NSUB = 1, int NT = 1, bool FULL = !ONE, bool XL2 = false, bool QKV = false>
-__global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2 : 1))) void decode_attn_split_mfma_kernel(CC_LEAD_PARAMS SplitArgs a_in) {
+__global__ __launch_bounds__(NW * 64, QKV ? 1 : ((ONE || QB) ? 2 : 1)) void decode_attn_split_mfma_kernel(SplitArgs a_in) {
   // FULL (measurement instantiation): the workgroup's first instruction, on both clocks — the phases of cc_decode_step_trace count
   // from HERE (late r4; they used to count from behind the issue of the first K rows, ~0.8 us later)
   unsigned long long tr_entry = 0, rt_entry = 0;
@@ -986,77 +879,8 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
     tr_entry = __builtin_amdgcn_s_memtime();
     rt_entry = __builtin_amdgcn_s_memrealtime();  // 100 MHz, one clock for the whole device (s_memtime is per XCD)
   }
-  // LATE (r6, with the preloaded arguments; the LDS-DMA steps): the argument block is read in TWO PHASES.  Phase 0 — entry to the
-  // first K request — runs on the 14 preloaded dwords alone: the step's words, the key row and the K rows are requested without one
-  // kernel-argument load having been issued, so nothing the compiler does with scalar registers can put a wait in front of them
-  // (left to the compiler, 37 of 47 LDS-DMA instantiations had an `s_waitcnt lgkmcnt(0)` there: a scalar register reused while an
-  // argument load into it was pending — tools/isa_first_request_audit.py).  Phase 1 — right behind the K request — fetches the rest
-  // of the block in one round of scalar loads through a laundered kernarg pointer (late_phase below): one round trip, in the shadow
-  // of the K rows.
-  constexpr bool LATE = CC_V_PRELOAD != 0 && CC_V_LATE != 0 && CC_V_LDSDMA != 0 && ONE && NT == 1 && QB == 0 && !HYB && !QKV;
-  constexpr bool SMALLFIRST = LATE && CC_V_EARLYARGS != 0 && CC_V_ORDER != 0 && !L2;
   SplitArgs a{};
-  if constexpr (!LATE) a = a_in;
-#if CC_V_PRELOAD
-  // the preloaded copies REPLACE the argument block's (same values: CC_LEAD_ARGS): every use below reads an SGPR that was there
-  // when the wave started, not a kernel-argument load
-  auto apply_lead = [&]() {
-    a.k = pl_k;
-    a.S = pl_S;
-    a.rows_per_split = pl_rps;
-    a.next_key = pl_key;
-    a.nk = pl_nk;
-    a.nk_read = pl_misc & kLeadNkReadMax;
-    a.one_hdr = pl_hdr;
-    a.input_pos = pl_pos;
-    a.commit = pl_commit;
-  };
-  apply_lead();
-  const int lead_H = (int)(((unsigned)pl_misc >> 20) & (unsigned)kLeadHMax);
-  // EARLY (LATE steps): phase 1's scalar loads go out HERE, as the kernel's first instructions, in assembly — the compiler does not
-  // know that these registers are pending and therefore never waits for them (nor may it read them: nothing touches ea* until the
-  // `s_waitcnt lgkmcnt(0)` of late_phase hands them over; tools/isa_first_request_audit.py checks that in the ISA).  Offsets: the
-  // block starts kLeadBytes into the kernel-argument segment; the static_asserts pin the fields.
-  typedef unsigned ea_x8 __attribute__((ext_vector_type(8)));
-  typedef unsigned ea_x4 __attribute__((ext_vector_type(4)));
-  typedef unsigned ea_x2 __attribute__((ext_vector_type(2)));
-  constexpr bool EARLY = LATE && CC_V_EARLYARGS != 0;
-  if constexpr (EARLY && FULL) asm volatile("" : "+s"(tr_entry), "+s"(rt_entry));  // (the entry stamps are scalar-memory results too: waited for HERE, ahead of the loads below)
-  ea_x8 ea_q = {}, ea_kn = {}, ea_ct = {}, ea_ao = {};
-  ea_x4 ea_r = {}, ea_rn = {};
-  ea_x2 ea_hp = {}, ea_y = {}, ea_nrm = {}, ea_tr = {};
-  unsigned ea_abl = 0;
-  if constexpr (EARLY) {
-    static_assert(offsetof(SplitArgs, q) == 0 && offsetof(SplitArgs, v) == 16 && offsetof(SplitArgs, mask) == 24, "ea_q");
-    static_assert(offsetof(SplitArgs, R) == 60 && offsetof(SplitArgs, n_split) == 64 && offsetof(SplitArgs, scale) == 72 && offsetof(SplitArgs, abl) == 76, "ea_r");
-    static_assert(offsetof(SplitArgs, k_new) == 104 && offsetof(SplitArgs, v_new) == 112 && offsetof(SplitArgs, pos) == 120 && offsetof(SplitArgs, mask_w) == 128, "ea_kn");
-    static_assert(offsetof(SplitArgs, cache_cts) == 136 && offsetof(SplitArgs, num) == 144 && offsetof(SplitArgs, denom) == 152 && offsetof(SplitArgs, H) == 160 &&
-                  offsetof(SplitArgs, Hc) == 164 && offsetof(SplitArgs, Hp) == 168, "ea_ct / ea_hp");
-    static_assert(offsetof(SplitArgs, key_norm) == 224 && offsetof(SplitArgs, y) == 280, "ea_nrm / ea_y");
-    static_assert(offsetof(SplitArgs, attn_out) == 288 && offsetof(SplitArgs, hh_counter) == 296 && offsetof(SplitArgs, g) == 304 && offsetof(SplitArgs, w) == 308 &&
-                  offsetof(SplitArgs, policy) == 312, "ea_ao");
-    static_assert(offsetof(SplitArgs, rand_next) == 320 && offsetof(SplitArgs, rng_seed) == 328 && offsetof(SplitArgs, trace) == 344, "ea_rn / ea_tr");
-    static_assert(kLeadBytes == 56, "the immediates below are 56 + the field's offset");
-    typedef const char __attribute__((address_space(4))) kernarg_b;
-    kernarg_b* kp0 = (kernarg_b*)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile(
-        "s_load_dwordx8 %0, %11, 0x38\n\t"    // q, k, v, mask
-        "s_load_dwordx8 %1, %11, 0xa0\n\t"    // k_new, v_new, pos, mask_w
-        "s_load_dwordx8 %2, %11, 0xc0\n\t"    // cache_cts, num, denom, H, Hc
-        "s_load_dwordx2 %6, %11, 0xe0\n\t"    // Hp
-        "s_load_dwordx4 %4, %11, 0x74\n\t"    // R, n_split, rows_per_split, scale
-        "s_load_dwordx2 %7, %11, 0x150\n\t"   // y
-        "s_load_dwordx8 %3, %11, 0x158\n\t"   // attn_out, hh_counter, g, w, policy
-        "s_load_dwordx4 %5, %11, 0x178\n\t"   // rand_next, rng_seed
-        "s_load_dwordx2 %8, %11, 0x118\n\t"   // key_norm
-        "s_load_dwordx2 %9, %11, 0x190\n\t"   // trace
-        "s_load_dword %10, %11, 0x84"           // abl
-        : "=s"(ea_q), "=s"(ea_kn), "=s"(ea_ct), "=s"(ea_ao), "=s"(ea_r), "=s"(ea_rn), "=s"(ea_hp), "=s"(ea_y), "=s"(ea_nrm), "=s"(ea_tr), "=s"(ea_abl)
-        : "s"(kp0));
-  }
-#else
-  auto apply_lead = [&]() {};
-#endif
+  a = a_in;
   static_assert(!(HYB && L2), "the hybrid decision rides the plain streaming pass or the single-launch step");
   static_assert(QB == 0 || ((QB == 8 || QB == kQbFp8 || QB == kQbU4 || QB == kQbMx4) && !L2 && !QKV),
                 "fused quantised cache: uint8, FP8 or 4-bit images, heavy hitter (W = 1 or the ring) / recent_global / random / hybrid");
@@ -1067,55 +891,26 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
   // EML (r3): the workgroup's (m, l) pairs leave EARLY — right behind the scores, while the V rows are still in flight — so that
   // the final (M, L) of the head, the probabilities, the history update and the next-eviction keys run in the shadow of the
   // partial-O exchange; what is left behind the last O granule is the y fold alone
-  // (l2 included since late r3: its norm maxima leave with the (m, l) pairs.  r4: the several-tiles-per-wave steps too — their pairs
-  //  leave behind the LAST tile, ahead of the cross-wave merge: the finish's per-slot passes then run in the shadow of the partial-O
-  //  exchange instead of behind it, the state stores sit behind the last gather, and the step is recoverable like the single-tile one.)
-  constexpr bool EML = ONE && !HYB && (NT == 1 || CC_V_EMLMT != 0);
-#ifdef CC_NO_RC  // (A/B builds)
-  constexpr bool RC = false;
-#else
+  // (l2 included since late r3: its norm maxima leave with the (m, l) pairs.)
+  constexpr bool EML = ONE && !HYB && NT == 1;
   constexpr bool RC = EML;  // the recoverable hand-off (status / commit / fail words, state stores behind the last gather) rides the same kinds
-#endif
   // NRC (late r4): the single-launch steps whose tail keeps the memory order (one gather: (m, l) and O travel together) — the
   // hybrid step and the several-tiles-per-wave steps — are recoverable too when the caller passes commit words (a.commit): the
   // whole commit (y, history / ring column / window sums, keys, counts) sits behind that gather.  HRC: the hybrid part of it (the
   // recorded decision carries the kind, the head's count and the ring column as well).
-#ifdef CC_NO_HRC  // (A/B builds)
-  constexpr bool NRC = false;
-#else
   constexpr bool NRC = ONE && !EML;
-#endif
   constexpr bool HRC = NRC && HYB;
   // L2X (r4): the l2 policy's norm maximum crosses kv heads (cache.py:602).  With the placement of XL2 it travels in two levels:
   // the workgroups' maxima inside the head's XCD (plain granules, gathered with the (m, l) pairs by one wave), then ONE granule
   // per kv head through memory (published by the head's split-0 workgroup, gathered by one wave per workgroup in the shadow of the
   // partial-O exchange) — instead of every thread of every workgroup gathering all H x n_split maxima through memory ahead of the
   // final (M, L).  max is associative: the same value, hence the same keys, bit for bit.
-  // L2C (r6): the carried norm record — see CC_V_L2CARRY.  cache.py:602 takes the maximum of the norms over ALL kv heads and slots; the
-  // step of position p leaves, per kv head, the maximum over the slots the head KEEPS at p + 1 (everything but the slot p + 1 evicts:
-  // that slot is the arg-min of the keys this very step scores) in the head's key row tail.  The step of p + 1 then needs no reduction
-  // over norms and no hand-off between heads, and — the l2 keys depend on nothing the attention computes — the workgroup's LAST wave
-  // does the policy's whole per-slot pass alone, between its scores and its P.V products (the V rows are still landing):
-  //   loads   (that wave only, between the K and the V rows) the new keys of all kv heads, the heads' records, position and norm of
-  //           every slot of the workgroup;
-  //   fold    the new keys' norms (the inserting row group's arithmetic, bit for bit: four heads per pass, one per row group) ->
-  //           max over heads of max(record, new norm) = the maximum at this position; the keys of the workgroup's slots, their
-  //           minimum, the slots' two largest norms after the insert (with a holder) -> two granules inside the head's XCD; the
-  //           minimum key goes to the wave's entry of the key row with the step's commit (the other waves' entries stay ~0);
-  //   record  the last wave of the head's split-0 workgroup gathers the workgroups' granules with the partial-O round (they left a
-  //           whole streaming phase earlier), finds the slot position p + 2 will evict, resolves the head's maximum without it and
-  //           stores the record of THIS position with the step's commit (entry [live + (p & 1)]: a retry of p still finds p - 1's in
-  //           the other entry).
-  // Nothing of the r4 / r5 exchange is left in the launch: no norm maxima with the (m, l) pairs, no level-one / level-two gathers, no
-  // per-slot pass in the tail, no per-slot state in the other waves.  Seeds and two-launch steps leave the same record through
-  // l2_record_kernel (cc_evict.hip).
-  constexpr bool L2C = L2 && EML && CC_V_L2CARRY != 0;
-  constexpr bool L2X = L2 && XL2 && EML && !L2C;
+  constexpr bool L2X = L2 && XL2 && EML;
   static_assert(sizeof(T) == 2 && (RT == 1 || RT == 2 || RT == 4 || RT == 8), "16-bit caches, up to 8 query heads per pass (the MFMA has 16 columns)");
-  static_assert(!ONE || NW == 4 || ((NW == 8 || (NW == 16 && !L2 && !HYB && QB == 0 && !QKV)) && NT == 1),
-                "the single-launch step runs on 4-wave workgroups, or on ONE 8-wave workgroup per CU (single tile); 16 waves: the r6 A/B build (CC_V_NW16)");
+  static_assert(!ONE || NW == 4 || (NW == 8 && NT == 1),
+                "the single-launch step runs on 4-wave workgroups, or on ONE 8-wave workgroup per CU (single tile)");
   constexpr int D = 128, VEC = 8, RPW = 4, U = 4;
-  static_assert(!QKV || (ONE && NT == 1 && !HYB && QB == 0 && !L2 && !FULL && (NW == 4 || NW == 8) && CC_V_LDSDMA != 0 && CC_V_WORDSFIRST != 0),
+  static_assert(!QKV || (ONE && NT == 1 && !HYB && QB == 0 && !L2 && !FULL && (NW == 4 || NW == 8)),
                 "the fused projection rides the lean single-tile step of the plain 16-bit caches");
   static_assert(FULL || ONE, "the lean form exists for the single-launch step only");
   static_assert(!XL2 || ONE, "the L2-resident hand-off belongs to the single-launch steps");
@@ -1133,13 +928,11 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
   __shared__ __attribute__((aligned(16))) uint4 sm_k[NW][16][16];  // [wave][tile row i][slot]: 4 KiB per wave
   __shared__ __attribute__((aligned(16))) uint4 sm_v[NW][16][16];  // [wave][tile row][chunk ^ 2*(row & 7)]: V tile, row major
   __shared__ float sm_wm[NW][RT], sm_wl[NW][RT];  // the waves' softmax state per query head (merged across the workgroup)
-  __shared__ float sm_wf[NW][RT];                 // EML: the waves' merge factors exp(m_w - M) per query head (CC_V_WFACT)
   __shared__ unsigned sm_mlcnt;                    // EML: waves whose (m, l) rows are in LDS — the LAST one to arrive publishes
   __shared__ unsigned sm_fail;                     // EML: some wave of this workgroup gave up waiting (recoverable hand-off)
   __shared__ __attribute__((aligned(16))) float sm_l2w[NW];  // ONE + L2: per-wave maxima of the norms this workgroup's slots hold AFTER the step's insert
   __shared__ __attribute__((aligned(16))) T sm_l2sc[L2 ? NW : 1][L2 ? 128 : 8];  // l2: the new key, transposed for its norm (the slabs belong to the DMA loads)
   __shared__ float sm_gmax;     // L2X: the norm maximum over all kv heads (NaN propagates)
-  __shared__ __attribute__((aligned(16))) T sm_l2c4[L2C ? 4 : 1][L2C ? 128 : 8];  // L2C: four new keys, transposed for their norms (one per row group of the workgroup's last wave)
   // QKV: the projection's partial sums [K quarter][row of this workgroup's share], the RMSNorm partials, and the head's gathered
   // q (RT heads), k_new, v_new
   constexpr int QNU = (RT + 2) * 32;  // granule units (4 projection rows each) per kv head
@@ -1179,17 +972,8 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
     // needs ALL workgroups of the launch resident (the launcher checks the capacity).  Should the relation ever not hold for a
     // launch (grids of two queues dealt alternately, say), a head's workgroups do not see each other's granules: the bounded wait
     // ends the step as a recoverable failure and the host falls back to the memory hand-off (harness._recover_token).
-#if CC_V_PRELOAD
-    const int b = blockIdx.x;  // (a 1-D grid of n_split * H blocks: the head count comes preloaded)
-#if CC_V_FEWXCD
-    const int Hg = pl_misc < 0 ? 8 : lead_H;  // (bit 31: eight virtual heads)
-#else
-    const int Hg = lead_H;
-#endif
-#else
     const int b = blockIdx.x + gridDim.x * blockIdx.y;
     const int Hg = (int)gridDim.y;
-#endif
     if ((Hg & (Hg - 1)) == 0) {  // (the usual case: no integer division in front of the first loads)
       h_ = b & (Hg - 1);
       split_ = b >> __builtin_ctz(Hg);
@@ -1197,16 +981,13 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
       h_ = b % Hg;
       split_ = b / Hg;
     }
-#if CC_V_FEWXCD
-    if (h_ >= lead_H) return;  // a virtual head: nothing to do (before any barrier, any load)
-#endif
   }
   const int split = split_, h = h_;
   const int S = a.S;
   const int row_begin = split * a.rows_per_split;
   const int row_end = min(S, row_begin + a.rows_per_split);
   const T* kb = reinterpret_cast<const T*>(a.k) + (size_t)h * S * D;
-  // what hangs on the argument block's later fields (LATE: worked out again behind phase 1)
+  // what hangs on the argument block
   int q0 = 0;
   const T* vh = nullptr;
   const uint8_t *kqb = nullptr, *vqh = nullptr;  // QB: byte images (a row is QRB bytes, a lane's 8-value chunk QCB) ...
@@ -1225,7 +1006,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
     mh = has_mask ? a.mask + (size_t)h * S : reinterpret_cast<const uint8_t*>(a.k);
     sc_out = reinterpret_cast<T*>(a.scores);
   };
-  if constexpr (!LATE) derive();
+  derive();
 
   float m = -INFINITY, l = 0.f;  // softmax state of (wave, query head c) / (row group g, head c); meaningful for c < RT
   // O^T accumulators of the P.V MFMAs: block b covers output columns 16b .. 16b+15; lane (g, n = c) holds
@@ -1249,7 +1030,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
   int ins_idx = -1, ins_was_empty = 0;
   int hyb_kind = 0, hyb_cts = 0;  // HYB: 0 = append at the end, 1 = evict the candidate, 2 = drop (slot S - 1, mask untouched)
   bool hyb_punc = false;
-  bool key_pending = a.next_key != nullptr && (LATE || !(a.abl & 128));  // (LATE: the measurement bit is looked at behind phase 1)
+  bool key_pending = a.next_key != nullptr && !(a.abl & 128);
   unsigned long long key_part = ~0ull;
   unsigned long long key_more[3] = {~0ull, ~0ull, ~0ull};  // up to 256 entries are requested at once and folded when first used
   // (late r2, measured on one box against the same build without it: these loads and the fold below cost the step 0.35 us — every
@@ -1288,12 +1069,12 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
       }
     }
   };
-  constexpr bool KFIRST = CC_V_PRO != 0 && ONE1 && !HYB;  // the K rows go out ahead of the (branchy) mask word
+  constexpr bool KFIRST = ONE1 && !HYB;  // the K rows go out ahead of the (branchy) mask word
   // LDS-DMA (r4 A/B): the tile's rows land in the wave's slabs directly — load u of a wave delivers tile rows 4u .. 4u + 3 (lane
   // (g, c) asks for row 4u + g, the chunk that belongs in slot c of that row under the slab's swizzle) into one contiguous 1 KiB
   // block (lane L -> byte 16 L); no staging registers, no ds_write, and the row OWNERSHIP of the scores (row group g: rows 4g .. 4g + 3,
   // the MFMA's C layout) is untouched
-  constexpr bool DMA = CC_V_LDSDMA != 0 && ONE1 && QB == 0 && !HYB;
+  constexpr bool DMA = ONE1 && QB == 0 && !HYB;
   // (buffer_load ... lds, not global_load_lds: the compiler's wait-count pass treats the FLAT-encoded form as an access to both
   //  memories and turns every later wait into vmcnt(0) lgkmcnt(0) while one is pending; the MUBUF form is counted exactly)
   auto dma16 = [](__amdgpu_buffer_rsrc_t rs, int voff, void* lp) {
@@ -1315,102 +1096,16 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
       dma16(vrs, rr * (D * (int)sizeof(T)) + ((c ^ (2 * (i & 7))) & 15) * 16, &sm_v[wave][4 * u][0]);
     }
   };
-  unsigned long long tr_kreq = 0;
-  // LATE, phase 1: the rest of the argument block through a laundered pointer — the loads cannot be issued ahead of the asm that
-  // "produces" it, i.e. ahead of the K request in front of it — then the preloaded copies and the constants again
-  auto late_phase = [&]() {
-    if constexpr (LATE) {
-      typedef const char __attribute__((address_space(4))) kernarg_bytes;
-      kernarg_bytes* kp = (kernarg_bytes*)__builtin_amdgcn_kernarg_segment_ptr();
-      asm volatile("" : "+s"(kp));
-      static_assert(kLeadBytes % alignof(SplitArgs) == 0, "the argument block follows the 14 preloaded dwords without padding");
-      // member by member THROUGH the constant address space (a memcpy through a generic pointer becomes vector loads behind the
-      // DMA request — the compiler must assume it wrote what they read — with in-order waits for the K rows in front of them);
-      // the hybrid / QKV sub-blocks and the two-launch scratch are not this instantiation's
-#if CC_V_PRELOAD
-      if constexpr (EARLY) {
-        // the loads of the kernel's first instructions: ONE wait, here — they have been in flight for the whole prologue
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(ea_q), "+s"(ea_kn), "+s"(ea_ct), "+s"(ea_ao), "+s"(ea_r), "+s"(ea_rn), "+s"(ea_hp), "+s"(ea_y),
-                     "+s"(ea_nrm), "+s"(ea_tr), "+s"(ea_abl));
-        auto p64 = [](unsigned lo, unsigned hi) { return (unsigned long long)lo | ((unsigned long long)hi << 32); };
-        // (pointers rebuilt from integers must be told that they point to GLOBAL memory — kernel arguments are by the ABI — or every
-        //  access through them becomes a FLAT instruction, counted in vmcnt AND lgkmcnt: the in-order waits all turn into (0, 0))
-        typedef __attribute__((address_space(1))) char gchar;
-#define CC_GPTR(T, lo, hi) reinterpret_cast<T>((char*)(gchar*)p64(lo, hi))
-        a.q = CC_GPTR(const void*, ea_q[0], ea_q[1]);
-        a.v = CC_GPTR(const void*, ea_q[4], ea_q[5]);
-        a.mask = CC_GPTR(const uint8_t*, ea_q[6], ea_q[7]);
-        a.R = (int)ea_r[0];
-        a.n_split = (int)ea_r[1];
-        a.scale = __uint_as_float(ea_r[3]);
-        a.abl = (int)ea_abl;
-        a.k_new = CC_GPTR(const void*, ea_kn[0], ea_kn[1]);
-        a.v_new = CC_GPTR(const void*, ea_kn[2], ea_kn[3]);
-        a.pos = CC_GPTR(int32_t*, ea_kn[4], ea_kn[5]);
-        a.mask_w = CC_GPTR(uint8_t*, ea_kn[6], ea_kn[7]);
-        a.cache_cts = CC_GPTR(int32_t*, ea_ct[0], ea_ct[1]);
-        a.num = CC_GPTR(double*, ea_ct[2], ea_ct[3]);
-        a.denom = CC_GPTR(int32_t*, ea_ct[4], ea_ct[5]);
-        a.H = (int)ea_ct[6];
-        a.Hc = (int)ea_ct[7];
-        a.Hp = (int)ea_hp[0];
-        a.key_norm = CC_GPTR(void*, ea_nrm[0], ea_nrm[1]);
-        // (the granule regions sit at fixed offsets behind the workspace's header: no loads)
-        a.one_ml = reinterpret_cast<char*>(a.one_hdr) + kOneHdrBytes;
-        a.one_o = reinterpret_cast<char*>(a.one_hdr) + kOneHdrBytes + kOneMlCap;
-        a.one_ml_bytes = (unsigned)kOneMlCap;
-        a.one_o_bytes = (unsigned)kOneOCap;
-        a.y = CC_GPTR(void*, ea_y[0], ea_y[1]);
-        a.attn_out = CC_GPTR(void*, ea_ao[0], ea_ao[1]);
-        a.hh_counter = CC_GPTR(int64_t*, ea_ao[2], ea_ao[3]);
-        a.g = (int)ea_ao[4];
-        a.w = (int)ea_ao[5];
-        a.policy = (int)ea_ao[6];
-        a.rand_next = CC_GPTR(const float*, ea_rn[0], ea_rn[1]);
-        a.rng_seed = p64(ea_rn[2], ea_rn[3]);
-        a.trace = CC_GPTR(unsigned long long*, ea_tr[0], ea_tr[1]);
-        apply_lead();
-        apply_consts();
-        derive();
-        if (a.abl & 128) key_pending = false;
-#undef CC_GPTR
-        return;
-      }
-#endif
-      typedef const SplitArgs __attribute__((address_space(4))) args_c;
-      args_c* ap = (args_c*)(kp + kLeadBytes);
-#define CC_LATE_FIELD(f) a.f = ap->f
-      CC_LATE_FIELD(q); CC_LATE_FIELD(v); CC_LATE_FIELD(mask); CC_LATE_FIELD(R); CC_LATE_FIELD(n_split); CC_LATE_FIELD(scale);
-      CC_LATE_FIELD(abl); CC_LATE_FIELD(k_new); CC_LATE_FIELD(v_new); CC_LATE_FIELD(pos); CC_LATE_FIELD(mask_w); CC_LATE_FIELD(cache_cts);
-      CC_LATE_FIELD(num); CC_LATE_FIELD(denom); CC_LATE_FIELD(H); CC_LATE_FIELD(Hc); CC_LATE_FIELD(Hp); CC_LATE_FIELD(key_norm);
-      CC_LATE_FIELD(one_ml); CC_LATE_FIELD(one_o); CC_LATE_FIELD(one_ml_bytes); CC_LATE_FIELD(one_o_bytes); CC_LATE_FIELD(y);
-      CC_LATE_FIELD(attn_out); CC_LATE_FIELD(hh_counter); CC_LATE_FIELD(g); CC_LATE_FIELD(w); CC_LATE_FIELD(policy); CC_LATE_FIELD(rand_next);
-      CC_LATE_FIELD(rng_seed); CC_LATE_FIELD(trace); CC_LATE_FIELD(virt8);
-#undef CC_LATE_FIELD
-      apply_lead();
-      apply_consts();
-      derive();
-      if (a.abl & 128) key_pending = false;  // (measurement: the key row was read, and is ignored)
-    }
-  };
   auto issue_k = [&](TileRegs& R, int base) {  // mask word + the four K rows of this lane's row group (tile row i = 4g + u takes chunk c ^ i)
     const int row0 = base + g * U;
     if constexpr (DMA) {
       issue_k_dma(base);
       __builtin_amdgcn_sched_barrier(0);
-      if constexpr (LATE && FULL) tr_kreq = __builtin_amdgcn_s_memtime();  // (the trace's "K requested": the block's trace pointer arrives with phase 1, behind it)
-      if constexpr (LATE && !SMALLFIRST) late_phase();  // (single tile: this is the step's one K request)
     } else
     if constexpr (KFIRST) {
       issue_k_rows(R, base);
       __builtin_amdgcn_sched_barrier(0);
     }
-    if constexpr (DMA && CC_V_FLATLOADS != 0) {
-      // one aligned word per lane, no branch: a lane whose four rows are not one aligned word inside the cache (a ragged end, an odd
-      // base) reads the first word of the K cache instead and takes the bytes one by one where the word is consumed (mword_fixup)
-      const bool okw = has_mask && row0 + 3 < S && ((reinterpret_cast<uintptr_t>(mh) + (size_t)row0) & 3) == 0;
-      R.mword = *reinterpret_cast<const uint32_t*>(okw ? mh + row0 : reinterpret_cast<const uint8_t*>(a.k));
-    } else {
     R.mword = 0x01010101u;
     if (has_mask) {
       if (row0 + 3 < S && ((reinterpret_cast<uintptr_t>(mh) + (size_t)row0) & 3) == 0) {
@@ -1421,7 +1116,6 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
         for (int u = 0; u < U; u++)
           if (row0 + u < S) R.mword |= (uint32_t)mh[row0 + u] << (8 * u);
       }
-    }
     }
     if constexpr (!KFIRST && !DMA) issue_k_rows(R, base);
   };
@@ -1450,40 +1144,17 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
   // unchanged).  The neighbours of this placement all LOSE: K ahead of the key row +0.1 (every workgroup's first decision then
   // queues behind 16 MB of rows), K and V both here +0.2, q moved up with K +0.1 (+0.5 at one kv head), the per-slot state moved
   // behind V +0.45.
-#ifdef CC_NO_KEARLY  // (A/B builds)
-  constexpr bool KEARLY = false;
-#else
   // (several tiles per wave — hybrid included: the first tile's K rows likewise; C4 hybrid at S = 18432 25.8 -> 25.1 us and
   //  17.15 -> 16.7 at S = 9000 on two boxes, unchanged on a third; heavy hitter unchanged: its stream is bandwidth-bound.  NOT the
   //  hybrid cache's single-tile step: 11.1 -> 11.6 us at S = 4096 with it — its decision operands want to be ahead of the rows)
-  constexpr bool KEARLY = ONE && QB == 0 && !(HYB && NT == 1) && !SMALLFIRST;
-#endif
+  constexpr bool KEARLY = ONE && QB == 0 && !(HYB && NT == 1);
   unsigned one_tag = 0;
   int32_t one_pin = 0;
   unsigned rc_status = 0;    // EML: the workspace's status word (a step failed since the host last looked: do nothing)
   int32_t rc_commit = -2;    // EML: step_commit[h][2 + split]: the last position this workgroup committed
   int32_t rc_insw = 0, rc_insp = -2;  // EML: step_commit[h][0 .. 1]: the insert slot word of position rc_insp
   int32_t rc_cts = 0, rc_col = 0;     // hybrid: step_commit[h][66 .. 67]: the head's count before that step, its ring column
-  // VW (r6, with the preloaded arguments): in the LDS-DMA steps the words travel as VECTOR loads of a wave-uniform address (an
-  // opaque zero in a VGPR keeps the compiler from turning them back into scalar loads), the first loads the wave issues.  As scalar
-  // loads they shared lgkmcnt with the argument block's own loads: one register reused between the two kinds and the compiler put an
-  // `s_waitcnt lgkmcnt(0)` — a cold round trip to memory — in front of the key row and the first K request.  Vector loads return in
-  // order: the wait where the words are first consumed (words_to_sgpr, behind the issue of the whole tile) is an exact vmcnt(N).
-  constexpr bool VW = CC_V_PRELOAD != 0 && DMA;
   auto load_step_words = [&]() {
-    if constexpr (VW) {
-      int vz;
-      asm volatile("v_mov_b32 %0, 0" : "=v"(vz));
-      one_tag = a.one_hdr[h + vz];
-      one_pin = a.input_pos[vz];
-      rc_status = a.one_hdr[kOneStatusWordDev + vz];
-      // (no branch around the loads: without commit words a valid dummy — the header — is read and ignored)
-      const int32_t* cw = a.commit ? a.commit + (size_t)h * kRcStride : reinterpret_cast<const int32_t*>(a.one_hdr);
-      rc_commit = cw[2 + split + vz];
-      rc_insw = cw[vz];
-      rc_insp = cw[1 + vz];
-      return;
-    }
     one_tag = a.one_hdr[h] + 1u;
     one_pin = *a.input_pos;
     if constexpr (RC || NRC) {
@@ -1499,18 +1170,6 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
       }
     }
   };
-  auto words_to_sgpr = [&]() {  // VW: the words are back (the compiler's wait sits right here) — wave-uniform values again
-    if constexpr (VW) {
-      one_tag = (unsigned)__builtin_amdgcn_readfirstlane((int)one_tag) + 1u;
-      one_pin = __builtin_amdgcn_readfirstlane(one_pin);
-      rc_status = (RC || NRC) ? (unsigned)__builtin_amdgcn_readfirstlane((int)rc_status) : 0u;
-      const bool have = (RC || NRC) && a.commit != nullptr;
-      rc_commit = have ? __builtin_amdgcn_readfirstlane(rc_commit) : -2;
-      rc_insw = have ? __builtin_amdgcn_readfirstlane(rc_insw) : 0;
-      rc_insp = have ? __builtin_amdgcn_readfirstlane(rc_insp) : -2;
-    }
-  };
-#if CC_V_WORDSFIRST
   if constexpr (DMA) {
     // the step's wave-uniform words are requested AHEAD of the first DMA load: behind it they could no longer travel as scalar
     // loads (the compiler must assume the DMA writes memory they read) and would become vector loads with a wait for the whole tile.
@@ -1519,15 +1178,12 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
     // (r4) they made the K request wait a memory round trip for the commit words (found with a time stamp at the kernel's entry).
     load_step_words();
     __builtin_amdgcn_sched_barrier(0);
-#if CC_V_KPIN && !CC_V_PRELOAD
     // ... and behind them the kernel arguments the key row, the first K / V rows, q, the mask and the per-slot state need, in ONE
     // round of scalar loads (left to the compiler they arrive in three, each behind the previous one's wait).  Only here: behind a
     // volatile asm the compiler reads nothing from memory through scalar loads any more — the step's words are already on their way.
     asm volatile("" ::"s"(a.next_key), "s"(a.nk), "s"(a.nk_read), "s"(a.k), "s"(a.v), "s"(a.q), "s"(a.mask), "s"(a.S), "s"(a.n_split),
                  "s"(a.rows_per_split), "s"(a.num), "s"(a.denom), "s"(a.pos), "s"(a.Hp));
-#endif
   }
-#endif
   if (key_pending) {
     // KEY ROWS (late r3).  Every kv head reads — and at the end of the step rewrites — ITS OWN row, also under the head-constant
     // policies, whose rows all hold the same keys.  They used to share row 0, rewritten by kv head 0's waves once THEIR head's
@@ -1537,7 +1193,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
     // and put their row into the wrong slot, silently.  A head's own row is safe by the argument that already covers the
     // head-specific policies: its writers have gathered every workgroup of the head, i.e. every reader has published, i.e. read.
     const unsigned long long* krow = a.next_key + (size_t)h * a.nk;
-    if constexpr (CC_V_PRO != 0 && ONE) {
+    if constexpr (ONE) {
       // no branch around the loads: a lane past the row's live entries reads the row's last live entry again (the minimum does not
       // change); four exec-mask branches less in front of the first K rows
       const int last = a.nk_read - 1;
@@ -1557,12 +1213,6 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
       key_part = x < key_part ? x : key_part;
     }
   }
-#if !CC_V_WORDSFIRST
-  if constexpr (DMA) {
-    load_step_words();
-    __builtin_amdgcn_sched_barrier(0);
-  }
-#endif
   // ---- QKV: the projection's operands — the input vector, then round 0 of this wave's weight rows — go out HERE, ahead of the
   //      tile (the tile is not needed before q exists; the weights are on the path to q)
   const int q_w4 = wave & 3, q_hw = wave >> 2;  // K quarter of this wave / wave half (8-wave workgroups: two halves share the rows)
@@ -1573,8 +1223,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
   // load, 4 us later; every wave reading the whole vector instead — 18 loads per lane in front of the weights — delayed the first
   // weight request by 1 us)
   Vec16<T> q_xa[QXS], q_da[QXS], q_nv[QXS];
-  constexpr int QDEPTH = CC_QKV_DEPTH;
-  static_assert(QDEPTH == 2 || QDEPTH == 3, "two or three weight units in flight");
+  constexpr int QDEPTH = 2;
   uint4 q_w[QDEPTH][4][QXS];  // QDEPTH units (4 rows x QXS segments each) in flight per lane: see the rounds below
   uint32_t q_fr_raw = 0;  // the finishing lane's (cos, sin) pair and bias, raw (converted where used)
   uint16_t q_bi_raw = 0;
@@ -1625,27 +1274,12 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
       q_fr_raw = *fp;
       q_bi_raw = *bp;
     }
-    if constexpr (CC_QKV_TILE_AT == 0) {
-      issue_k(tregs[0], base);
-      issue_v(tregs[0], base);
-      __builtin_amdgcn_sched_barrier(0);
-    }
     if (q_nmine > 0) q_issue_w(IntC<0>{}, 0);
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (CC_QKV_TILE_AT == 1) {
-      issue_k(tregs[0], base);
-      issue_v(tregs[0], base);
-      __builtin_amdgcn_sched_barrier(0);
-    }
     qstamp(1);
   }
-  // SMALLFIRST: the rest of the argument block (requested at the kernel's first instruction) is taken HERE, behind the key row's
-  // requests; the per-slot state, q, the K rows, the mask word and the V rows follow in program order below
-  if constexpr (SMALLFIRST) late_phase();
-  constexpr bool VEARLY = DMA && !QKV && (CC_V_VEARLY == 2 || (CC_V_VEARLY == 1 && !XL2));
   if constexpr (KEARLY && !QKV) {  // (QKV: the tile is requested behind the projection's last weight rows, below)
     issue_k(tregs[0], base);
-    if constexpr (VEARLY) issue_v(tregs[0], base);
     __builtin_amdgcn_sched_barrier(0);  // (keeps the scheduler from sinking them back to the rest of the tile)
   }
   // (r4, with the DMA loads: the V rows right behind the K rows +0.4 us, the K rows ahead of the key row +0.35, both +0.8 — whatever
@@ -1681,7 +1315,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
   unsigned long long tr0 = 0, tr1 = 0, tr2 = 0, tr3 = 0, tr4 = 0, rt0 = 0, rt1 = 0, trA = 0, trB = 0, trC = 0;
   if constexpr (ONE) {
     if (a.trace) {
-      tr3 = (LATE && FULL) ? tr_kreq : __builtin_amdgcn_s_memtime();  // the first K rows (and the key row, the step words) are requested
+      tr3 = __builtin_amdgcn_s_memtime();  // the first K rows (and the key row, the step words) are requested
       tr0 = tr_entry;
       rt0 = rt_entry;
     }
@@ -1690,7 +1324,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
   // dependent instructions — runs on ALL 64 lanes (lane L takes the wave's slots j = L + 64 k, slot j = row (j & 15) of the wave's
   // tile (j >> 4)) instead of on the 16 score-holding lanes of one tile after the other: ceil(NT / 4) passes instead of NT; the
   // group-mean probabilities reach it through a wave-private LDS row, the per-slot state is requested per (lane, k) — coalesced
-  constexpr bool ALL = CC_V_ALLLANES != 0 && ONE && NT > 1 && !HYB;
+  constexpr bool ALL = ONE && NT > 1 && !HYB;
   constexpr int SN = ALL ? (NT * RPW * U + 63) / 64 : NT;  // per-slot state entries per lane
   double one_numv[SN];
   int32_t one_denv[SN], one_psv[SN];
@@ -1725,13 +1359,6 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
 #pragma unroll
     for (int ti = 0; ti < SN; ti++) {
       const int sl = ALL ? all_slot(ti) : one_slot + ti * (NW * RPW * U);
-      if constexpr (DMA && CC_V_FLATLOADS != 0) {  // every lane, no branch: a lane without a slot reads the split's first (valid, ignored)
-        const int slc = (one_lane && sl < row_end) ? sl : row_begin;
-        one_numv[ti] = nump[((size_t)h * S + slc) * hist];
-        one_denv[ti] = denp[((size_t)h * S + slc) * hist];
-        one_psv[ti] = a.pos[(a.Hp == 1 ? 0 : (size_t)h * S) + slc];
-        if (a.policy == 3 && a.rand_next) one_rndv[ti] = a.rand_next[slc];
-      } else
       if (ALL ? all_valid(ti) : (one_lane && sl < row_end)) {
         one_numv[ti] = nump[((size_t)h * S + sl) * hist];
         one_denv[ti] = denp[((size_t)h * S + sl) * hist];
@@ -1809,7 +1436,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
     // single tile: requested AHEAD of the K/V tile (measured: behind it the step is 0.3 us slower — the tile's in-order waits
     // then end on these stragglers, and the workgroup leaves the streaming part later); several tiles: requested after the
     // publish, in the shadow of the hand-off
-    if constexpr (NT == 1 && !HYB && !L2C) {  // (L2C: the workgroup's last wave reads the state of ALL its slots, between the K and the V rows)
+    if constexpr (NT == 1 && !HYB) {
       load_slot_state();
       if constexpr (L2)  // (unconditional: lanes without a slot read a valid neighbour and ignore it)
         one_kn_raw = reinterpret_cast<const uint16_t*>(a.key_norm)[(size_t)h * S + (one_have ? one_slot : row_begin)];
@@ -1836,7 +1463,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
   int32_t p_ins = 0;
   qb_kn.raw = make_uint4(0, 0, 0, 0);
   qb_vn.raw = make_uint4(0, 0, 0, 0);
-  if (AHEAD && ((DMA && CC_V_FLATLOADS != 0) || a.k_new)) {  // (the single-launch steps always carry the new rows: no branch around the loads)
+  if (AHEAD && a.k_new) {
     qb_kn.load(reinterpret_cast<const T*>(a.k_new) + (size_t)h * D + c * VEC);
     qb_vn.load(reinterpret_cast<const T*>(a.v_new) + (size_t)h * D + c * VEC);
     p_ins = *a.input_pos;
@@ -1845,7 +1472,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
   if constexpr (L2X) {
     hm_ep = a.one_hdr[lane < a.H ? lane : 0];  // (ahead of the tile and of anything this workgroup publishes, like l2_ep below)
   } else
-  if constexpr (L2 && EML && !L2C) {
+  if constexpr (L2 && EML) {
     // the epoch words of the kv heads whose norm granules this thread gathers — AHEAD of the tile here: this workgroup's first
     // publish (its (m, l) pairs and norm maximum, right behind the scores) must not happen before these loads have completed
     // (no head's word is bumped before every workgroup of the launch has published), and behind the tile they would make that
@@ -1866,42 +1493,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
   for (int j = 0; j < 4; j++) {
     qB[j].raw = make_uint4(0, 0, 0, 0);
     if constexpr (!QKV) {
-      if constexpr (DMA && CC_V_FLATLOADS != 0) {  // every lane, no branch: columns n >= RT aim past the buffer's end (no request, zeros back)
-        const auto q_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.q), 0, (q0 + RT) * D * (int)sizeof(T), 0x00020000);
-        const u32x4_t qv = __builtin_amdgcn_raw_buffer_load_b128(q_rsrc, c < RT ? ((q0 + c) * D + (4 * j + g) * VEC) * (int)sizeof(T) : 0x7ffffff0, 0, 0);
-        qB[j].raw = make_uint4(qv[0], qv[1], qv[2], qv[3]);
-      } else
       if (c < RT) qB[j].load(reinterpret_cast<const T*>(a.q) + (size_t)(q0 + c) * D + (4 * j + g) * VEC);
-    }
-  }
-  // L2C: what the workgroup's last wave needs for the policy's per-slot pass — see L2C above.  A wave-uniform branch around loads:
-  // harmless HERE (between the K and the V rows), where the only older loads anybody waits for are the K tile and the small ones in
-  // front of it — an in-order wait that does not count these loads merely lets a few of the small ones land first.
-  constexpr int L2S = L2C ? NW / 4 : 1;  // slots per lane: the workgroup holds NW * 16
-  uint4 l2c_kn[2];
-  ulonglong2 l2c_rc = make_ulonglong2(0ull, 0ull);
-  int32_t l2c_ps[L2S];
-  uint16_t l2c_nr[L2S];
-  l2c_kn[0] = l2c_kn[1] = make_uint4(0, 0, 0, 0);
-#pragma unroll
-  for (int k = 0; k < L2S; k++) {
-    l2c_ps[k] = 0;
-    l2c_nr[k] = 0;
-  }
-  if constexpr (L2C) {
-    if (wave == NW - 1) {
-#pragma unroll
-      for (int j = 0; j < 2; j++) {  // heads 4 j + row group (heads past the count re-read this head's: valid, ignored)
-        const int hj = 4 * j + g < a.H ? 4 * j + g : h;
-        l2c_kn[j] = *reinterpret_cast<const uint4*>(reinterpret_cast<const T*>(a.k_new) + (size_t)hj * D + c * VEC);
-      }
-      l2c_rc = *reinterpret_cast<const ulonglong2*>(a.next_key + (size_t)(lane < a.H ? lane : h) * a.nk + (a.nk - kNextKeyTail));  // lane = kv head
-#pragma unroll
-      for (int k = 0; k < L2S; k++) {
-        const int sl = row_begin + k * 64 + lane < row_end ? row_begin + k * 64 + lane : row_end - 1;
-        l2c_ps[k] = a.pos[(size_t)h * S + sl];
-        l2c_nr[k] = reinterpret_cast<const uint16_t*>(a.key_norm)[(size_t)h * S + sl];
-      }
     }
   }
   // UNCONDITIONAL (rows past the split's end are clamped to its last row, a valid address): behind a branch, the compiler's
@@ -1911,8 +1503,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
   for (int sub = 0; sub < NSUB; sub++) {
     if constexpr (!KEARLY) issue_k(tregs[sub], base + sub * NW * RPW * U);
     if constexpr (QB) __builtin_amdgcn_sched_barrier(0);  // K's bytes and parameters go out BEFORE V's: the K stash waits for them only
-    if constexpr (DMA && CC_V_VDELAY != 0) __builtin_amdgcn_s_sleep(CC_V_VDELAY);
-    if constexpr (!QKV && !VEARLY) issue_v(tregs[sub], base + sub * NW * RPW * U);
+    if constexpr (!QKV) issue_v(tregs[sub], base + sub * NW * RPW * U);
     if constexpr (QB) __builtin_amdgcn_sched_barrier(0);
   }
   // ONE + L2: the epoch words of the kv heads whose norm granules this thread will gather.  Read HERE (behind the tile's loads: three integer divisions kept out of the way of the first K rows): every workgroup has read
@@ -1926,7 +1517,6 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
     }
   }
   if constexpr (QKV) {
-    words_to_sgpr();
     if (rc_status != 0u) return;  // a step of this token failed before this launch: leave everything as it is (the host retries)
     // ================= the projection (cc_gemv.hip's gemv_kernel<T, false, RB, 2, 2>, operation for operation) =================
     // Four waves split K into quarters exactly like the stand-alone GEMV's workgroup (wave w: the 1 KiB segments w and w + 4 of a row,
@@ -1980,9 +1570,6 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
       }
     }
     if (q_nmine > 1) q_issue_w(IntC<1>{}, 1);  // (the second unit: behind the barrier — in front of it, only 14 requests per lane are out)
-    if constexpr (QDEPTH == 3) {
-      if (q_nmine > 2) q_issue_w(IntC<2>{}, 2);
-    }
     __builtin_amdgcn_sched_barrier(0);
     qstamp(3);
     // rounds: unit ul of this half is consumed from buffer ul & 1 while unit ul + 1 is in flight; unit ul + 2 is requested into the
@@ -2013,11 +1600,9 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
       }
       q_slot = q_slot + 1 == QDEPTH ? 0 : q_slot + 1;
     }
-    if constexpr (CC_QKV_TILE_AT == 2) {
-      issue_k(tregs[0], base);
-      issue_v(tregs[0], base);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    issue_k(tregs[0], base);
+    issue_v(tregs[0], base);
+    __builtin_amdgcn_sched_barrier(0);
     for (; q_ul < q_nmine; q_ul++) {
       if (q_slot == 0) q_consume(IntC<0>{}, q_ul);
       else if (q_slot == 1) q_consume(IntC<1>{}, q_ul);
@@ -2093,11 +1678,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
     } else {
       __syncthreads();
     }
-    if constexpr (!VW) {
-      if (rc_status != 0u) return;  // a step of this token failed before this launch: leave everything as it is (the host retries)
-    }
-    // (VW: the words are vector loads, the oldest in flight — the test sits in front of the wave's first tile half, below, so that
-    //  the gather arithmetic in between still runs in the shadow of the K rows)
+    if (rc_status != 0u) return;  // a step of this token failed before this launch: leave everything as it is (the host retries)
   }
   if constexpr (NRC) {
     // (HERE, behind the issue of the first tile's loads — at the top of the kernel the test waited for the step words, a cold
@@ -2105,7 +1686,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
     if (a.commit && rc_status != 0u) return;
   }
   bool rc_replay = false;  // this WORKGROUP committed its part of this position's step already: it recomputes and stores nothing
-  if constexpr (!(VW && !QKV)) rc_replay = (EML || (NRC && a.commit != nullptr)) && rc_commit == one_pin;
+  rc_replay = (EML || (NRC && a.commit != nullptr)) && rc_commit == one_pin;
   // ONE: what this thread gathers in the hand-off — up to NOG partial-O granules of the output pairs this workgroup finishes (pair
   // P = r * 64 + d / 2).  Two integer divisions by run-time values (~100 scalar and vector instructions): worked out HERE, with the
   // tile in flight, and pinned — left where they are used, they sat between the merge barrier and the first look at the (m, l)
@@ -2266,18 +1847,6 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
             }
           }
         }
-      }
-    }
-    if constexpr (DMA && CC_V_FLATLOADS != 0) {  // mword_fixup: see issue_k
-      const bool okw = has_mask && row0 + 3 < S && ((reinterpret_cast<uintptr_t>(mh) + (size_t)row0) & 3) == 0;
-      if (!has_mask) {
-        R.mword = 0x01010101u;
-      } else if (__any(!okw)) {  // (wave-uniform; rare: the cache's ragged end or an unaligned mask)
-        uint32_t mw = 0;
-#pragma unroll
-        for (int u = 0; u < U; u++)
-          if (!okw && row0 + u < S) mw |= (uint32_t)mh[row0 + u] << (8 * u);
-        if (!okw) R.mword = mw;
       }
     }
     // fused insert (cache.py:356-362, 460-490, 754-763) — see the VALU kernel; the K chunk follows the swizzle
@@ -2512,128 +2081,13 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
     tile_pv(R, tbase_next, more_next);
   };
   // EML: the wave's (m, l) row goes to LDS; the LAST wave to arrive merges the workgroup's pairs and publishes them — behind the
-  // scores of the wave's only tile (NT == 1: ahead of its P.V products), or behind the wave's last tile (NT > 1)
-  // L2C: the policy's per-slot pass, by the workgroup's last wave alone (see L2C above).  Results: the workgroup's minimum key (into
-  // l2c_wk, stored with the commit) and its two granules (stored by the caller, unconditionally).
-  unsigned long long l2c_wk = ~0ull;
-  u32x4_t l2c_g1 = {0u, 0u, 0u, 0u}, l2c_g2 = {0u, 0u, 0u, 0u};
-  auto l2c_pass = [&]() {
-    // ---- the norms of the new keys, four kv heads per pass (row group g: head 4 j + g), the inserting row group's arithmetic
-    //      operation for operation.  The transposition through LDS is spelled in assembly with its own waits: a plain LDS access
-    //      behind pending LDS-DMA loads gets a wait for THOSE from the compiler (it cannot tell these rows from the slabs the V rows
-    //      are still landing in).
-    auto norm16 = [&](const uint4& kn) -> unsigned {
-      unsigned eb[8];
-      const unsigned wa = (unsigned)(uintptr_t)(__attribute__((address_space(3))) T*)&sm_l2c4[g][0];
-      const u32x4_t kr = {kn.x, kn.y, kn.z, kn.w};
-      asm volatile(
-          "ds_write_b128 %8, %9\n\t"
-          "s_waitcnt lgkmcnt(0)\n\t"
-          "ds_read_u16 %0, %10\n\t"
-          "ds_read_u16 %1, %10 offset:32\n\t"
-          "ds_read_u16 %2, %10 offset:64\n\t"
-          "ds_read_u16 %3, %10 offset:96\n\t"
-          "ds_read_u16 %4, %10 offset:128\n\t"
-          "ds_read_u16 %5, %10 offset:160\n\t"
-          "ds_read_u16 %6, %10 offset:192\n\t"
-          "ds_read_u16 %7, %10 offset:224\n\t"
-          "s_waitcnt lgkmcnt(0)"
-          : "=&v"(eb[0]), "=&v"(eb[1]), "=&v"(eb[2]), "=&v"(eb[3]), "=&v"(eb[4]), "=&v"(eb[5]), "=&v"(eb[6]), "=&v"(eb[7])
-          : "v"(wa + (unsigned)c * 16u), "v"(kr), "v"(wa + (unsigned)c * 2u)
-          : "memory");
-      float ss = 0.f;
-#pragma unroll
-      for (int i = 0; i < D / 16; i++) {
-        T et;
-        et.x = (uint16_t)eb[i];
-        const float e = ElemTraits<T>::load(&et, 0);
-        ss = __fadd_rn(ss, __fmul_rn(e, e));
-      }
-#pragma unroll
-      for (int off = 8; off > 0; off >>= 1) ss = __fadd_rn(ss, __shfl_xor(ss, off, 16));
-      T nt;
-      ElemTraits<T>::store(&nt, 0, cc_sqrt_rn(ss));
-      return (unsigned)nt.x;  // (every lane of the row group)
-    };
-    if (key_pending) {  // a last wave without rows (ragged last split) never entered its tile: the insert slot, as tile_qk derives it
-#pragma unroll
-      for (int j = 0; j < 3; j++) key_part = key_more[j] < key_part ? key_more[j] : key_part;
-      const unsigned long long key = wave_min_u64_uniform(key_part);
-      ins_idx = (key == ~0ull) ? -1 : (int)((key & 0xffffffffull) >> 1);
-      ins_was_empty = (int)(key & 1ull);
-      if (rc_insp == one_pin) {  // a retry: the slot the first attempt's insert went to
-        ins_idx = rc_insw >> 1;
-        ins_was_empty = rc_insw & 1;
-      }
-      key_pending = false;
-    }
-    // the record of position p - 1 of kv head `lane` (bits 0-15: the head's maximum over the slots it keeps at p)
-    const unsigned rec16 = (unsigned)((((one_pin + 1) & 1) ? l2c_rc.y : l2c_rc.x) & 0xffffull);
-    unsigned gmax16 = 0u, nv_own = 0u;
-    const int npass = (a.H + 3) >> 2;
-    for (int j = 0; j < npass; j++) {  // (wave-uniform trip count; the first two passes' keys were prefetched)
-      const int hj = 4 * j + g;
-      uint4 kn = j == 0 ? l2c_kn[0] : l2c_kn[1];
-      if (j >= 2) kn = *reinterpret_cast<const uint4*>(reinterpret_cast<const T*>(a.k_new) + (size_t)(hj < a.H ? hj : h) * D + c * VEC);
-      const unsigned nv = norm16(kn);
-      const unsigned rh = (unsigned)__shfl((int)rec16, hj < a.H ? hj : 0, CC_WAVE);
-      unsigned term = hj < a.H ? (nv > rh ? nv : rh) : 0u;  // max(record, new norm): patterns, unsigned order, NaN on top
-      gmax16 = term > gmax16 ? term : gmax16;
-      if (j == (h >> 2)) nv_own = (unsigned)__builtin_amdgcn_readlane((int)nv, (h & 3) << 4);  // this head's new norm (its row group's lanes all hold it)
-    }
-    gmax16 = (unsigned)wave_max_uniform((float)gmax16);  // (small integers: exact as floats)
-    T mt;
-    mt.x = (uint16_t)gmax16;
-    const float gm = ElemTraits<T>::load(&mt, 0);  // NaN propagates (torch.max)
-    T vt;
-    vt.x = (uint16_t)nv_own;
-    const float nv_own_f = ElemTraits<T>::load(&vt, 0);
-    // ---- the workgroup's slots: ref cache.py:597-605 dtype(max - norm), recent window -> +inf, base rules; and the two largest
-    //      norms AFTER this step's insert
-    const int32_t p_next = one_pin + 1;
-    unsigned long long kmin = ~0ull, k1 = 0ull;
-    unsigned t2 = 0u;
-#pragma unroll
-    for (int k = 0; k < L2S; k++) {
-      const int sl = row_begin + k * 64 + lane;
-      if (sl < row_end) {
-        const bool ins = sl == ins_idx;
-        const int32_t ps = ins ? one_pin : l2c_ps[k];
-        T et;
-        et.x = l2c_nr[k];
-        const float kn_eff = ins ? nv_own_f : ElemTraits<T>::load(&et, 0);
-        const unsigned kp = ins ? nv_own : (unsigned)l2c_nr[k];
-        float scn = ElemTraits<T>::rnd(gm - kn_eff);
-        if (ps >= p_next - a.w) scn = INFINITY;
-        if (sl < a.g) scn = INFINITY;
-        if (ps == -1) scn = -INFINITY;
-        const unsigned long long key = make_key(orderable_f32(scn), ((uint32_t)sl << 1) | (uint32_t)(ps == -1));
-        kmin = key < kmin ? key : kmin;
-        const unsigned long long nk64 = ((unsigned long long)kp << 32) | (unsigned)sl;
-        if (nk64 > k1) {
-          t2 = (unsigned)(k1 >> 32);
-          k1 = nk64;
-        } else if (kp > t2) {
-          t2 = kp;
-        }
-      }
-    }
-    l2c_wk = wave_min_u64_uniform(kmin);
-    const unsigned long long K1 = ~wave_min_u64_uniform(~k1);
-    const unsigned long long x2 = (k1 == K1) ? (unsigned long long)t2 : (k1 >> 32);
-    const unsigned T2w = (unsigned)~wave_min_u64_uniform(~x2);
-    l2c_g1 = u32x4_t{one_tag, (unsigned)(l2c_wk >> 32), one_tag, (unsigned)(l2c_wk & 0xffffffffull)};
-    l2c_g2 = u32x4_t{one_tag, (unsigned)(K1 >> 32) | (T2w << 16), one_tag, (unsigned)(K1 & 0xffffffffull)};
-  };
+  // scores of the wave's only tile (ahead of its P.V products)
   auto ml_block = [&]() {
       l = xor_combine<32, false>(xor_combine<16, false>(l));  // the wave's l of head c, in every row group
       if (lane < RT) {                                          // row group 0, column c = head
         sm_wm[wave][lane] = m;
         sm_wl[wave][lane] = l;
       }
-      if constexpr (L2C) {
-        // (nothing leaves with the pairs: the head's maximum comes from the record, see L2C)
-      } else
       if constexpr (L2) {  // the wave's maximum over the norms its slots hold AFTER this step's insert (decided above)
         float kv = -INFINITY;
         if (one_have) kv = (one_slot == ins_idx) ? l2_nv_lane : one_kn_f();
@@ -2672,7 +2126,6 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
 #pragma unroll
         for (int w = 0; w < NW; w++) {
           const float f = fast_exp(sm_wm[w][r] - Mu);
-          if constexpr (CC_V_WFACT != 0) sm_wf[w][r] = f;  // (read by the partial-O publish, behind the merge barrier)
           L = fmaf(sm_wl[w][r], f, L);
         }
         ml_M = M;
@@ -2687,8 +2140,6 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
         const auto ml_rsrc_e = __builtin_amdgcn_make_buffer_rsrc(a.one_ml, 0, (int)a.one_ml_bytes, 0x00020000);
         const int off = ml_last ? h * kOneMlHead + (split * RT + lane) * 16 : 0x7ffffff0;
         __builtin_amdgcn_raw_buffer_store_b128(mg, ml_rsrc_e, off, 0, XL2 ? 0 : kOneAuxCoherent);
-        if constexpr (L2C) {
-        } else
         if constexpr (L2) {  // l2: the workgroup's norm maximum leaves with the pairs (same unconditional form; lane RT of the publisher)
           float wm = -INFINITY;
           bool nn = false;
@@ -2730,28 +2181,12 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
       }
     };
     if (more) run_tiles(run_tiles, IntC<0>{});
-    if constexpr (EML) ml_block();  // (a wave without rows arrives with (-inf, 0))
   } else if constexpr (EML) {
     // single tile, early (m, l): scores -> [the workgroup's (m, l) pairs leave] -> P.V.  A wave without rows (ragged last split)
     // skips the tile halves but not the arrival counter: its pair is (-inf, 0).
-    if constexpr (VW && !QKV) {
-      __builtin_amdgcn_sched_barrier(0);  // (the scheduler otherwise hoists the first of these waits up to the barrier)
-      words_to_sgpr();
-      if (rc_status != 0u) return;  // a step of this token failed before this launch: leave everything as it is (the host retries)
-      rc_replay = rc_commit == one_pin;
-    }
     if (more) tile_qk(tregs[0], base, base, false, IntC<0>{});
     qstamp(8);
     ml_block();
-    if constexpr (L2C) {
-      // the policy's whole per-slot pass, by the workgroup's last wave, while its V rows land; its two granules leave HERE (stores
-      // unconditional: the other waves aim past the buffer's end, where the hardware drops the write)
-      if (wave == NW - 1) l2c_pass();
-      const auto nm_rsrc_e = __builtin_amdgcn_make_buffer_rsrc(a.one_ml, 0, (int)a.one_ml_bytes, 0x00020000);
-      const int goff = (wave == NW - 1 && lane == 0) ? kOneMaxHeads * kOneMlHead + h * kOneNmHead + split * 32 : 0x7ffffff0;
-      __builtin_amdgcn_raw_buffer_store_b128(l2c_g1, nm_rsrc_e, goff, 0, XL2 ? 0 : kOneAuxCoherent);
-      __builtin_amdgcn_raw_buffer_store_b128(l2c_g2, nm_rsrc_e, (wave == NW - 1 && lane == 0) ? goff + 16 : 0x7ffffff0, 0, XL2 ? 0 : kOneAuxCoherent);
-    }
     if (more) tile_pv(tregs[0], base, false);
     qstamp(9);
   } else {
@@ -2900,15 +2335,15 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
     const auto o_rsrc = __builtin_amdgcn_make_buffer_rsrc(a.one_o, 0, (int)a.one_o_bytes, 0x00020000);
     constexpr int MLN = (RT + NW - 1) / NW;            // (m, l) granules per thread: wave w collects heads w, w + NW, ...
     int ml_off[MLN];
-    // the waves that fold a head's (m, l) pairs: the first RT — or (MLW) the LAST RT of a workgroup with at least 2 RT waves: the first
+    // the waves that fold a head's (m, l) pairs: the first RT — or the LAST RT of a workgroup with at least 2 RT waves: the first
     // RT waves merge and publish the partial O meanwhile (thread t: outputs 2t, 2t + 1), the others would idle
-    constexpr int ML_W0 = (CC_V_MLW != 0 && EML && NW >= 2 * RT) ? NW - RT : 0;
+    constexpr int ML_W0 = (EML && NW >= 2 * RT) ? NW - RT : 0;
     const int ml_w = wave - ML_W0;  // this wave's first head (negative: none)
 #pragma unroll
     for (int k = 0; k < MLN; k++) ml_off[k] = h * kOneMlHead + ((lane < ns ? lane : 0) * RT + (ml_w >= 0 && ml_w + k * NW < RT ? ml_w + k * NW : 0)) * 16;
     u32x4_t mlq[MLN];
     const int nm_base = kOneMaxHeads * kOneMlHead;  // l2: the norm-maximum granules sit behind the (m, l) regions of all heads
-    constexpr int NLG = (L2 && !L2X && !L2C) ? 3 : 0;  // l2, one-level exchange: norm-maximum granules per thread (H * n_split <= 768 workgroups are ever co-resident)
+    constexpr int NLG = (L2 && !L2X) ? 3 : 0;  // l2, one-level exchange: norm-maximum granules per thread (H * n_split <= 768 workgroups are ever co-resident)
     int nm_off[NLG > 0 ? NLG : 1];
     bool nm_use[NLG > 0 ? NLG : 1];
     unsigned nm_tag[NLG > 0 ? NLG : 1];  // a granule of kv head h' carries h''s tag (its epoch word was read in the prologue: l2_ep)
@@ -2943,14 +2378,6 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
       {
         const int r = o2 / D, d = o2 - r * D;
         float M = 0.f, L = 0.f, O0 = 0.f, O1 = 0.f;
-        if constexpr (EML && CC_V_WFACT != 0) {
-#pragma unroll
-          for (int w = 0; w < NW; w++) {  // fixed order: deterministic (the factors: ml_block, the (m, l) merge)
-            const float f = sm_wf[w][r];
-            O0 = fmaf(sm_wacc(w, r, d), f, O0);
-            O1 = fmaf(sm_wacc(w, r, d + 1), f, O1);
-          }
-        } else {
         M = sm_wm[0][r];
 #pragma unroll
         for (int w = 1; w < NW; w++) M = fmaxf(M, sm_wm[w][r]);
@@ -2961,7 +2388,6 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
           L = fmaf(sm_wl[w][r], f, L);
           O0 = fmaf(sm_wacc(w, r, d), f, O0);
           O1 = fmaf(sm_wacc(w, r, d + 1), f, O1);
-        }
         }
         const u32x4_t og = {tag, __float_as_uint(O0), tag, __float_as_uint(O1)};
         __builtin_amdgcn_raw_buffer_store_b128(og, o_rsrc, h * kOneOHead + ((r * ns + split) * 64 + (d >> 1)) * 16, 0, kPublishAux);
@@ -3115,9 +2541,6 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
       else if (peer_failed && lane == 0) sm_fail = 1u;
       if (a.trace) tr4 = __builtin_amdgcn_s_memtime();
       if (ml_mine) final_ml();
-      if constexpr (L2C) {
-        // (the kv heads' terms sit in sm_l2m since the merge barrier: folded where the keys are scored, below)
-      } else
       if constexpr (L2) {  // the wave's fold of the gathered norm maxima (NaN propagates: torch.max)
         float gm = -INFINITY;
         bool gn = false;
@@ -3340,8 +2763,8 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
         }
       }
     };
-    if constexpr (!L2X && !L2C) {
-      if (!hrc_skip) all_tiles(all_tiles, IntC<0>{});  // (L2X: behind the partial-O gather — the heads' maxima arrive with it; L2C: done long ago by one wave)
+    if constexpr (!L2X) {
+      if (!hrc_skip) all_tiles(all_tiles, IntC<0>{});  // (L2X: behind the partial-O gather — the heads' maxima arrive with it)
     }
     if constexpr (ALL) {
       // ---- the second half of the per-slot pass on all lanes: the slot_pass branches above, operation for operation (heavy hitter:
@@ -3422,9 +2845,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
             old_e.x = hy_old[k];
             const float old_v = ElemTraits<T>::load(&old_e, 0);
             T* shadow = reinterpret_cast<T*>(a.ring_acc + hs * 4 + 2) + (size_t)one_rcol * hs;
-#ifndef CC_HYB_NO_RING_STORE  // (A/B builds: the price of the reference-layout column — one 2-byte store per slot, W * 2 bytes apart)
             ElemTraits<T>::store(reinterpret_cast<T*>(a.ring_num), i * (size_t)a.ring_W + one_rcol, av);
-#endif
             ElemTraits<T>::store(shadow, i, av);
             dn = hy_den[k] + late_one;
             a.denom[i] = dn;
@@ -3455,8 +2876,7 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
     // one key per WAVE (a head's key row has room for NW per 64-slot workgroup): nothing crosses the waves after the last
     // barrier of the finish, so no wave's stores wait for another wave (the launch ends a store round trip after the LAST
     // store is issued: every store that can go out early shortens it)
-    // (L2C: the workgroup's minimum in its last wave's entry, ~0 in the others': the row's minimum is all a reader takes)
-    unsigned long long wk = L2C ? l2c_wk : wave_min_u64_uniform(my_key);
+    unsigned long long wk = wave_min_u64_uniform(my_key);
     auto store_key = [&]() {
       if (lane == 0) {
         unsigned long long* nk_row = const_cast<unsigned long long*>(a.next_key) + (size_t)h * a.nk;
@@ -3476,20 +2896,9 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
       if constexpr (L2X) {
         if (hm_mine) hmq = __builtin_amdgcn_raw_buffer_load_b128(ml_rsrc, hm_off, 0, kOneAuxCoherent);
       }
-      // L2C, tail: the workgroups' two granules of this head (lane = split), gathered by the last wave of the head's split-0 workgroup
-      // with the partial-O round — the record of this position is resolved from them
-      const bool rec_mine = L2C && split == 0 && wave == NW - 1;
-      const int rec_off = nm_base + h * kOneNmHead + (lane < ns ? lane : 0) * 32;
-      u32x4_t recq = {0u, 0u, 0u, 0u}, recq2 = {0u, 0u, 0u, 0u};
-      auto ok_rec = [&]() { return !rec_mine || lane >= ns || (recq[0] == tag && recq[2] == tag && recq2[0] == tag && recq2[2] == tag); };
-      auto load_rec = [&]() {
-        recq = __builtin_amdgcn_raw_buffer_load_b128(ml_rsrc, rec_mine ? rec_off : 0x7ffffff0, 0, kGatherAux);
-        recq2 = __builtin_amdgcn_raw_buffer_load_b128(ml_rsrc, rec_mine ? rec_off + 16 : 0x7ffffff0, 0, kGatherAux);
-      };
-      if constexpr (L2C) load_rec();  // (unconditional: every other wave aims past the buffer's end — no request, zeros back)
       WaitBound o_wb;
       for (unsigned spins = 0;; spins++) {
-        if (__all(ok_o()) && __all(ok_hm()) && __all(ok_rec())) break;
+        if (__all(ok_o()) && __all(ok_hm())) break;
         if (RC && failq == tag) break;  // a workgroup of this head gave up: the head's step is not committed, nothing left to wait for
         if (o_wb.expired(spins)) {
           timed_out = true;
@@ -3500,26 +2909,6 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
         load_o();
         if constexpr (L2X) {
           if (hm_mine) hmq = __builtin_amdgcn_raw_buffer_load_b128(ml_rsrc, hm_off, 0, kOneAuxCoherent);
-        }
-        if constexpr (L2C) load_rec();
-      }
-      unsigned long long rec_new = 0ull;  // L2C: the head's record of this position (wave-uniform; meaningful in rec_mine's wave)
-      if constexpr (L2C) {
-        if (rec_mine) {
-          // the slot position p + 2 will evict: the arg-min of the keys this step scored (the minimum over the workgroups' minima)
-          const unsigned long long kq = lane < ns ? (((unsigned long long)recq[1] << 32) | recq[3]) : ~0ull;
-          const unsigned long long kmin = wave_min_u64_uniform(kq);
-          const int e_next = (kmin == ~0ull) ? -1 : (int)((kmin & 0xffffffffull) >> 1);
-          // the head's two largest norms, a holder of the largest — and the head's maximum over the slots it keeps
-          const unsigned a1 = lane < ns ? (recq2[1] & 0xffffu) : 0u, a2 = lane < ns ? (recq2[1] >> 16) : 0u, ai = lane < ns ? recq2[3] : 0u;
-          const unsigned long long k64 = ((unsigned long long)a1 << 32) | ai;
-          const unsigned long long K1 = ~wave_min_u64_uniform(~k64);
-          const unsigned long long win = __ballot(k64 == K1);                         // (slots are distinct across workgroups; lanes
-          const int wl = (int)__builtin_ctzll(win ? win : 1ull);                      //  without one tie at 0 only when every norm is +0)
-          const unsigned long long x2 = (lane == wl) ? (unsigned long long)a2 : (unsigned long long)a1;
-          const unsigned T2h = (unsigned)~wave_min_u64_uniform(~x2);
-          const unsigned T1h = (unsigned)(K1 >> 32), i1h = (unsigned)(K1 & 0xffffffffull);
-          rec_new = cc_l2_record((e_next >= 0 && i1h == (unsigned)e_next) ? T2h : T1h, T1h, i1h);
         }
       }
       if (a.trace) trE = __builtin_amdgcn_s_memtime();
@@ -3552,10 +2941,6 @@ __global__ __launch_bounds__(NW * 64, NW == 16 ? 4 : (QKV ? 1 : ((ONE || QB) ? 2
               }
           }
           store_key();
-          if constexpr (L2C) {  // the record the step of position p + 1 starts from (a retry of p reads p - 1's: the other entry)
-            if (rec_mine && lane == 0)
-              const_cast<unsigned long long*>(a.next_key)[(size_t)h * a.nk + (a.nk - kNextKeyTail) + (one_pin & 1)] = rec_new;
-          }
         }
       }
     } else {

@@ -22,13 +22,6 @@
 
 #include "cc_common.h"
 
-#ifndef CC_PF_WPE_PV
-#define CC_PF_WPE_PV 2     // waves per SIMD the compiler must leave room for (r6 A/B: 3 = 168 VGPRs)
-#endif
-#ifndef CC_PF_WPE_FLASH
-#define CC_PF_WPE_FLASH 2
-#endif
-
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -252,7 +245,7 @@ struct BoolC {
 };
 
 template <typename T, int NB>
-__global__ __launch_bounds__(256, CC_PF_WPE_PV) void prefill_pv_lds_kernel(MArgs a) {
+__global__ __launch_bounds__(256, 2) void prefill_pv_lds_kernel(MArgs a) {
   __shared__ __attribute__((aligned(16))) uint4 sm_kt[2][kTK][16];   // [buf][key][chunk ^ (key & 15)]
   __shared__ __attribute__((aligned(16))) uint4 sm_vt[2][kD][4];     // [buf][d][chunk ^ ((d >> 2) & 3)]  (V^T, permuted keys)
   __shared__ float sm_p[4][kTK][kTQ + 1];                            // per-wave probability tiles: [r][key][query]
@@ -485,7 +478,7 @@ constexpr float kLazy = 6.0f;  // in units of the scaled logits (natural log): e
 // normalises with — l_exact sums the UNROUNDED weights exp(x - m_ref) (softmax is shift-invariant: exp(x - m_ref) / l_exact is the
 // reference's fp32 softmax up to fp32 rounding, attention_utils.py:52), next to l_run, which sums what P.V multiplies.
 template <typename T, bool STATS = false>
-__global__ __launch_bounds__(256, CC_PF_WPE_FLASH) void prefill_flash_kernel(MArgs a) {
+__global__ __launch_bounds__(256, 2) void prefill_flash_kernel(MArgs a) {
   __shared__ __attribute__((aligned(16))) uint4 sm_kt[2][kTK][16];   // [buf][key][chunk ^ (key & 15)]
   __shared__ __attribute__((aligned(16))) uint4 sm_vt[2][kD][4];     // [buf][d][chunk ^ ((d >> 2) & 3)]  (V^T, permuted keys)
   __shared__ __attribute__((aligned(16))) float sm_row[4][kTQ];      // per wave: a factor per query row, re-read in the O layout
@@ -680,10 +673,6 @@ __global__ __launch_bounds__(256, CC_PF_WPE_FLASH) void prefill_flash_kernel(MAr
 constexpr int kQSeg = 512;    // queries per unit (a multiple of 32; doubled until the segments fit the workspace's 64 partial planes)
 constexpr int kKBlk = 128;    // keys per unit: 4 waves x 32
 
-#ifndef CC_KSTAT_SGB
-#define CC_KSTAT_SGB 0   // VALU instructions woven in behind each (fragment read, MFMA) pair of the side-sum pass (0: the compiler's own order —
-                         // measured best: 1.514 ms per layer at L = 8192 against 1.540 (10) and 1.547 (18), same box)
-#endif
 template <typename T, int NB, bool OBS>
 __global__ __launch_bounds__(256, 2) void prefill_colsum_kstat_kernel(MArgs a, int nseg, int qseg, int units_per_head) {
   __shared__ __attribute__((aligned(16))) uint4 sm_q[2][4][kTQ][16];  // [buf][head][query][chunk ^ (query & 15)]: 64 KiB
@@ -756,12 +745,6 @@ __global__ __launch_bounds__(256, 2) void prefill_colsum_kstat_kernel(MArgs a, i
 #pragma unroll
         for (int r = 0; r < 4; r++) st4n[r] = *reinterpret_cast<const float2*>(a.stats + ((size_t)(h * 4 + r) * L + qc) * 2);
       };
-      // One step = four heads.  The head's eight products (each with its own LDS fragment read) and the PREVIOUS head's rounding
-      // chain are independent instruction streams: they are written side by side and the scheduler is told to weave them — one
-      // fragment read, one MFMA, a slice of the chain, eight times (CC_KSTAT_SGB) — so that the matrix pipe, the LDS and the VALU of
-      // a wave work at the same time.  Left to itself the compiler issues the step's 32 MFMAs first and the 650 VALU instructions
-      // behind them, and the four waves of a workgroup — in lockstep at the tile's barrier — all wait for the LDS together and then
-      // all for the VALU: 5400 cycles per step where either phase alone is ~2000 (profiles/r06_prefill_kstat.md).
       // One step = four heads, written as SLICES: slice i of a stage holds the fragment read of the NEXT product, product i of head
       // r + 1 and pair i (two of the 16 keys) of head r's rounding chain, and ends at a scheduling fence — the matrix pipe, the LDS and
       // the VALU of a wave work at the same time, by construction (hints alone — sched_group_barrier — were followed loosely and

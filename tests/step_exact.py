@@ -95,7 +95,7 @@ MIRRORED_LINES = {
         "return (nt <= kOneMaxTiles && (p.rt == 4 || p.rt == 8)) ? nt : 0;",
         "constexpr int kOneMaxTiles = 16;",
         "if (kind == -1 && H * p.n_split > 3 * p.nw * 64) return nullptr;",
-        "if (allow_xl2 && ((H & 7) == 0 || virt8) && xl2_device_ok()) {",
+        "if (allow_xl2 && (H & 7) == 0 && xl2_device_ok()) {",
     ],
     "cc_attn_decode_kernels.h": ["constexpr int kOneMaxHeads = 32;", "return __builtin_amdgcn_exp2f(x * 1.4426950408889634f);",
                                  "const float e = __builtin_amdgcn_exp2f(t);"],
