@@ -1,8 +1,9 @@
 // cc_gemv_core.h — the arithmetic of the streamed matrix-vector products (cc_gemv.hip), shared with the single-launch layer step
 // that folds the layer's QKV projection in (cc_attn_decode_qkv.hip): the SAME products, chains and reduction orders, so that the
 // fused launch and the stand-alone GEMV give bit-identical q / k / v.  Also here, once for the five cc_gemv*.hip: the weight tiles of
-// the two layouts (gv_plain_tile, gv_scaled_tile), the dense body (gemv_body) and the entry points' shared argument check
-// (gv_check_args).  DESIGN.md §2.19 lists which step lives where, and which are still one text per kernel.
+// the two layouts (gv_plain_tile, gv_scaled_tile), the dense body (gemv_body), its prologue and epilogue as functions (gv_prologue,
+// gv_epilogue), the pipelined body for long rows that calls the same two (gemv_long_body) and the entry points' shared argument
+// check (gv_check_args).  DESIGN.md §2.19 lists which step lives where, and which are still one text per kernel.
 #pragma once
 #include "cc_common.h"
 
@@ -156,31 +157,15 @@ struct GemvArgs {
   int N, K, rope_rows, head_dim;
 };
 
-template <typename T, bool SWIGLU, int RB, int CU, int XS, typename ISSUE, typename GET, typename GET3>
-__device__ __forceinline__ void gemv_body(const GemvArgs& a, ISSUE&& issue, GET&& get, GET3&& get3) {
+// ---- the prologue of every single-vector body: the input vector.  Every lane keeps exactly the 16-byte chunks it will multiply
+//      (no LDS staging).  With a norm prologue, x / delta / norm weight of those chunks are requested together (one memory round
+//      trip), the four waves exchange their partial sums of squares through LDS (one barrier), and the normalised chunks replace h
+//      in the same registers.  sm_red: kGvCoreWaves floats of the caller's LDS.
+template <typename T, int XS>
+__device__ __forceinline__ void gv_prologue(const GemvArgs& a, float* sm_red, uint4 (&xr)[XS], int nch, int nstep, int lane, int wave) {
   constexpr int VEC = 16 / (int)sizeof(T);
-  __shared__ float sm_red[kGvCoreWaves];
-  __shared__ float sm_part[kGvCoreWaves][2][RB];
-  const int K = a.K, N = a.N;
-  const int nch = K / VEC;
+  const int K = a.K;
   const T* xg = reinterpret_cast<const T*>(a.x);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-
-  // ---- Work decomposition: a WORKGROUP owns RB consecutive rows at a time; its four waves split K (wave w takes
-  //      the 1 KiB segments w, w+4, w+8, ... of every row), CU segments per row in flight per wave, and the four
-  //      partial sums meet in LDS.  For the decode shapes this puts a whole matrix in flight in one phase
-  //      (wo: 2 rows x 2 segments per wave; w2: 4 rows x 4 of 7 segments) instead of looping inside a wave.
-  //      The FIRST tile's weight loads are issued before the input vector is touched: W does not depend on x.
-  const int nseg = (nch + 63) / 64;                      // 1 KiB segments per row
-  const int nstep = (nseg + kGvCoreWaves - 1) / kGvCoreWaves;    // segments per wave (<= XS, checked by the launcher)
-  const int row_first = blockIdx.x * RB;
-  if (row_first < N) issue(row_first, 0);
-
-  // ---- the input vector: every lane keeps exactly the 16-byte chunks it will multiply (no LDS staging).  With a
-  //      norm prologue, x / delta / norm weight of those chunks are requested together (one memory round trip), the
-  //      four waves exchange their partial sums of squares through LDS (one barrier), and the normalised chunks
-  //      replace h in the same registers.
-  uint4 xr[XS];
   if (a.norm_w != nullptr) {
     const T* dg = reinterpret_cast<const T*>(a.delta);
     const T* wg = reinterpret_cast<const T*>(a.norm_w);
@@ -240,30 +225,17 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, ISSUE&& issue, GET&
       xr[j] = (j < nstep && c < nch) ? reinterpret_cast<const uint4*>(xg)[c] : make_uint4(0, 0, 0, 0);
     }
   }
+}
 
+// ---- the end of a row group in every single-vector body: the four K-quarters of every row meet in LDS (fixed order:
+//      deterministic), then lane r of wave 0 finishes row r0 + r (bias, rounding to the model dtype, SwiGLU, RoPE, store).
+//      sm_part: the caller's LDS, reused by the next row group (the second barrier).
+template <typename T, bool SWIGLU, int RB>
+__device__ __forceinline__ void gv_epilogue(const GemvArgs& a, float (*sm_part)[2][RB], const float (&acc)[RB], const float (&acc3)[RB],
+                                            int r0, int lane, int wave) {
+  const int N = a.N;
   T* yo = reinterpret_cast<T*>(a.y);
-  bool first = true;
-  for (int r0 = row_first; r0 < N; r0 += gridDim.x * RB) {
-    float acc[RB], acc3[RB];
-#pragma unroll
-    for (int r = 0; r < RB; r++) acc[r] = acc3[r] = 0.f;
-#pragma unroll
-    for (int s0 = 0; s0 < XS; s0 += CU) {
-      if (s0 < nstep) {
-        if (!first) issue(r0, s0);
-        first = false;
-#pragma unroll
-        for (int u = 0; u < CU; u++) {
-          const uint4 xv = xr[s0 + u < XS ? s0 + u : XS - 1];  // beyond nstep the weights are zero-filled
-#pragma unroll
-          for (int r = 0; r < RB; r++) {
-            acc[r] = Dot16<T>::run(get(r, u), xv, acc[r]);
-            if (SWIGLU) acc3[r] = Dot16<T>::run(get3(r, u), xv, acc3[r]);
-          }
-        }
-      }
-    }
-    // ---- the four K-quarters of every row meet in LDS (fixed order: deterministic)
+  {
 #pragma unroll
     for (int r = 0; r < RB; r++) {
       const float s = gv_wave_sum(acc[r]);
@@ -303,6 +275,125 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, ISSUE&& issue, GET&
       if (lane < RB && row < N) ElemTraits<T>::store(yo, (size_t)row, cc_opaque_f32(out));
     }
     __syncthreads();  // sm_part is reused by the next row group
+  }
+}
+
+template <typename T, bool SWIGLU, int RB, int CU, int XS, typename ISSUE, typename GET, typename GET3>
+__device__ __forceinline__ void gemv_body(const GemvArgs& a, ISSUE&& issue, GET&& get, GET3&& get3) {
+  constexpr int VEC = 16 / (int)sizeof(T);
+  __shared__ float sm_red[kGvCoreWaves];
+  __shared__ float sm_part[kGvCoreWaves][2][RB];
+  const int N = a.N;
+  const int nch = a.K / VEC;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+
+  // ---- Work decomposition: a WORKGROUP owns RB consecutive rows at a time; its four waves split K (wave w takes
+  //      the 1 KiB segments w, w+4, w+8, ... of every row), CU segments per row in flight per wave, and the four
+  //      partial sums meet in LDS.  For the decode shapes this puts a whole matrix in flight in one phase
+  //      (wo: 2 rows x 2 segments per wave; w2: 4 rows x 4 of 7 segments) instead of looping inside a wave.
+  //      The FIRST tile's weight loads are issued before the input vector is touched: W does not depend on x.
+  const int nseg = (nch + 63) / 64;                      // 1 KiB segments per row
+  const int nstep = (nseg + kGvCoreWaves - 1) / kGvCoreWaves;    // segments per wave (<= XS, checked by the launcher)
+  const int row_first = blockIdx.x * RB;
+  if (row_first < N) issue(row_first, 0);
+
+  uint4 xr[XS];
+  gv_prologue<T, XS>(a, sm_red, xr, nch, nstep, lane, wave);
+
+  bool first = true;
+  for (int r0 = row_first; r0 < N; r0 += gridDim.x * RB) {
+    float acc[RB], acc3[RB];
+#pragma unroll
+    for (int r = 0; r < RB; r++) acc[r] = acc3[r] = 0.f;
+#pragma unroll
+    for (int s0 = 0; s0 < XS; s0 += CU) {
+      if (s0 < nstep) {
+        if (!first) issue(r0, s0);
+        first = false;
+#pragma unroll
+        for (int u = 0; u < CU; u++) {
+          const uint4 xv = xr[s0 + u < XS ? s0 + u : XS - 1];  // beyond nstep the weights are zero-filled
+#pragma unroll
+          for (int r = 0; r < RB; r++) {
+            acc[r] = Dot16<T>::run(get(r, u), xv, acc[r]);
+            if (SWIGLU) acc3[r] = Dot16<T>::run(get3(r, u), xv, acc3[r]);
+          }
+        }
+      }
+    }
+    gv_epilogue<T, SWIGLU, RB>(a, sm_part, acc, acc3, r0, lane, wave);
+  }
+}
+
+// ---- the same GEMV for LONG rows (NSTEP = 3 .. 8 column steps per wave, a template argument), plain form, with its own requests in
+//      flight while it works: small RB x CU tiles in TWO register sets, and the tile after the current one — the next column steps
+//      of this row group, or the first tile of the workgroup's next row group — is requested before the current one is consumed, so
+//      a wave's requests also cross the wave sums, the LDS meet and the barriers of gv_epilogue.  Column steps beyond NSTEP are not
+//      requested and not read (known at compile time: the waits count down load by load); a next row group that does not exist
+//      is not requested either.  The arithmetic of a row is gemv_body's: chunk ownership, a lane's Dot16 chain over ascending column
+//      steps, gv_wave_sum, the four-wave meet, prologue and epilogue (the same two functions).  Where gemv_body's long-row geometry
+//      (4 column steps in flight) ends a row on zero-filled chunks, NSTEP % 4 != 0, the chain here ends on one Dot16 of zeros too.
+//      Callables: issue(set, r0, s0) requests a tile into register set `set`, get(set, r, u, r0, s0) hands one of its chunks out;
+//      `set` is a GvSet<0 or 1> (the sets are registers, so the choice is a type).  Tile t of a row group lives in set
+//      (PAR + t) & 1, and the next row group starts where this one ended: PAR ^ (tiles & 1).
+template <int V>
+struct GvSet {
+  static constexpr int value = V;
+};
+
+template <typename T, int RB, int CU, int NSTEP, int PAR, typename ISSUE, typename GET>
+__device__ __forceinline__ void gv_long_group(const uint4 (&xr)[NSTEP], float (&acc)[RB], int r0, int r_next, int N, ISSUE&& issue, GET&& get) {
+  constexpr int NT = (NSTEP + CU - 1) / CU;
+#pragma unroll
+  for (int t = 0; t < NT; t++) {
+    const int s0 = t * CU;
+    const bool even = ((PAR + t) & 1) == 0;  // (constants once unrolled: the choices of a set fold)
+    if (t + 1 < NT) {
+      if (even) issue(GvSet<1>(), r0, s0 + CU);
+      else issue(GvSet<0>(), r0, s0 + CU);
+    } else if (r_next < N) {
+      if (even) issue(GvSet<1>(), r_next, 0);
+      else issue(GvSet<0>(), r_next, 0);
+    }
+#pragma unroll
+    for (int u = 0; u < CU; u++) {
+      if (s0 + u < NSTEP) {
+#pragma unroll
+        for (int r = 0; r < RB; r++)
+          acc[r] = Dot16<T>::run(even ? get(GvSet<0>(), r, u, r0, s0) : get(GvSet<1>(), r, u, r0, s0), xr[s0 + u < NSTEP ? s0 + u : 0], acc[r]);
+      }
+    }
+  }
+  if (NSTEP % 4 != 0) {
+#pragma unroll
+    for (int r = 0; r < RB; r++) acc[r] = Dot16<T>::run(make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), acc[r]);
+  }
+}
+
+template <typename T, int RB, int CU, int NSTEP, typename ISSUE, typename GET>
+__device__ __forceinline__ void gemv_long_body(const GemvArgs& a, ISSUE&& issue, GET&& get) {
+  constexpr int VEC = 16 / (int)sizeof(T);
+  constexpr int NT = (NSTEP + CU - 1) / CU;
+  __shared__ float sm_red[kGvCoreWaves];
+  __shared__ float sm_part[kGvCoreWaves][2][RB];
+  const int N = a.N;
+  const int nch = a.K / VEC;  // ((nch + 63) / 64 + 3) / 4 == NSTEP, checked by the launcher
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int row_first = blockIdx.x * RB, stride = gridDim.x * RB;
+  if (row_first < N) issue(GvSet<0>(), row_first, 0);  // before the input vector is touched: W does not depend on x
+
+  uint4 xr[NSTEP];
+  gv_prologue<T, NSTEP>(a, sm_red, xr, nch, NSTEP, lane, wave);
+
+  int par = 0;
+  for (int r0 = row_first; r0 < N; r0 += stride) {
+    float acc[RB], acc3[RB];
+#pragma unroll
+    for (int r = 0; r < RB; r++) acc[r] = acc3[r] = 0.f;
+    if (NT % 2 == 0 || par == 0) gv_long_group<T, RB, CU, NSTEP, 0>(xr, acc, r0, r0 + stride, N, issue, get);
+    else gv_long_group<T, RB, CU, NSTEP, 1>(xr, acc, r0, r0 + stride, N, issue, get);
+    par ^= NT & 1;
+    gv_epilogue<T, false, RB>(a, sm_part, acc, acc3, r0, lane, wave);
   }
 }
 

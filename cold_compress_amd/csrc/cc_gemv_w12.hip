@@ -32,6 +32,10 @@
 // same on the dword rotated right by 4 gives those of weights 4 .. 7; four v_perm interleave high and low bytes.  Nine operations
 // per chunk against 24.  The layout of a packed copy travels in bits 8 .. 15 of the `rb` word (include/coldcompress.h).
 //
+// Layout id 2, "long": planar codes with the records and the launch of gemv_w12_long_kernel below — plain matrices with 3 .. 8
+// column steps per wave (4096 < K <= 16384), two register sets of 2 x 2 tiles, the next tile requested before the current one is
+// decoded.  On by default for w2 (seven steps) and K = 8192 (four): DESIGN.md §2.17.
+//
 // Packer (cc_w12_pack, once per tensor): exponent histogram -> the window of 16 that covers most weights -> codes and records.
 #include <cstdio>
 #include <cstdlib>
@@ -57,7 +61,7 @@ struct GemvW12Args {
   uint32_t bw, bw3;     // layout 0: base << 7 | base << 23; planar: base / 2 in every byte
 };
 
-constexpr int kW12Planar = 1;  // layout ids
+constexpr int kW12Planar = 1, kW12Long = 2;  // layout ids (kW12Long: planar codes, the long-row launch and its records)
 
 typedef unsigned int u32x3_t __attribute__((ext_vector_type(3)));
 
@@ -151,17 +155,91 @@ __global__ __launch_bounds__(kW12Threads) void gemv_w12_kernel(GemvW12Args a) {
   gemv_body<bf16_t, SWIGLU, RB, CU, XS>(a.g, issue, get, get3);
 }
 
+// ---- layout id 2, "long": planar codes behind a launch of their own for LONG rows, 3 .. 8 column steps per wave (4096 < K <= 16384),
+//      plain form only.  gemv_long_body (cc_gemv_core.h) keeps two small tiles of codes in two register sets and requests the tile
+//      after the current one — with its record ahead of its codes, as above — before it decodes the current one, also across the
+//      end of a row group.  Column steps beyond nstep are not requested (wave-uniform); rows beyond N and the chunks of a partial
+//      last segment keep the clamped unconditional form.  Records are the packer's, laid out for this tile shape.
+//      NORM false: the launch has no norm prologue (w2), and the registers that prologue needs (x, delta and the norm weight of
+//      every input chunk at once) do not count against the kernel.
+template <int RB, int CU, int NSTEP, bool NORM>
+__global__ __launch_bounds__(kW12Threads) void gemv_w12_long_kernel(GemvW12Args a) {
+  if (!NORM) a.g.norm_w = nullptr;  // (it is: launch_w12_long)
+  const int N = a.g.N, nch = a.g.K / 8;
+  constexpr int nph = (NSTEP + CU - 1) / CU;
+  // (the wave index as a scalar: row and record addresses are then scalar too, and a load takes a 32-bit lane offset beside them)
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const char* Wb = reinterpret_cast<const char*>(a.g.W);
+  const char* Pb = reinterpret_cast<const char*>(a.P);
+  uint32_t coff[NSTEP];  // byte offset of this lane's codes in a row, per column step (clamped into the row)
+#pragma unroll
+  for (int s = 0; s < NSTEP; s++) {
+    const int c = (s * kW12Waves + wave) * 64 + lane;
+    coff[s] = (uint32_t)(c < nch ? c : nch - 1) * 12u;
+  }
+  u32x3_t q0[RB][CU], q1[RB][CU];
+  uint32_t rec0 = 0, rec1 = 0;  // the two tiles' records: word i in lane i < 8
+  auto request = [&](u32x3_t (&q)[RB][CU], uint32_t& rec, int r0, int s0) {
+    rec = a.R[(((size_t)(r0 / RB) * nph + s0 / CU) * kW12Waves + wave) * 8 + (lane & 7)];
+#pragma unroll
+    for (int u = 0; u < CU; u++) {
+      if (s0 + u < NSTEP) {
+#pragma unroll
+        for (int r = 0; r < RB; r++) {
+          const int rr = r0 + r < N ? r0 + r : N - 1;
+          const char* row = Pb + (size_t)rr * nch * 12;
+          q[r][u] = __builtin_nontemporal_load(reinterpret_cast<const u32x3_t*>(row + coff[s0 + u < NSTEP ? s0 + u : 0]));
+        }
+      }
+    }
+  };
+  auto chunk = [&](u32x3_t code, uint32_t rc, int r, int u, int r0, int s0) {  // (called for column steps below NSTEP only)
+    const int c = ((s0 + u) * kW12Waves + wave) * 64 + lane;
+    const bool in = c < nch && (r0 + r < N);
+    uint4 d = w12_decode<kW12Planar>(code, in ? a.bw : 0u);
+    const uint32_t cnt = __builtin_amdgcn_readlane(rc, 0);
+    if (cnt != 0u) {  // wave-uniform
+      if (cnt == kW12Overflow) {
+        d = in ? nt_load(reinterpret_cast<const uint4*>(Wb + (size_t)(r0 + r) * nch * 16 + (uint32_t)c * 16u)) : make_uint4(0, 0, 0, 0);
+      } else {
+        d = w12_patch(d, rc, (int)cnt, r * CU + u, lane);
+      }
+    }
+    return d;
+  };
+  auto issue = [&](auto set, int r0, int s0) {
+    if constexpr (decltype(set)::value == 0) request(q0, rec0, r0, s0);
+    else request(q1, rec1, r0, s0);
+  };
+  auto get = [&](auto set, int r, int u, int r0, int s0) {
+    if constexpr (decltype(set)::value == 0) return chunk(q0[r][u], rec0, r, u, r0, s0);
+    else return chunk(q1[r][u], rec1, r, u, r0, s0);
+  };
+  gemv_long_body<bf16_t, RB, CU, NSTEP>(a.g, issue, get);
+}
+
 // ---- launch geometry.  The starting point is cc_gemv.hip's pick_cfg (the same loads in flight per lane, each a quarter shorter).
 //      Both layouts take it: for planar, w2 at 2 x 4 on 512 / 1024 workgroups measured 27.1 / 27.6 us against 28.1 at 4 x 4 and 20.6
 //      dense (with the record still requested last: DESIGN.md §2.17), and wo / wqkv already run the dense kernel's own geometry;
 //      that instantiation is not built.
-static GvCfg pick_w12_cfg(int N, int K, bool swiglu) {
+// the long-row launch: the tile and the most workgroups that the same-session sweeps chose: 2 x 2 everywhere;
+// one resident round of workgroups where the kernel runs at 3 waves per SIMD (5 .. 8 column steps: w2 17.4 us on 768 workgroups
+// against 18.7 / 19.1 / 17.9 / 18.1 / 18.4 / 18.6 on 512 / 1024 / 1280 / 1536 / 1792 / 2048), 1024 at 3 and 4 column steps
+// (8192 x 8192: 19.4 us against 19.8 / 19.5 on 1280 / 2048; 128256 x 8192: 239.5 against 244.9 / 243.4)
+constexpr int kW12LongRb = 2, kW12LongCu = 2;
+static int w12_long_cap(int K) {
+  const int nstep = ((K / 8 + 63) / 64 + kGvCoreWaves - 1) / kGvCoreWaves;
+  return nstep <= 4 ? 1024 : 768;
+}
+
+static GvCfg pick_w12_cfg(int N, int K, bool swiglu, int layout) {
   static int env_rb = -1, env_cu = -1, env_cap = 2048;
   if (env_rb < 0) {  // tuning hook: CC_GEMV_W12_CFG="RB,CU[,max workgroups]"
     env_rb = env_cu = 0;
     if (const char* e = getenv("CC_GEMV_W12_CFG")) sscanf(e, "%d,%d,%d", &env_rb, &env_cu, &env_cap);
   }
   if (env_rb > 0 && env_cu > 0) return {env_rb, env_cu, env_cap};
+  if (layout == kW12Long) return {kW12LongRb, kW12LongCu, w12_long_cap(K)};
   const int nseg = (K / 8 + 63) / 64, nstep = (nseg + kW12Waves - 1) / kW12Waves;
   GvCfg c;
   c.cap = 2048;
@@ -183,6 +261,7 @@ static GvCfg pick_w12_cfg(int N, int K, bool swiglu) {
   return c;
 }
 
+// the long-row launch: the tile and the most workgroups that the same-session sweep chose
 static int w12_xs(int K) {
   const int nseg = (K / 8 + 63) / 64, nstep = (nseg + kW12Waves - 1) / kW12Waves;
   return nstep <= 2 ? 2 : nstep <= 8 ? 8 : 0;  // (rows beyond 8 steps per wave, K > 16384, are not served: CC_ERR_UNSUPPORTED)
@@ -190,7 +269,8 @@ static int w12_xs(int K) {
 
 static bool w12_cfg_built(int layout, bool swiglu, int xs, int rb, int cu) {
   const int key = (swiglu ? 100000 : 0) + xs * 1000 + rb * 10 + cu;
-  switch (key) {  // (the same list in both layouts)
+  if (layout == kW12Long) return key == 8022;  // (4 x 2 and 2 x 4 lost the sweep and are not built)
+  switch (key) {  // (the same list in layouts 0 and 1)
     case 2022: case 2042: case 8044: case 102022: case 108024: return layout == 0 || layout == kW12Planar;
     default: return false;
   }
@@ -198,8 +278,35 @@ static bool w12_cfg_built(int layout, bool swiglu, int xs, int rb, int cu) {
 
 // the planar launch classes switched on by default (cc_w12_geometry): the SwiGLU pair and the LM head at K <= 4096, <true, 2, 2, 2>
 // and <false, 2, 2, 2> on 1024 workgroups — 33.2 us against 34.9 (layout 0) and 39.6 (dense), 123.7 against 134.9 and 156.3.
-// wqkv, wo and w2 lost to the dense kernel in this layout too (1.03x, 1.12x, 1.23x) and stay dense; K = 8192 is not switched on.
+// wqkv, wo and w2 lost to the dense kernel in this layout too (1.03x, 1.12x, 1.23x); wqkv and wo stay dense, w2 and the plain K = 8192
+// shapes are served by layout 2's launch (w12_long_won); K = 8192 is not switched on in this layout.
 static bool w12_planar_won(int nstep, bool swiglu, int N) { return nstep <= 2 && (swiglu || N >= 32768); }
+
+// the long-row classes switched on by default (cc_w12_geometry, layout 2), by the same rule as planar's: the two that were measured
+// (profiles/w12_long_gemv.jsonl) — seven column steps per wave (w2, 4096 x 14336: 17.5 us against 20.2 dense and 26.0 planar) and
+// four (K = 8192: 8192 x 8192 and 128256 x 8192).  3, 5, 6 and 8 steps are served and tested, not measured, and stay off.
+static bool w12_long_won(int nstep) { return nstep == 7 || nstep == 4; }
+
+template <int RB, int CU>
+static int launch_w12_long(const GemvW12Args& a, hipStream_t st, int cap) {
+  int blocks = (a.g.N + RB - 1) / RB;
+  if (blocks > cap) blocks = cap;
+  const int nstep = ((a.g.K / 8 + 63) / 64 + kW12Waves - 1) / kW12Waves;
+#define W12_LONG(NS)                                                                                                   \
+  if (a.g.norm_w) hipLaunchKernelGGL((gemv_w12_long_kernel<RB, CU, NS, true>), dim3(blocks), dim3(kW12Threads), 0, st, a); \
+  else hipLaunchKernelGGL((gemv_w12_long_kernel<RB, CU, NS, false>), dim3(blocks), dim3(kW12Threads), 0, st, a)
+  switch (nstep) {  // (one kernel per number of column steps: which tiles exist is then known to the compiler)
+    case 3: W12_LONG(3); break;
+    case 4: W12_LONG(4); break;
+    case 5: W12_LONG(5); break;
+    case 6: W12_LONG(6); break;
+    case 7: W12_LONG(7); break;
+    case 8: W12_LONG(8); break;
+    default: return CC_ERR_UNSUPPORTED;
+  }
+#undef W12_LONG
+  return CC_OK;
+}
 
 template <int LAY, bool SWIGLU, int RB, int CU, int XS>
 static void launch_w12_cfg(const GemvW12Args& a, hipStream_t st, int cap) {
@@ -242,7 +349,7 @@ __global__ void w12_base_kernel(int32_t* meta, int nrec, int layout) {
   long long best = -1;
   int base = 0;
   // base + 15 <= 255: the decode's index add never carries into the sign.  Planar: even bases only (its index is exponent >> 1)
-  for (int b = 0; b + 15 <= 255; b += (layout == kW12Planar ? 2 : 1)) {
+  for (int b = 0; b + 15 <= 255; b += (layout != 0 ? 2 : 1)) {
     long long s = 0;
     for (int i = 0; i < 16; i++) s += meta[kW12MetaHist + b + i];
     if (s > best) {
@@ -282,7 +389,7 @@ __global__ __launch_bounds__(64) void w12_pack_kernel(const uint4* W, int N, int
       const uint32_t bits = (wd[k >> 1] >> ((k & 1) * 16)) & 0xffffu;
       const int idx = (int)((bits >> 7) & 0xffu) - base;
       const bool esc = in && (idx < 0 || idx > 15);
-      if (!esc && layout == kW12Planar) {
+      if (!esc && layout != 0) {  // planar codes (layouts 1 and 2)
         if (in) {  // (base is even here: idx >> 1 = (exponent >> 1) - base / 2)
           const uint32_t hi = (uint32_t)idx >> 1, sg = bits >> 15;
           const int j = k & 3;
@@ -321,13 +428,20 @@ __global__ __launch_bounds__(64) void w12_pack_kernel(const uint4* W, int N, int
 
 // (the layout id travels in bits 8 .. 15 of a word whose low byte keeps its old meaning: 0 = the first layout, as before)
 static inline int w12_layout_of(int32_t word) { return (word >> 8) & 0xff; }
+static inline bool w12_layout_known(int layout) { return layout == 0 || layout == kW12Planar || layout == kW12Long; }
+// layout 2 serves plain matrices with 3 .. 8 column steps per wave only (4096 < K <= 16384)
+static inline bool w12_long_serves(int K) {
+  const int nstep = ((K / 8 + 63) / 64 + kW12Waves - 1) / kW12Waves;
+  return nstep >= 3 && nstep <= 8;
+}
 
 extern "C" int cc_w12_geometry(int32_t N, int32_t K, int32_t swiglu, int32_t* out) {
   const int layout = w12_layout_of(swiglu);
   const bool pair = (swiglu & 0xff) != 0;
-  if (!out || N <= 0 || K <= 0 || (swiglu >> 16) != 0 || (layout != 0 && layout != kW12Planar)) return CC_ERR_BAD_ARG;
+  if (!out || N <= 0 || K <= 0 || (swiglu >> 16) != 0 || !w12_layout_known(layout)) return CC_ERR_BAD_ARG;
   if (K % 8 || (size_t)K * 2 > 64 * 1024) return CC_ERR_UNSUPPORTED;
-  const GvCfg c = pick_w12_cfg(N, K, pair);
+  if (layout == kW12Long && (pair || !w12_long_serves(K))) return CC_ERR_UNSUPPORTED;
+  const GvCfg c = pick_w12_cfg(N, K, pair, layout);
   const int xs = w12_xs(K);
   if (xs == 0 || c.cu > xs || c.cap <= 0 || !w12_cfg_built(layout, pair, xs, c.rb, c.cu)) return CC_ERR_UNSUPPORTED;
   out[0] = c.rb;
@@ -335,6 +449,10 @@ extern "C" int cc_w12_geometry(int32_t N, int32_t K, int32_t swiglu, int32_t* ou
   out[2] = xs;
   out[3] = c.cap;
   const int nstep = ((K / 8 + 63) / 64 + kW12Waves - 1) / kW12Waves;
+  if (layout == kW12Long) {  // the same rule and regime
+    out[4] = ((long long)N >= (long long)c.rb * c.cap && w12_long_won(nstep)) ? 1 : 0;
+    return CC_OK;
+  }
   if (layout == kW12Planar) {
     // planar: the launch classes that MEASURED faster than both the dense kernel and the first layout, by more than the dense
     // kernel's own spread (profiles/w12_planar_gemv.jsonl), in the regime measured: a grid that is full
@@ -354,10 +472,11 @@ extern "C" int cc_w12_pack(const void* W, int32_t N, int32_t K, int32_t rb, int3
                            cc_stream_t stream) {
   CC_ENTRY();
   const int layout = w12_layout_of(rb);
-  if ((rb >> 16) != 0 || (layout != 0 && layout != kW12Planar)) return CC_ERR_BAD_ARG;
+  if ((rb >> 16) != 0 || !w12_layout_known(layout)) return CC_ERR_BAD_ARG;
   rb &= 0xff;
   if (!W || !codes || !records || !meta || N <= 0 || K <= 0 || rb <= 0 || cu <= 0 || rb * cu > 64) return CC_ERR_BAD_ARG;
   if (K % 8 || (size_t)K * 2 > 64 * 1024) return CC_ERR_UNSUPPORTED;
+  if (layout == kW12Long && !w12_long_serves(K)) return CC_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   const int nch = K / 8;
   const int nstep = ((nch + 63) / 64 + kW12Waves - 1) / kW12Waves;
@@ -384,12 +503,12 @@ extern "C" int cc_gemv_fused_w12(const void* codes, const void* records, int32_t
                                  int32_t head_dim, void* y, int32_t N, int32_t K, int32_t dtype, cc_stream_t stream) {
   CC_ENTRY();
   const int layout = w12_layout_of(rb);
-  if ((rb >> 16) != 0 || (layout != 0 && layout != kW12Planar)) return CC_ERR_BAD_ARG;
+  if ((rb >> 16) != 0 || !w12_layout_known(layout)) return CC_ERR_BAD_ARG;
   rb &= 0xff;
   if (!codes || !records || !W || !x || !y || N <= 0 || K <= 0 || !cc_dt_ok(dtype)) return CC_ERR_BAD_ARG;
   if ((W3 != nullptr) != (codes3 != nullptr) || (W3 != nullptr) != (records3 != nullptr)) return CC_ERR_BAD_ARG;
   if (base < 0 || base > 240 || (W3 && (base3 < 0 || base3 > 240))) return CC_ERR_BAD_ARG;
-  if (layout == kW12Planar && ((base & 1) || (W3 && (base3 & 1)))) return CC_ERR_BAD_ARG;
+  if (layout != 0 && ((base & 1) || (W3 && (base3 & 1)))) return CC_ERR_BAD_ARG;
   if (!w12_layout_ok(codes, layout) || (codes3 && !w12_layout_ok(codes3, layout))) return CC_ERR_BAD_ARG;  // packed in the other layout
   if ((delta || h_out) && !norm_w) return CC_ERR_BAD_ARG;
   if (freqs && (W3 || rope_rows < 0 || rope_rows > N || head_dim <= 0 || (head_dim & 1) || (rope_rows % head_dim))) return CC_ERR_BAD_ARG;
@@ -405,7 +524,7 @@ extern "C" int cc_gemv_fused_w12(const void* codes, const void* records, int32_t
   a.P3 = reinterpret_cast<const uint32_t*>(codes3);
   a.R = reinterpret_cast<const uint32_t*>(records);
   a.R3 = reinterpret_cast<const uint32_t*>(records3);
-  if (layout == kW12Planar) {
+  if (layout != 0) {
     a.bw = (uint32_t)(base >> 1) * 0x01010101u;
     a.bw3 = (uint32_t)(base3 >> 1) * 0x01010101u;
   } else {
@@ -425,6 +544,9 @@ extern "C" int cc_gemv_fused_w12(const void* codes, const void* records, int32_t
     case 1008044: launch_w12_cfg<kW12Planar, false, 4, 4, 8>(a, st, geo[3]); break;
     case 1102022: launch_w12_cfg<kW12Planar, true, 2, 2, 2>(a, st, geo[3]); break;
     case 1108024: launch_w12_cfg<kW12Planar, true, 2, 4, 8>(a, st, geo[3]); break;
+    case 2008022:
+      if (launch_w12_long<2, 2>(a, st, geo[3]) != CC_OK) return CC_ERR_UNSUPPORTED;
+      break;
     default: return CC_ERR_UNSUPPORTED;
   }
   CC_LAUNCH_CHECK();

@@ -93,11 +93,12 @@ class W12Packed:
     [N, K / 8, 3], `records` uint32 [records, 8], `base` the first exponent of the window, (`rb`, `cu`, `xs`, `cap`) the launch
     geometry it was packed for (the records follow `rb` and `cu`); `n_overflow` records hold more than 7 escapes (their tiles are
     read from the dense tensor), `n_escapes` weights lie outside the window.  `layout`: 0 (sign + mantissa bytes and 4-bit exponent
-    indices) or W12_PLANAR (low bytes and a dword of high-byte fields; `base` is even); a copy is tied to it as to (`rb`, `cu`)."""
+    indices), W12_PLANAR (low bytes and a dword of high-byte fields; `base` is even) or W12_LONG (planar codes with the records of
+    the long-row launch, plain matrices with 4096 < K <= 16384); a copy is tied to it as to (`rb`, `cu`)."""
     __slots__ = ("codes", "records", "base", "rb", "cu", "xs", "cap", "n_records", "n_overflow", "n_escapes", "layout")
 
 
-W12_PLANAR = 1  # layout ids (include/coldcompress.h): they travel in bits 8 .. 15 of the rb / swiglu words
+W12_PLANAR, W12_LONG = 1, 2  # layout ids (include/coldcompress.h): they travel in bits 8 .. 15 of the rb / swiglu words
 
 
 W12_MAX_OVERFLOW = 0.01  # a tensor with more overflowing records than this share stays on cc_gemv_fused
@@ -118,7 +119,7 @@ def w12_enabled():
 def w12_geometry(N, K, swiglu=False, layout=0):
     """(RB, CU, input chunks per lane, most workgroups, faster) of the packed GEMV's launch for this shape, form and code layout, or
     None: unsupported.  `faster`: 1 when that launch class measured faster than the dense kernel (layout 0) resp. than the dense
-    kernel and layout 0 (W12_PLANAR), else 0."""
+    kernel and layout 0 (W12_PLANAR), than the dense kernel and the planar launch (W12_LONG), else 0."""
     key = (int(N), int(K), bool(swiglu), int(layout))
     if key not in _w12_geo:
         out = (C.c_int32 * 5)()
@@ -166,13 +167,18 @@ def _w12_drop(key):
 def _w12_get(weight, swiglu, force=False, layout=None):
     """The packed copy of `weight`, built at its first eager use; None: take the plain path (a launch class that did not measure
     faster than the dense kernel, unless `force`; under capture before a copy exists; refused by the packer; unsupported shape; no
-    room).  `layout` None: planar where its launch class measured faster than the dense kernel and layout 0, else layout 0.  Keyed
-    on the storage, its version counter and the layout: an in-place change of the weight drops the copy."""
+    room).  `layout` None: the long-row launch (W12_LONG) where its class measured faster than the dense kernel and planar, else
+    planar where its launch class measured faster than the dense kernel and layout 0, else layout 0.  Keyed on the storage, its
+    version counter and the layout: an in-place change of the weight drops the copy."""
     global _w12_warned
     N, K = weight.shape
     if layout is None:
-        planar = w12_geometry(N, K, swiglu, W12_PLANAR)
-        layout = W12_PLANAR if (planar is not None and planar[4]) else 0
+        layout = 0
+        for lay in (W12_LONG, W12_PLANAR):
+            g = w12_geometry(N, K, swiglu, lay)
+            if g is not None and g[4]:
+                layout = lay
+                break
     geo = w12_geometry(N, K, swiglu, layout)
     if geo is None or not (force or geo[4]):
         return None
@@ -279,9 +285,10 @@ def gemv_fused(weight, x, w3=None, delta=None, norm_weight=None, eps=1e-5, h_out
     if w12 and weight.dtype == torch.bfloat16 and w12_enabled() and (w3 is None or w3.dtype == torch.bfloat16):
         # the lossless 12-bit packed copies of the weights: the same bits from three quarters of the bytes (cc_gemv_fused_w12).
         # w12=True: where that launch class measured faster than the dense kernel, in the layout that measured fastest there;
-        # w12="force" / "force-planar": wherever the kernel serves the shape, in layout 0 / the planar layout
-        force = w12 in ("force", "force-planar")
-        lay = {"force": 0, "force-planar": W12_PLANAR}.get(w12)
+        # w12="force" / "force-planar" / "force-long": wherever the kernel serves the shape, in layout 0 / the planar layout / the
+        # long-row launch (layout id 2)
+        force = w12 in ("force", "force-planar", "force-long")
+        lay = {"force": 0, "force-planar": W12_PLANAR, "force-long": W12_LONG}.get(w12)
         pk = _w12_get(weight, w3 is not None, force, lay)
         pk3 = _w12_get(w3, True, force, lay) if (w3 is not None and pk is not None) else None
         if pk is not None and (w3 is None or pk3 is not None):

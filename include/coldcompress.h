@@ -814,9 +814,9 @@ int cc_gemv_fused_multi(const void* W, const void* W3, const void* x, const void
  *             whose record overflowed are read from them.  dtype: CC_DT_BF16 (others: CC_ERR_UNSUPPORTED).  A plain grid, no
  *             atomics; arguments are validated before any launch: an error writes nothing.
  *
- * A packed copy exists in one of two code LAYOUTS.  The layout id travels in bits 8 .. 15 of the `rb` word of cc_w12_pack and
+ * A packed copy exists in one of three LAYOUTS (two code formats; id 2 is a launch and record layout over the second).  The id travels in bits 8 .. 15 of the `rb` word of cc_w12_pack and
  * cc_gemv_fused_w12 and of the `swiglu` word of cc_w12_geometry (the low byte keeps its meaning; higher bits must be 0; an id other
- * than 0 or 1: CC_ERR_BAD_ARG).  Id 0 is the layout above.  Id 1, "planar", keeps chunk index, records, overflow rule and the
+ * than 0, 1 or 2: CC_ERR_BAD_ARG).  Id 0 is the layout above.  Id 1, "planar", keeps chunk index, records, overflow rule and the
  * dense fallback and changes the 12 bytes of a chunk, with e the 8-bit exponent, s the sign, `base` EVEN and B = base / 2:
  *   dword 0, 1  byte k = the low byte of bf16 weight k resp. 4 + k as it is (e & 1 in bit 7, the mantissa below)
  *   dword 2     byte k = s of weight k << 7 | ((e >> 1) - B) of weight 4 + k << 4 | s of weight 4 + ((k + 3) & 3) << 3 |
@@ -827,7 +827,15 @@ int cc_gemv_fused_multi(const void* W, const void* W3, const void* x, const void
  * cc_w12_geometry answers per layout: its own (RB, CU, chunks, workgroups) and, as out[4], whether that layout's launch class
  * measured faster than cc_gemv_fused AND than layout 0 on MI355X, in the regime measured (N >= RB x workgroups: a full grid).
  * A copy is tied to its layout as to (rb, cu): cc_w12_pack notes the layout by the address of `codes` (host memory, this
- * process), and cc_gemv_fused_w12 returns CC_ERR_BAD_ARG, before any launch, for codes handed in under the other id. */
+ * process), and cc_gemv_fused_w12 returns CC_ERR_BAD_ARG, before any launch, for codes handed in under another id.
+ * Id 2, "long": planar codes (id 1's 12 bytes, an even base) behind a launch of its own for LONG rows — plain matrices (W3 == NULL)
+ * with 3 <= nstep <= 8, i.e. 4096 < K <= 16384.  Under id 2 all three entry points return CC_ERR_UNSUPPORTED for anything else (the
+ * pair form; every K <= 4096; cc_w12_pack, which does not see the form, for such a K).  The kernel keeps small RB x CU tiles of codes
+ * in two register sets and requests the tile after the current one (record first) before it decodes the current one, also across
+ * the end of a row group; records have the format above and are laid out for that (RB, CU) — cc_w12_geometry(..., swiglu = 2 << 8)
+ * gives it, with out[2] = 8 and out[4] = 1 where the class measured faster than cc_gemv_fused AND than id 1's launch, with a full
+ * grid (seven column steps per wave, e.g. 4096 x 14336, and four, K = 8192).  A copy packed under id 1 is refused under id 2 and
+ * the other way round (the records differ). */
 int cc_w12_geometry(int32_t N, int32_t K, int32_t swiglu, int32_t* out);
 size_t cc_w12_meta_words(void);
 int cc_w12_pack(const void* W, int32_t N, int32_t K, int32_t rb, int32_t cu, void* codes, void* records, void* meta,

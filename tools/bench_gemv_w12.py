@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
-"""cc_gemv_fused_w12 (the lossless 12-bit packed copy of dense bf16 weights) in its two code layouts — the first one ("w12") and the
-planar one — against cc_gemv_fused on the same weights in ONE session, at the Llama-3-8B decode shapes and the LM head, in the fused
+"""cc_gemv_fused_w12 (the lossless 12-bit packed copy of dense bf16 weights) in its three layouts — the first one ("w12"), the
+planar one and, where it serves the shape (plain, 4096 < K <= 16384), the long-row launch over planar codes ("long", layout id 2) —
+against cc_gemv_fused on the same weights in ONE session, at the Llama-3-8B decode shapes and the LM head, in the fused
 forms the decode loop launches (wqkv: norm + RoPE; w1/w3: norm + SwiGLU pair; LM head: final norm).  Rotates over enough distinct
-weight copies to exceed the 256 MB Infinity Cache; hipGraph replays, HIP events, median of 10, the three kernels alternating three
-times.  Outputs are compared bit for bit.  One JSON line per shape.  Both packed kernels are forced for every shape here; the
-harness uses one only where `on_by_default` / `planar_on_by_default` say it measured faster.  `planar_wins`: the rule those defaults
+weight copies to exceed the 256 MB Infinity Cache; hipGraph replays, HIP events, median of 10, the kernels alternating three
+times.  Outputs are compared bit for bit.  One JSON line per shape.  The packed kernels are forced for every shape here; the
+harness uses one only where `on_by_default` / `planar_on_by_default` / `long_on_by_default` say it measured faster.  `long_wins`:
+the same rule for layout 2, against the dense kernel and planar.  `planar_wins`: the rule those defaults
 follow — planar's best beats the best of the dense kernel AND of the first layout by more than `bf16_spread_us`, the dense kernel's
 own min-to-max spread over this session's repeats.
     python tools/bench_gemv_w12.py [shape ...]      (CC_GEMV_W12_CFG="RB,CU[,workgroups]" overrides the packed launch geometry;
-                                                     the 70B shapes w1w3_70b and lm_head_70b run only when named)"""
+                                                     the K = 8192 shapes w1w3_70b, lm_head_70b and square_8k run only when named)"""
 import json
 import os
 import sys
@@ -21,17 +23,18 @@ from bench_gemv import timed  # noqa: E402
 
 dev = "cuda"
 REPEATS = 3
-MODES = {"bf16": False, "w12": "force", "planar": "force-planar"}
+MODES = {"bf16": False, "w12": "force", "planar": "force-planar", "long": "force-long"}
+LAYOUTS = (("w12", 0), ("planar", glue.W12_PLANAR), ("long", glue.W12_LONG))
 
 
 def main():
     torch.manual_seed(0)
     shapes = {"wqkv": (6144, 4096), "wo": (4096, 4096), "w1w3": (14336, 4096), "w2": (4096, 14336), "lm_head": (128256, 4096),
-              "w1w3_70b": (28672, 8192), "lm_head_70b": (128256, 8192)}
+              "w1w3_70b": (28672, 8192), "lm_head_70b": (128256, 8192), "square_8k": (8192, 8192)}
     only = sys.argv[1:]
     bf = torch.bfloat16
     for name, (N, K) in shapes.items():
-        if (only and name not in only) or (not only and name.endswith("_70b")):
+        if (only and name not in only) or (not only and name.endswith(("_70b", "_8k"))):
             continue
         pair = name.startswith("w1w3")
         nmat = 2 if pair else 1
@@ -52,7 +55,7 @@ def main():
         def run(i, mode):
             return glue.gemv_fused(W[i % ncopy][0], x, w3=W[i % ncopy][1] if pair else None, w12=MODES[mode], **kw)
 
-        pk = {m: glue._w12_get(W[0][0], pair, True, lay) for m, lay in (("w12", 0), ("planar", glue.W12_PLANAR))}
+        pk = {m: glue._w12_get(W[0][0], pair, True, lay) for m, lay in LAYOUTS}
         same = {m: pk[m] is not None for m in pk}
         for i in range(ncopy):  # packs every copy eagerly (nothing is packed under capture) and checks the bits
             ref = run(i, "bf16").view(torch.int16)
@@ -65,7 +68,7 @@ def main():
                     ts[m].append(timed(lambda i: run(i, m), max(ncopy, 8)))
         best = {m: (min(t) if t else None) for m, t in ts.items()}
         spread = max(ts["bf16"]) - min(ts["bf16"])
-        geo = {m: glue.w12_geometry(N, K, pair, lay) for m, lay in (("w12", 0), ("planar", glue.W12_PLANAR))}
+        geo = {m: glue.w12_geometry(N, K, pair, lay) for m, lay in LAYOUTS}
         res = {"shape": name, "N": N, "K": K, "matrices": nmat, "MB_bf16": round(nbytes16 / 1e6, 1), "MB_w12": round(nbytes16 * 0.75 / 1e6, 1),
                "copies": ncopy, "bf16_spread_us": round(spread, 3), "cfg_env": os.environ.get("CC_GEMV_W12_CFG")}
         for m in MODES:
@@ -81,8 +84,11 @@ def main():
                 res[m + "_pack"] = dict(base=pk[m].base, records=pk[m].n_records, overflow=pk[m].n_overflow, escapes=pk[m].n_escapes)
         others = [best[m] for m in ("bf16", "w12") if best[m] is not None]
         res["planar_wins"] = bool(best["planar"] is not None and best["planar"] < min(others) - spread)
+        others = [best[m] for m in ("bf16", "planar") if best[m] is not None]
+        res["long_wins"] = bool(best["long"] is not None and best["long"] < min(others) - spread)
         res["on_by_default"] = bool(geo["w12"] and geo["w12"][4])
         res["planar_on_by_default"] = bool(geo["planar"] and geo["planar"][4])
+        res["long_on_by_default"] = bool(geo["long"] and geo["long"][4])
         print(json.dumps(res), flush=True)
         del W
         glue.w12_cache_clear()
