@@ -70,6 +70,8 @@ SIGNATURES = {
     "cc_sample_topk": (C.c_int, [_vp, _i32, _i32, _f32, _i32, C.c_uint64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "cc_sample_nucleus_workspace_bytes": (_sz, []),
     "cc_sample_nucleus": (C.c_int, [_vp, _i32, _i32, _f32, _i32, _f32, _f32, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "cc_sample_rows_workspace_bytes": (_sz, [_i32]),
+    "cc_sample_rows": (C.c_int, [_vp, _i32, _i32, C.c_int64, _i32, _f32, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "cc_logprob_rows_workspace_bytes": (_sz, []),
     "cc_logprob_rows": (C.c_int, [_vp, _i32, _i32, C.c_int64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "cc_logprob_topn_workspace_bytes": (_sz, []),
@@ -208,6 +210,7 @@ DEVICE_ONLY = {"cc_error_string", "cc_device_info", "cc_decode_step_single_launc
                "cc_gemv_fused_w8_multi", "cc_gemv_fused_mx4_multi",
                "cc_sample_topk_workspace_bytes", "cc_sample_topk",  # sampling tail: its checker is the numpy twin of the contract (tests/sample_twin.py)
                "cc_sample_nucleus_workspace_bytes", "cc_sample_nucleus",  # top-p / min-p on the same tail: likewise (tests/sample_nucleus_twin.py)
+               "cc_sample_rows_workspace_bytes", "cc_sample_rows",  # the same tail for up to 8 rows: its checker is cc_sample_nucleus itself, row by row, bit for bit
                "cc_logprob_rows_workspace_bytes", "cc_logprob_rows",  # per-token log-probabilities: float64 torch.log_softmax and the fp32 twin of the contract (tests/logprob_twin.py)
                "cc_logprob_topn_workspace_bytes", "cc_logprob_topn",  # the N best alternatives of a row: the float64 order and values (tests/logprob_topn_twin.py)
                "cc_token_counts_add", "cc_logits_penalize",  # token-history penalties: the fp32 torch twin of the contract (tests/penalty_twin.py)

@@ -28,6 +28,21 @@ struct SpWs {  // caller-provided scratch (cc_sample_topk_workspace_bytes); noth
   unsigned int prefix[4], krem[4];  // after pass P: the digits chosen so far, and the rank of the pivot among the elements that match them
 };
 
+// Rows (cc_sample_rows): every kernel runs on a (kSpBlocks, T) grid and blockIdx.y is the row: its logits at row * row_stride, its
+// probs at row * V, its token / kept count / position at [row], its seed from the by-value array, its workspace record at
+// row * ws_stride BYTES (sizeof(SpWs) or sizeof(SpNucWs): the record type of the entry point that was called).  Nothing else in a
+// kernel looks at blockIdx.y or at T, so a row's arithmetic is the single-row launch's; the single-row entry points are T = 1.
+struct SpSeeds {
+  unsigned long long s[CC_SAMPLE_MAX_ROWS];
+};
+template <typename T>
+__device__ __forceinline__ const T* sp_row_logits(const T* logits, long long row_stride) {
+  return logits + (size_t)blockIdx.y * (size_t)row_stride;
+}
+__device__ __forceinline__ SpWs* sp_row_ws(SpWs* ws, size_t ws_stride) {
+  return reinterpret_cast<SpWs*>(reinterpret_cast<char*>(ws) + (size_t)blockIdx.y * ws_stride);
+}
+
 template <typename T>
 __device__ __forceinline__ float sp_exp(float x) {  // cc_softmax_argmax's accuracy class (cc_glue.hip, sm_exp)
   if constexpr (sizeof(T) == 4) return expf(x);
@@ -115,8 +130,11 @@ __device__ __forceinline__ void sp_fold(SpWs* ws, int P, int k, unsigned int* s_
 
 // select pass P (k > 0), and for P == 0 the per-workgroup maxima (k == 0: those alone)
 template <typename T, int P>
-__global__ __launch_bounds__(kSpThreads) void sample_hist_kernel(const T* logits, int V, float tmax, int k, SpWs* ws) {
+__global__ __launch_bounds__(kSpThreads) void sample_hist_kernel(const T* logits, long long row_stride, int V, float tmax, int k, SpWs* ws,
+                                                                 size_t ws_stride) {
   constexpr int NB = SpKey<T>::NB;
+  logits = sp_row_logits(logits, row_stride);
+  ws = sp_row_ws(ws, ws_stride);
   __shared__ unsigned int sh[256];
   __shared__ unsigned int s_w[kSpWaves + 2];
   __shared__ float s_f[kSpWaves];
@@ -169,11 +187,15 @@ __device__ __forceinline__ float sp_gumbel_key(float d, uint64_t seed, int32_t p
 }
 
 template <typename T, int NP>  // NP: select passes that ran (0: everything is kept)
-__global__ __launch_bounds__(kSpThreads) void sample_draw_kernel(const T* logits, int V, float tmax, int k, unsigned long long seed,
-                                                                 const int32_t* input_pos, SpWs* ws) {
+__global__ __launch_bounds__(kSpThreads) void sample_draw_kernel(const T* logits, long long row_stride, int V, float tmax, int k, SpSeeds seeds,
+                                                                 const int32_t* input_pos, SpWs* ws, size_t ws_stride) {
   __shared__ unsigned int s_w[kSpWaves + 2];
   __shared__ float s_f[kSpWaves];
   __shared__ unsigned long long s_k[kSpWaves + 1];
+  logits = sp_row_logits(logits, row_stride);
+  ws = sp_row_ws(ws, ws_stride);
+  input_pos += blockIdx.y;
+  const unsigned long long seed = seeds.s[blockIdx.y];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int lo, hi;
   sp_slice(V, lo, hi);
@@ -207,9 +229,14 @@ __global__ __launch_bounds__(kSpThreads) void sample_draw_kernel(const T* logits
 }
 
 template <typename T, int NP>
-__global__ __launch_bounds__(kSpThreads) void sample_write_kernel(const T* logits, int V, float tmax, T* probs, int32_t* idx_out, SpWs* ws) {
+__global__ __launch_bounds__(kSpThreads) void sample_write_kernel(const T* logits, long long row_stride, int V, float tmax, T* probs,
+                                                                  int32_t* idx_out, SpWs* ws, size_t ws_stride) {
   __shared__ float s_f[kSpWaves];
   __shared__ float s_sum;
+  logits = sp_row_logits(logits, row_stride);
+  ws = sp_row_ws(ws, ws_stride);
+  probs += (size_t)blockIdx.y * (size_t)V;
+  idx_out += blockIdx.y;
   int lo, hi;
   sp_slice(V, lo, hi);
   const float m = sp_fold_max(ws, s_f);
@@ -242,25 +269,25 @@ __global__ __launch_bounds__(kSpThreads) void sample_write_kernel(const T* logit
 }
 
 template <typename T>
-void sp_launch(const void* logits_, int V, float tmax, int k, unsigned long long seed, const int32_t* input_pos, void* probs_, int32_t* idx_out,
-               SpWs* ws, hipStream_t st) {
+void sp_launch(const void* logits_, int rows, long long rs, int V, float tmax, int k, const SpSeeds& seeds, const int32_t* input_pos,
+               void* probs_, int32_t* idx_out, SpWs* ws, size_t wss, hipStream_t st) {
   const T* logits = (const T*)logits_;
   T* probs = (T*)probs_;
-  dim3 grid(kSpBlocks), block(kSpThreads);
-  hipLaunchKernelGGL((sample_hist_kernel<T, 0>), grid, block, 0, st, logits, V, tmax, k, ws);
+  dim3 grid(kSpBlocks, rows), block(kSpThreads);
+  hipLaunchKernelGGL((sample_hist_kernel<T, 0>), grid, block, 0, st, logits, rs, V, tmax, k, ws, wss);
   if (k <= 0) {
-    hipLaunchKernelGGL((sample_draw_kernel<T, 0>), grid, block, 0, st, logits, V, tmax, k, seed, input_pos, ws);
-    hipLaunchKernelGGL((sample_write_kernel<T, 0>), grid, block, 0, st, logits, V, tmax, probs, idx_out, ws);
+    hipLaunchKernelGGL((sample_draw_kernel<T, 0>), grid, block, 0, st, logits, rs, V, tmax, k, seeds, input_pos, ws, wss);
+    hipLaunchKernelGGL((sample_write_kernel<T, 0>), grid, block, 0, st, logits, rs, V, tmax, probs, idx_out, ws, wss);
     return;
   }
-  hipLaunchKernelGGL((sample_hist_kernel<T, 1>), grid, block, 0, st, logits, V, tmax, k, ws);
+  hipLaunchKernelGGL((sample_hist_kernel<T, 1>), grid, block, 0, st, logits, rs, V, tmax, k, ws, wss);
   constexpr int NP = SpKey<T>::NB / 8;
   if constexpr (NP == 4) {
-    hipLaunchKernelGGL((sample_hist_kernel<T, 2>), grid, block, 0, st, logits, V, tmax, k, ws);
-    hipLaunchKernelGGL((sample_hist_kernel<T, 3>), grid, block, 0, st, logits, V, tmax, k, ws);
+    hipLaunchKernelGGL((sample_hist_kernel<T, 2>), grid, block, 0, st, logits, rs, V, tmax, k, ws, wss);
+    hipLaunchKernelGGL((sample_hist_kernel<T, 3>), grid, block, 0, st, logits, rs, V, tmax, k, ws, wss);
   }
-  hipLaunchKernelGGL((sample_draw_kernel<T, NP>), grid, block, 0, st, logits, V, tmax, k, seed, input_pos, ws);
-  hipLaunchKernelGGL((sample_write_kernel<T, NP>), grid, block, 0, st, logits, V, tmax, probs, idx_out, ws);
+  hipLaunchKernelGGL((sample_draw_kernel<T, NP>), grid, block, 0, st, logits, rs, V, tmax, k, seeds, input_pos, ws, wss);
+  hipLaunchKernelGGL((sample_write_kernel<T, NP>), grid, block, 0, st, logits, rs, V, tmax, probs, idx_out, ws, wss);
 }
 
 // ---- top-p / min-p (cc_sample_nucleus): a second radix select over the same key, after the top-k one, whose bins hold 64-bit masses
@@ -328,12 +355,15 @@ __device__ __forceinline__ uint32_t sp_fold_mass(SpNucWs* nws, int Q, float top_
 
 // nucleus pass Q over K = the top-k kept set without NaNs (NPK: top-k select passes that ran; pass 0 folds the last of them)
 template <typename T, int NPK, int Q>
-__global__ __launch_bounds__(kSpThreads) void sample_mass_kernel(const T* logits, int V, float tmax, int k, float top_p, SpNucWs* nws) {
+__global__ __launch_bounds__(kSpThreads) void sample_mass_kernel(const T* logits, long long row_stride, int V, float tmax, int k, float top_p,
+                                                                 SpNucWs* nws) {
   constexpr int NB = SpKey<T>::NB;
   __shared__ unsigned long long shm[256];
   __shared__ unsigned long long s_m[kSpWaves + 1];
   __shared__ unsigned int s_w[kSpWaves + 2];
   __shared__ float s_f[kSpWaves];
+  logits = sp_row_logits(logits, row_stride);
+  nws += blockIdx.y;
   SpWs* ws = &nws->base;
   int lo, hi;
   sp_slice(V, lo, hi);
@@ -364,12 +394,17 @@ __global__ __launch_bounds__(kSpThreads) void sample_mass_kernel(const T* logits
 
 // the draw launch with the two filters (NPQ: nucleus passes that ran; 0: top-p is off) and the per-workgroup count of kept elements
 template <typename T, int NPK, int NPQ>
-__global__ __launch_bounds__(kSpThreads) void sample_draw_nucleus_kernel(const T* logits, int V, float tmax, int k, float top_p, float dmin,
-                                                                         unsigned long long seed, const int32_t* input_pos, SpNucWs* nws) {
+__global__ __launch_bounds__(kSpThreads) void sample_draw_nucleus_kernel(const T* logits, long long row_stride, int V, float tmax, int k,
+                                                                         float top_p, float dmin, SpSeeds seeds, const int32_t* input_pos,
+                                                                         SpNucWs* nws) {
   __shared__ unsigned int s_w[kSpWaves + 2];
   __shared__ float s_f[kSpWaves];
   __shared__ unsigned long long s_k[kSpWaves + 1];
   __shared__ unsigned int s_c[kSpWaves];
+  logits = sp_row_logits(logits, row_stride);
+  nws += blockIdx.y;
+  input_pos += blockIdx.y;
+  const unsigned long long seed = seeds.s[blockIdx.y];
   SpWs* ws = &nws->base;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int lo, hi;
@@ -420,10 +455,15 @@ __global__ __launch_bounds__(kSpThreads) void sample_draw_nucleus_kernel(const T
 }
 
 template <typename T, int NPK, int NPQ>
-__global__ __launch_bounds__(kSpThreads) void sample_write_nucleus_kernel(const T* logits, int V, float tmax, float dmin, T* probs,
-                                                                          int32_t* idx_out, int32_t* n_kept_out, SpNucWs* nws) {
+__global__ __launch_bounds__(kSpThreads) void sample_write_nucleus_kernel(const T* logits, long long row_stride, int V, float tmax, float dmin,
+                                                                          T* probs, int32_t* idx_out, int32_t* n_kept_out, SpNucWs* nws) {
   __shared__ float s_f[kSpWaves];
   __shared__ float s_sum;
+  logits = sp_row_logits(logits, row_stride);
+  nws += blockIdx.y;
+  probs += (size_t)blockIdx.y * (size_t)V;
+  idx_out += blockIdx.y;
+  if (n_kept_out) n_kept_out += blockIdx.y;
   SpWs* ws = &nws->base;
   int lo, hi;
   sp_slice(V, lo, hi);
@@ -465,44 +505,95 @@ __global__ __launch_bounds__(kSpThreads) void sample_write_nucleus_kernel(const 
   }
 }
 
+struct SpnArgs {  // one call's rows and settings, as the launch helpers pass them on
+  int rows;
+  long long rs;
+  int V;
+  float tmax;
+  int k;
+  bool with_p;
+  float top_p, dmin;
+  SpSeeds seeds;
+  const int32_t* input_pos;
+  int32_t *idx_out, *n_kept_out;
+  SpNucWs* nws;
+  hipStream_t st;
+};
+
 template <typename T, int NPK>
-void spn_tail(const T* logits, int V, float tmax, int k, bool with_p, float top_p, float dmin, unsigned long long seed, const int32_t* input_pos,
-              T* probs, int32_t* idx_out, int32_t* n_kept_out, SpNucWs* nws, hipStream_t st) {
+void spn_tail(const T* logits, T* probs, const SpnArgs& a) {
   constexpr int NP = SpKey<T>::NB / 8;
-  dim3 grid(kSpBlocks), block(kSpThreads);
-  if (!with_p) {
-    hipLaunchKernelGGL((sample_draw_nucleus_kernel<T, NPK, 0>), grid, block, 0, st, logits, V, tmax, k, top_p, dmin, seed, input_pos, nws);
-    hipLaunchKernelGGL((sample_write_nucleus_kernel<T, NPK, 0>), grid, block, 0, st, logits, V, tmax, dmin, probs, idx_out, n_kept_out, nws);
+  dim3 grid(kSpBlocks, a.rows), block(kSpThreads);
+  if (!a.with_p) {
+    hipLaunchKernelGGL((sample_draw_nucleus_kernel<T, NPK, 0>), grid, block, 0, a.st, logits, a.rs, a.V, a.tmax, a.k, a.top_p, a.dmin, a.seeds,
+                       a.input_pos, a.nws);
+    hipLaunchKernelGGL((sample_write_nucleus_kernel<T, NPK, 0>), grid, block, 0, a.st, logits, a.rs, a.V, a.tmax, a.dmin, probs, a.idx_out,
+                       a.n_kept_out, a.nws);
     return;
   }
-  hipLaunchKernelGGL((sample_mass_kernel<T, NPK, 0>), grid, block, 0, st, logits, V, tmax, k, top_p, nws);
-  hipLaunchKernelGGL((sample_mass_kernel<T, NPK, 1>), grid, block, 0, st, logits, V, tmax, k, top_p, nws);
+  hipLaunchKernelGGL((sample_mass_kernel<T, NPK, 0>), grid, block, 0, a.st, logits, a.rs, a.V, a.tmax, a.k, a.top_p, a.nws);
+  hipLaunchKernelGGL((sample_mass_kernel<T, NPK, 1>), grid, block, 0, a.st, logits, a.rs, a.V, a.tmax, a.k, a.top_p, a.nws);
   if constexpr (NP == 4) {
-    hipLaunchKernelGGL((sample_mass_kernel<T, NPK, 2>), grid, block, 0, st, logits, V, tmax, k, top_p, nws);
-    hipLaunchKernelGGL((sample_mass_kernel<T, NPK, 3>), grid, block, 0, st, logits, V, tmax, k, top_p, nws);
+    hipLaunchKernelGGL((sample_mass_kernel<T, NPK, 2>), grid, block, 0, a.st, logits, a.rs, a.V, a.tmax, a.k, a.top_p, a.nws);
+    hipLaunchKernelGGL((sample_mass_kernel<T, NPK, 3>), grid, block, 0, a.st, logits, a.rs, a.V, a.tmax, a.k, a.top_p, a.nws);
   }
-  hipLaunchKernelGGL((sample_draw_nucleus_kernel<T, NPK, NP>), grid, block, 0, st, logits, V, tmax, k, top_p, dmin, seed, input_pos, nws);
-  hipLaunchKernelGGL((sample_write_nucleus_kernel<T, NPK, NP>), grid, block, 0, st, logits, V, tmax, dmin, probs, idx_out, n_kept_out, nws);
+  hipLaunchKernelGGL((sample_draw_nucleus_kernel<T, NPK, NP>), grid, block, 0, a.st, logits, a.rs, a.V, a.tmax, a.k, a.top_p, a.dmin, a.seeds,
+                     a.input_pos, a.nws);
+  hipLaunchKernelGGL((sample_write_nucleus_kernel<T, NPK, NP>), grid, block, 0, a.st, logits, a.rs, a.V, a.tmax, a.dmin, probs, a.idx_out,
+                     a.n_kept_out, a.nws);
 }
 
 template <typename T>
-void spn_launch(const void* logits_, int V, float tmax, int k, bool with_p, float top_p, float dmin, unsigned long long seed,
-                const int32_t* input_pos, void* probs_, int32_t* idx_out, int32_t* n_kept_out, SpNucWs* nws, hipStream_t st) {
+void spn_launch(const void* logits_, void* probs_, const SpnArgs& a) {
   const T* logits = (const T*)logits_;
   T* probs = (T*)probs_;
   constexpr int NP = SpKey<T>::NB / 8;
-  dim3 grid(kSpBlocks), block(kSpThreads);
-  hipLaunchKernelGGL((sample_hist_kernel<T, 0>), grid, block, 0, st, logits, V, tmax, k, &nws->base);  // (k == 0: the maxima alone)
-  if (k <= 0) {
-    spn_tail<T, 0>(logits, V, tmax, k, with_p, top_p, dmin, seed, input_pos, probs, idx_out, n_kept_out, nws, st);
+  constexpr size_t wss = sizeof(SpNucWs);
+  dim3 grid(kSpBlocks, a.rows), block(kSpThreads);
+  hipLaunchKernelGGL((sample_hist_kernel<T, 0>), grid, block, 0, a.st, logits, a.rs, a.V, a.tmax, a.k, &a.nws->base, wss);  // (k == 0: the maxima alone)
+  if (a.k <= 0) {
+    spn_tail<T, 0>(logits, probs, a);
     return;
   }
-  hipLaunchKernelGGL((sample_hist_kernel<T, 1>), grid, block, 0, st, logits, V, tmax, k, &nws->base);
+  hipLaunchKernelGGL((sample_hist_kernel<T, 1>), grid, block, 0, a.st, logits, a.rs, a.V, a.tmax, a.k, &a.nws->base, wss);
   if constexpr (NP == 4) {
-    hipLaunchKernelGGL((sample_hist_kernel<T, 2>), grid, block, 0, st, logits, V, tmax, k, &nws->base);
-    hipLaunchKernelGGL((sample_hist_kernel<T, 3>), grid, block, 0, st, logits, V, tmax, k, &nws->base);
+    hipLaunchKernelGGL((sample_hist_kernel<T, 2>), grid, block, 0, a.st, logits, a.rs, a.V, a.tmax, a.k, &a.nws->base, wss);
+    hipLaunchKernelGGL((sample_hist_kernel<T, 3>), grid, block, 0, a.st, logits, a.rs, a.V, a.tmax, a.k, &a.nws->base, wss);
   }
-  spn_tail<T, NP>(logits, V, tmax, k, with_p, top_p, dmin, seed, input_pos, probs, idx_out, n_kept_out, nws, st);
+  spn_tail<T, NP>(logits, probs, a);
+}
+
+// cc_sample_nucleus's value refusals and its launches for `rows` rows whose workspace records are SpNucWs (both entry points)
+int spn_rows(const void* logits, int rows, int V, long long rs, int dtype, float temperature, int top_k, float top_p, float min_p,
+             const SpSeeds& seeds, const int32_t* input_pos, void* probs, int32_t* idx_out, int32_t* n_kept_out, void* workspace,
+             size_t workspace_bytes, hipStream_t st) {
+  if (!logits || !probs || !idx_out || !input_pos || !workspace || V <= 0 || !cc_dt_ok(dtype) || !(temperature > 0.f)) return CC_ERR_BAD_ARG;
+  if (!(top_p > 0.f) || !(min_p <= 1.f)) return CC_ERR_BAD_ARG;  // (NaN fails both comparisons)
+  const bool with_p = top_p < 1.f, with_min = min_p > 0.f;
+  if (with_p && V > CC_SAMPLE_NUCLEUS_MAX_V) return CC_ERR_BAD_ARG;
+  if (workspace_bytes < (size_t)rows * sizeof(SpNucWs)) return CC_ERR_WORKSPACE;
+  if (((uintptr_t)workspace & 7u) != 0) return CC_ERR_BAD_ARG;
+  SpNucWs* nws = reinterpret_cast<SpNucWs*>(workspace);
+  const float tmax = temperature > 1e-5f ? temperature : 1e-5f;
+  const int k = (top_k <= 0 || top_k >= V) ? 0 : top_k;
+  if (!with_p && !with_min && !n_kept_out) {  // both filters off: cc_sample_topk's own launches
+    switch (dtype) {
+      case CC_DT_F32: sp_launch<float>(logits, rows, rs, V, tmax, k, seeds, input_pos, probs, idx_out, &nws->base, sizeof(SpNucWs), st); break;
+      case CC_DT_BF16: sp_launch<bf16_t>(logits, rows, rs, V, tmax, k, seeds, input_pos, probs, idx_out, &nws->base, sizeof(SpNucWs), st); break;
+      default: sp_launch<f16_t>(logits, rows, rs, V, tmax, k, seeds, input_pos, probs, idx_out, &nws->base, sizeof(SpNucWs), st); break;
+    }
+    CC_LAUNCH_CHECK();
+    return CC_OK;
+  }
+  const float dmin = with_min ? (float)log((double)min_p) : -INFINITY;
+  const SpnArgs a{rows, rs, V, tmax, k, with_p, top_p, dmin, seeds, input_pos, idx_out, n_kept_out, nws, st};
+  switch (dtype) {
+    case CC_DT_F32: spn_launch<float>(logits, probs, a); break;
+    case CC_DT_BF16: spn_launch<bf16_t>(logits, probs, a); break;
+    default: spn_launch<f16_t>(logits, probs, a); break;
+  }
+  CC_LAUNCH_CHECK();
+  return CC_OK;
 }
 }  // namespace
 
@@ -519,10 +610,12 @@ extern "C" int cc_sample_topk(const void* logits, int32_t V, int32_t dtype, floa
   SpWs* ws = reinterpret_cast<SpWs*>(workspace);
   const float tmax = temperature > 1e-5f ? temperature : 1e-5f;
   const int k = (top_k <= 0 || top_k >= V) ? 0 : top_k;  // k = min(top_k, V) = V keeps everything, as no top_k does
+  SpSeeds seeds{};
+  seeds.s[0] = seed;
   switch (dtype) {
-    case CC_DT_F32: sp_launch<float>(logits, V, tmax, k, seed, input_pos, probs, idx_out, ws, st); break;
-    case CC_DT_BF16: sp_launch<bf16_t>(logits, V, tmax, k, seed, input_pos, probs, idx_out, ws, st); break;
-    default: sp_launch<f16_t>(logits, V, tmax, k, seed, input_pos, probs, idx_out, ws, st); break;
+    case CC_DT_F32: sp_launch<float>(logits, 1, V, V, tmax, k, seeds, input_pos, probs, idx_out, ws, sizeof(SpWs), st); break;
+    case CC_DT_BF16: sp_launch<bf16_t>(logits, 1, V, V, tmax, k, seeds, input_pos, probs, idx_out, ws, sizeof(SpWs), st); break;
+    default: sp_launch<f16_t>(logits, 1, V, V, tmax, k, seeds, input_pos, probs, idx_out, ws, sizeof(SpWs), st); break;
   }
   CC_LAUNCH_CHECK();
   return CC_OK;
@@ -534,31 +627,22 @@ extern "C" int cc_sample_nucleus(const void* logits, int32_t V, int32_t dtype, f
                                  uint64_t seed, const int32_t* input_pos, void* probs, int32_t* idx_out, int32_t* n_kept_out,
                                  void* workspace, size_t workspace_bytes, cc_stream_t stream) {
   CC_ENTRY();
-  if (!logits || !probs || !idx_out || !input_pos || !workspace || V <= 0 || !cc_dt_ok(dtype) || !(temperature > 0.f)) return CC_ERR_BAD_ARG;
-  if (!(top_p > 0.f) || !(min_p <= 1.f)) return CC_ERR_BAD_ARG;  // (NaN fails both comparisons)
-  const bool with_p = top_p < 1.f, with_min = min_p > 0.f;
-  if (with_p && V > CC_SAMPLE_NUCLEUS_MAX_V) return CC_ERR_BAD_ARG;
-  if (workspace_bytes < sizeof(SpNucWs)) return CC_ERR_WORKSPACE;
-  if (((uintptr_t)workspace & 7u) != 0) return CC_ERR_BAD_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  SpNucWs* nws = reinterpret_cast<SpNucWs*>(workspace);
-  const float tmax = temperature > 1e-5f ? temperature : 1e-5f;
-  const int k = (top_k <= 0 || top_k >= V) ? 0 : top_k;
-  if (!with_p && !with_min && !n_kept_out) {  // both filters off: cc_sample_topk's own launches
-    switch (dtype) {
-      case CC_DT_F32: sp_launch<float>(logits, V, tmax, k, seed, input_pos, probs, idx_out, &nws->base, st); break;
-      case CC_DT_BF16: sp_launch<bf16_t>(logits, V, tmax, k, seed, input_pos, probs, idx_out, &nws->base, st); break;
-      default: sp_launch<f16_t>(logits, V, tmax, k, seed, input_pos, probs, idx_out, &nws->base, st); break;
-    }
-    CC_LAUNCH_CHECK();
-    return CC_OK;
-  }
-  const float dmin = with_min ? (float)log((double)min_p) : -INFINITY;
-  switch (dtype) {
-    case CC_DT_F32: spn_launch<float>(logits, V, tmax, k, with_p, top_p, dmin, seed, input_pos, probs, idx_out, n_kept_out, nws, st); break;
-    case CC_DT_BF16: spn_launch<bf16_t>(logits, V, tmax, k, with_p, top_p, dmin, seed, input_pos, probs, idx_out, n_kept_out, nws, st); break;
-    default: spn_launch<f16_t>(logits, V, tmax, k, with_p, top_p, dmin, seed, input_pos, probs, idx_out, n_kept_out, nws, st); break;
-  }
-  CC_LAUNCH_CHECK();
-  return CC_OK;
+  SpSeeds seeds{};
+  seeds.s[0] = seed;
+  return spn_rows(logits, 1, V, V, dtype, temperature, top_k, top_p, min_p, seeds, input_pos, probs, idx_out, n_kept_out, workspace,
+                  workspace_bytes, (hipStream_t)stream);
 }
+
+extern "C" size_t cc_sample_rows_workspace_bytes(int32_t T) { return T < 1 || T > CC_SAMPLE_MAX_ROWS ? 0 : (size_t)T * sizeof(SpNucWs); }
+
+extern "C" int cc_sample_rows(const void* logits, int32_t T, int32_t V, int64_t row_stride, int32_t dtype, float temperature, int32_t top_k,
+                              float top_p, float min_p, const uint64_t* seeds, const int32_t* input_pos, void* probs, int32_t* idx_out,
+                              int32_t* n_kept_out, void* workspace, size_t workspace_bytes, cc_stream_t stream) {
+  CC_ENTRY();
+  if (T < 1 || T > CC_SAMPLE_MAX_ROWS || !seeds || row_stride < (int64_t)V) return CC_ERR_BAD_ARG;
+  SpSeeds sd{};
+  for (int r = 0; r < T; r++) sd.s[r] = seeds[r];  // by value: the caller's array is not read after the call returns
+  return spn_rows(logits, T, V, (long long)row_stride, dtype, temperature, top_k, top_p, min_p, sd, input_pos, probs, idx_out, n_kept_out,
+                  workspace, workspace_bytes, (hipStream_t)stream);
+}
+

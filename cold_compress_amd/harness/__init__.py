@@ -5,5 +5,6 @@ from .generation import (GraphedDecoder, TokenScores, TokenTopScores, apply_patt
 from .penalties import LogitPenalties  # noqa: F401
 from .constraints import LogitConstraints  # noqa: F401
 from .model import CONFIGS, ModelArgs, Transformer, find_multiple  # noqa: F401
+from .streams import DecodeStreams, GraphedStreamsDecoder, generate_streams  # noqa: F401
 from .quantize import (WeightOnlyInt4Linear, WeightOnlyInt4QuantHandler, WeightOnlyInt8Linear,  # noqa: F401
                        WeightOnlyInt8QuantHandler)

@@ -3,7 +3,7 @@
 These are NOT part of the cache/attention hot path — they are the model-side code around it
 (ref: model.py:317-327, 375-387, 442-443, 452-457, 507-519), which the reference leaves to ~45 eager elementwise
 launches per layer or to torch.compile.  On device tensors they call the C ABI (`cc_add_rmsnorm`, `cc_qkv_rope`,
-`cc_silu_mul`, `cc_gemv_fused`, `cc_gemv_fused_multi` and its int8 / MXFP4 forms, `cc_softmax_argmax`, `cc_sample_topk`, `cc_sample_nucleus`, `cc_logprob_rows`, `cc_logprob_topn`,
+`cc_silu_mul`, `cc_gemv_fused`, `cc_gemv_fused_multi` and its int8 / MXFP4 forms, `cc_softmax_argmax`, `cc_sample_topk`, `cc_sample_nucleus`, `cc_sample_rows`, `cc_logprob_rows`, `cc_logprob_topn`,
 `cc_token_counts_add`, `cc_logits_penalize`, `cc_token_history_write`, `cc_logits_constrain`); CPU tensors raise — there is no host path in the package (the
 CPU model-wiring test brings its own eager twins: tests/host_glue.py).
 """
@@ -447,6 +447,55 @@ def sample_nucleus(logits, temperature, top_k, top_p, min_p, seed, input_pos, re
 
 
 _SN_WS = {}
+
+SAMPLE_MAX_ROWS = 8  # CC_SAMPLE_MAX_ROWS (include/coldcompress.h)
+
+
+def sample_rows(logits_2d, temperature, top_k, top_p, min_p, seeds, input_pos, return_n_kept=False):
+    """sample_nucleus for the T rows of `logits_2d` [T, V] (T <= SAMPLE_MAX_ROWS) in the launches of one row (cc_sample_rows;
+    include/coldcompress.h has the contract): row r is drawn under seeds[r] at the position input_pos[r], and its probabilities, token
+    and kept count are the bits sample_nucleus gives for that row alone.  A view with a row stride is passed as it is, without a
+    copy.  seeds: T Python integers; input_pos: a contiguous int32 DEVICE tensor of T elements, read by the kernels (a captured
+    call advances through it).  -> (probs [T, V], idx [T] int32), and with `return_n_kept` an int32 tensor of T counts as a third."""
+    if not logits_2d.is_cuda:
+        _host(logits_2d, "sample_rows logits")
+    x = logits_2d
+    if x.dim() != 2 or x.dtype not in _DT or x.shape[0] < 1 or x.shape[1] < 1:
+        raise _abi.ColdCompressError(f"sample_rows: logits must be [T, V] in float32 / bfloat16 / float16, got {x.dtype} {tuple(x.shape)}")
+    T, V = x.shape
+    if T > SAMPLE_MAX_ROWS:
+        raise _abi.ColdCompressError(f"sample_rows: at most {SAMPLE_MAX_ROWS} rows per call, got {T}")
+    seeds = [int(s) & (2 ** 64 - 1) for s in seeds]
+    if len(seeds) != T:
+        raise _abi.ColdCompressError(f"sample_rows: {T} rows need {T} seeds, got {len(seeds)}")
+    if not (input_pos.is_cuda and input_pos.dtype == torch.int32 and input_pos.numel() == T and input_pos.is_contiguous()):
+        raise _abi.ColdCompressError(f"sample_rows: input_pos must be a contiguous int32 device tensor of {T} elements, got "
+                                     f"{input_pos.dtype} {tuple(input_pos.shape)} on {input_pos.device}")
+    if not float(temperature) > 0:
+        raise _abi.ColdCompressError(f"sample_rows: temperature must be > 0, got {temperature}")
+    p = 1.0 if top_p is None else float(top_p)
+    mp = 0.0 if min_p is None else float(min_p)
+    if not p > 0:
+        raise _abi.ColdCompressError(f"sample_rows: top_p must be > 0 (>= 1: off), got {top_p}")
+    if not mp <= 1:
+        raise _abi.ColdCompressError(f"sample_rows: min_p must be <= 1 (<= 0: off), got {min_p}")
+    if V > 1 and x.stride(1) != 1 or (T > 1 and x.stride(0) < V):
+        x = x.contiguous()
+    stride = x.stride(0) if T > 1 else V
+    probs = torch.empty((T, V), dtype=x.dtype, device=x.device)
+    idx = torch.empty((T,), dtype=torch.int32, device=x.device)
+    n_kept = torch.empty((T,), dtype=torch.int32, device=x.device) if return_n_kept else None
+    ws = _SR_WS.get(x.device)
+    if ws is None:  # (one buffer for every T: 6 MB; a captured call holds its address)
+        ws = _SR_WS[x.device] = torch.empty(int(_abi.lib()["cc_sample_rows_workspace_bytes"](SAMPLE_MAX_ROWS)), dtype=torch.uint8,
+                                            device=x.device)
+    k = 0 if top_k is None else max(0, min(int(top_k), 2 ** 31 - 1))
+    _abi.call("cc_sample_rows", _p(x), T, V, int(stride), _DT[x.dtype], float(temperature), k, p, mp, (C.c_uint64 * T)(*seeds), _p(input_pos),
+              _p(probs), _p(idx), _p(n_kept), _p(ws), ws.numel(), _stream())
+    return (probs, idx, n_kept) if return_n_kept else (probs, idx)
+
+
+_SR_WS = {}
 
 
 def logprob_rows(logits_2d, targets=None, fallback=None, want_rank=True):

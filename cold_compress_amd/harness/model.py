@@ -164,10 +164,11 @@ class Attention(nn.Module):
             return self.prompt_compressor(input_pos, k_val, v_val, attn=attn)
         return input_pos, k_val, v_val, attn
 
-    def decode_attend(self, q, k, v, input_ids, input_pos, attn_top_k=1.0):
+    def decode_attend(self, q, k, v, input_ids, input_pos, attn_top_k=1.0, cache=None):
         """One decode token's insert + attention + state update on q [1,HQ,1,D], k / v [1,H,1,D] -> y [1,HQ,1,D].  The ONE place
-        this sequence lives: forward() runs it for its token, TransformerBlock.forward_block for each token of a block in turn."""
-        cache = self.kv_cache
+        this sequence lives: forward() runs it for its token, TransformerBlock.forward_block for each token of a block in turn.
+        `cache` (default: the layer's own `kv_cache`): the cache that is stepped — another stream's (harness/streams.py)."""
+        cache = self.kv_cache if cache is None else cache
         ck = {"input_ids": input_ids}
         if (self.fuse_decode_step and type(cache) in (KVCacheHeavyHitter, KVCacheRecentGlobal, KVCacheFull, KVCacheRandom, KVCacheL2,
                                                       KVCacheHybrid)
@@ -260,18 +261,29 @@ class TransformerBlock(nn.Module):
         return bool(self.fuse_gemv and x.is_cuda
                     and glue.gemv_supported(att.wqkv.weight, att.wo.weight, ffn.w1.weight, ffn.w3.weight, ffn.w2.weight))
 
-    def forward_block(self, x, delta, input_ids, input_pos, freqs_cis, attn_top_k=1.0):
+    def forward_block(self, x, delta, input_ids, input_pos, freqs_cis, attn_top_k=1.0, caches=None):
         """forward() for T decode tokens whose inputs are all known: x, delta [1, T, dim], input_ids [1, T], input_pos [T],
         freqs_cis [T, D/2, 2] -> (h, f) like forward().  Every dense product is ONE pass over its weights for the T tokens
         (cc_gemv_fused_multi, or its int8 / MXFP4 form: row t bit-identical to the single-token launch); the T cache steps run one after the other through
         Attention.decode_attend, as the token-by-token loop runs them — layer l at token t needs layer l - 1 at token t and this
         layer's cache behind tokens < t, both of which exist in this order.  CPU tensors (tests/cpu_twin.py): forward() row by
-        row, a correctness twin."""
+        row, a correctness twin.  `caches` (default None: every row steps the layer's own cache): a list of T caches of this
+        layer, row t steps caches[t] — T independent sequences in lock-step (Transformer.forward_streams)."""
         att, ffn = self.attention, self.feed_forward
         T = x.shape[1]
+        if caches is not None and len(caches) != T:
+            raise ColdCompressError(f"forward_block: {T} rows need {T} caches, got {len(caches)}")
         if not x.is_cuda:
-            outs = [self.forward(x[:, t:t + 1], None if delta is None else delta[:, t:t + 1], input_ids[:, t:t + 1], input_pos[t:t + 1],
-                                 False, freqs_cis[t:t + 1], None, attn_top_k=attn_top_k) for t in range(T)]
+            own, outs = att.kv_cache, []
+            try:
+                for t in range(T):
+                    if caches is not None:
+                        att.kv_cache = caches[t]
+                    outs.append(self.forward(x[:, t:t + 1], None if delta is None else delta[:, t:t + 1], input_ids[:, t:t + 1],
+                                             input_pos[t:t + 1], False, freqs_cis[t:t + 1], None, attn_top_k=attn_top_k))
+            finally:
+                if caches is not None:
+                    att.kv_cache = own
             return torch.cat([o[0] for o in outs], 1), torch.cat([o[1] for o in outs], 1)
         if not self.device_fused(x):
             raise ColdCompressError("forward_block needs the device-fused decode branch (Transformer.block_eligible)")
@@ -285,7 +297,8 @@ class TransformerBlock(nn.Module):
         for t in range(T):
             row = qkv[t]
             ys.append(att.decode_attend(row[: HQ * D].view(1, HQ, 1, D), row[HQ * D: (HQ + H) * D].view(1, H, 1, D),
-                                        row[(HQ + H) * D:].view(1, H, 1, D), input_ids[:, t:t + 1], input_pos[t:t + 1], attn_top_k).view(1, -1))
+                                        row[(HQ + H) * D:].view(1, H, 1, D), input_ids[:, t:t + 1], input_pos[t:t + 1], attn_top_k,
+                                        cache=None if caches is None else caches[t]).view(1, -1))
         a = glue.gemv_fused_multi(att.wo.weight, torch.cat(ys), **_quant(att.wo))
         h2 = torch.empty_like(x2)
         g = glue.gemv_fused_multi(ffn.w1.weight, h1, w3=ffn.w3.weight, delta=a, norm_weight=self.ffn_norm.weight, eps=self.ffn_norm.eps,
@@ -332,6 +345,8 @@ class Transformer(nn.Module):
             if kwargs.get("cache_quant_mode") and "cache_bits" in relevant:  # our extension: the fused quantised cache
                 lk["cache_quant_mode"] = kwargs["cache_quant_mode"]
             b.attention.kv_cache = ctor(self.max_batch_size, self.config.n_local_heads, head_dim, dtype, **lk)
+            # what built it: further cache sets of the same classes and arguments (harness/streams.py, DecodeStreams)
+            b.attention.kv_cache_spec = (ctor, (self.max_batch_size, self.config.n_local_heads, head_dim, dtype), dict(lk))
             b.attention.prompt_compressor = get_prompt_compressor_constructor(
                 kwargs["prompt_compression_strategy"][i])(head_specific=b.attention.kv_cache.head_specific, **lk)
         self.freqs_cis = precompute_freqs_cis(self.config.block_size, head_dim, self.config.rope_base, dtype,
@@ -428,6 +443,46 @@ class Transformer(nn.Module):
         if not x.is_cuda:
             if self.batch_quant_flush:
                 flush_quantized([layer.attention.kv_cache for layer in self.layers])
+            return torch.cat([self.output(self.norm(x[:, t:t + 1], delta[:, t:t + 1])[1]) for t in range(T)], 1)
+        return glue.gemv_fused_multi(self.output.weight, x.view(T, -1), delta=delta.view(T, -1), norm_weight=self.norm.weight,
+                                     eps=self.norm.eps, **_quant(self.output)).view(1, T, -1)
+
+    def streams_eligible(self, streams, attn_top_k=1.0):
+        """block_eligible evaluated over every stream's caches (harness/streams.py, DecodeStreams): True when forward_streams
+        computes, from one pass over the weights, what every stream's own single-token step computes."""
+        from ..cache import KVCacheAnalysis
+
+        if not self.block_eligible(attn_top_k):
+            return False
+        for caches in streams.sets:
+            for layer, cache in zip(self.layers, caches):
+                if cache is None or isinstance(cache, KVCacheAnalysis) or (cache.quantize and not cache.fused_quant):
+                    return False
+        return True
+
+    def forward_streams(self, idx, input_pos, streams, attn_top_k=1.0) -> Tensor:
+        """One decode step of n independent sequences in lock-step: idx [1, n] (stream t's input token), input_pos [n] (stream t's
+        position: per stream and arbitrary), streams a DecodeStreams of n cache sets -> logits [1, n, V].  Row t equals
+        forward(idx[:, t:t+1], input_pos[t:t+1], is_prefill=False)'s with stream t active, bit for bit, and stream t's caches are
+        left as that call leaves them: every dense product is ONE pass over its weights for the n rows (forward_block's launches),
+        each stream's cache step is the single launch on that stream's own cache.  Device tensors need streams_eligible(); CPU
+        tensors (tests/cpu_twin.py) run the same order row by row."""
+        assert self.freqs_cis is not None, "Caches must be initialized first"
+        T = idx.shape[1]
+        if T != streams.n or input_pos.numel() != T:
+            raise ColdCompressError(f"forward_streams: {streams.n} streams need idx [1, {streams.n}] and {streams.n} positions, got "
+                                    f"{tuple(idx.shape)} and {tuple(input_pos.shape)}")
+        if idx.is_cuda and not (1 <= T <= glue.GEMV_MULTI_MAX_T and self.streams_eligible(streams, attn_top_k)):
+            raise ColdCompressError(f"forward_streams: {T} streams on a model that is not streams_eligible (or more than {glue.GEMV_MULTI_MAX_T})")
+        freqs_cis = self.freqs_cis[input_pos]
+        x, delta = self.tok_embeddings(idx), None
+        for li, layer in enumerate(self.layers):
+            x, delta = layer.forward_block(x, delta, idx, input_pos, freqs_cis, attn_top_k=attn_top_k,
+                                           caches=[streams.sets[t][li] for t in range(T)])
+        if not x.is_cuda:
+            if self.batch_quant_flush:
+                for caches in streams.sets:
+                    flush_quantized(list(caches))
             return torch.cat([self.output(self.norm(x[:, t:t + 1], delta[:, t:t + 1])[1]) for t in range(T)], 1)
         return glue.gemv_fused_multi(self.output.weight, x.view(T, -1), delta=delta.view(T, -1), norm_weight=self.norm.weight,
                                      eps=self.norm.eps, **_quant(self.output)).view(1, T, -1)

@@ -1005,6 +1005,25 @@ int cc_sample_nucleus(const void* logits, int32_t V, int32_t dtype, float temper
                       uint64_t seed, const int32_t* input_pos, void* probs, int32_t* idx_out, int32_t* n_kept_out,
                       void* workspace, size_t workspace_bytes, cc_stream_t stream);
 
+/* cc_sample_nucleus for T rows of logits (1 <= T <= CC_SAMPLE_MAX_ROWS) in the launches of ONE row: every kernel of the tail runs on
+ * a (128, T) grid whose second index is the row.  Row r starts at logits + r * row_stride ELEMENTS (row_stride >= V; any value, any
+ * alignment of a row's base: the kernels read and write element by element and bound every access by the row's own V), is drawn
+ * under seeds[r] at the position input_pos[r], and writes probs + r * V (T contiguous rows), idx_out[r] and, unless it is NULL,
+ * n_kept_out[r]: the bits cc_sample_nucleus writes for (logits + r * row_stride, V, dtype, temperature, top_k, top_p, min_p,
+ * seeds[r], input_pos + r), whatever T and whatever the other rows hold (a NaN in one row is that row's alone).  The settings are
+ * the call's, shared by the rows.  With both filters off and n_kept_out NULL the three (bf16 / f16) or five (fp32) launches of
+ * cc_sample_topk run, as in cc_sample_nucleus.  `seeds` is a HOST array of T values, copied before the call returns; `input_pos`
+ * is a DEVICE array of T positions, read by the kernels (a captured call advances through it).  Never synchronises, never
+ * allocates, stream-capturable; `workspace` (cc_sample_rows_workspace_bytes(T), 8-byte aligned: T records of cc_sample_nucleus's)
+ * needs no initialisation.  Refused before any launch: CC_ERR_BAD_ARG for T < 1, T > CC_SAMPLE_MAX_ROWS, row_stride < V, a NULL
+ * logits / seeds / input_pos / probs / idx_out / workspace and everything cc_sample_nucleus refuses; CC_ERR_WORKSPACE for a
+ * workspace shorter than cc_sample_rows_workspace_bytes(T) (which is 0 for a T out of range). */
+#define CC_SAMPLE_MAX_ROWS 8
+size_t cc_sample_rows_workspace_bytes(int32_t T);
+int cc_sample_rows(const void* logits, int32_t T, int32_t V, int64_t row_stride, int32_t dtype, float temperature, int32_t top_k,
+                   float top_p, float min_p, const uint64_t* seeds, const int32_t* input_pos, void* probs, int32_t* idx_out,
+                   int32_t* n_kept_out, void* workspace, size_t workspace_bytes, cc_stream_t stream);
+
 /* Per-token log-probabilities: what a perplexity evaluation reads from the logits (ref: eval.py:230-241 takes the log of a probability
  * row that generate() returned; this entry point returns the one number per token instead of the row).  logits: T rows of V elements
  * of the model dtype (`dtype`), row r at logits + r * row_stride elements, row_stride >= V — a [1, T, V] block of logits, a single row,
