@@ -93,6 +93,7 @@ SIGNATURES = {
     "cc_gemv_fused_mx4": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
     "cc_gemv_fused_w8_multi": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     "cc_gemv_fused_mx4_multi": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "cc_gemv_fused_w4_multi": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "cc_kv_requant": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "cc_kv_requant_pair": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
     "cc_kv_requant_batch": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
@@ -208,6 +209,7 @@ DEVICE_ONLY = {"cc_error_string", "cc_device_info", "cc_decode_step_single_launc
                "cc_gemv_fused_mx4",  # MXFP4 weight-only GEMV: likewise (and bit-exact known-answer cases)
                # the two for up to 4 input vectors: their checkers are cc_gemv_fused_w8 / cc_gemv_fused_mx4 themselves, row by row, bit for bit
                "cc_gemv_fused_w8_multi", "cc_gemv_fused_mx4_multi",
+               "cc_gemv_fused_w4_multi",  # the int4 one: its checker is cc_gemv_fused_w4 itself, row by row, bit for bit
                "cc_sample_topk_workspace_bytes", "cc_sample_topk",  # sampling tail: its checker is the numpy twin of the contract (tests/sample_twin.py)
                "cc_sample_nucleus_workspace_bytes", "cc_sample_nucleus",  # top-p / min-p on the same tail: likewise (tests/sample_nucleus_twin.py)
                "cc_sample_rows_workspace_bytes", "cc_sample_rows",  # the same tail for up to 8 rows: its checker is cc_sample_nucleus itself, row by row, bit for bit

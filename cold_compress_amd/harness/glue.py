@@ -3,7 +3,7 @@
 These are NOT part of the cache/attention hot path — they are the model-side code around it
 (ref: model.py:317-327, 375-387, 442-443, 452-457, 507-519), which the reference leaves to ~45 eager elementwise
 launches per layer or to torch.compile.  On device tensors they call the C ABI (`cc_add_rmsnorm`, `cc_qkv_rope`,
-`cc_silu_mul`, `cc_gemv_fused`, `cc_gemv_fused_multi` and its int8 / MXFP4 forms, `cc_softmax_argmax`, `cc_sample_topk`, `cc_sample_nucleus`, `cc_sample_rows`, `cc_logprob_rows`, `cc_logprob_topn`,
+`cc_silu_mul`, `cc_gemv_fused`, `cc_gemv_fused_multi` and its int8 / MXFP4 / int4 forms, `cc_softmax_argmax`, `cc_sample_topk`, `cc_sample_nucleus`, `cc_sample_rows`, `cc_logprob_rows`, `cc_logprob_topn`,
 `cc_token_counts_add`, `cc_logits_penalize`, `cc_token_history_write`, `cc_logits_constrain`); CPU tensors raise — there is no host path in the package (the
 CPU model-wiring test brings its own eager twins: tests/host_glue.py).
 """
@@ -312,8 +312,8 @@ def gemv_fused_multi(weight, x, w3=None, delta=None, norm_weight=None, eps=1e-5,
     likewise), freqs [T, head_dim / 2, 2] -> [T, N].  Row t is bit-identical to gemv_fused on row t.
     int8 `weight` (and `w3`) with per-row `scales` (`scales3`): cc_gemv_fused_w8_multi, bf16 or f16 activations.
     uint8 `weight` (and `w3`) with uint8 `scales` (`scales3`), the e8m0 block bytes [N, K / 32]: cc_gemv_fused_mx4_multi, bf16
-    activations.  The int4 GEMV (uint8 codes with bf16 (scale, zero) pairs) has no multi form: an error, not a fallback — callers
-    ask Transformer.block_eligible first."""
+    activations.  The int4 GEMV (uint8 codes with bf16 (scale, zero) pairs) has no multi form HERE: an error, not a fallback — its
+    multi form is gemv_fused_w4_multi below, which takes the groupsize; callers ask Transformer.block_eligible first."""
     if weight.dtype == torch.int8:
         if scales is None or (w3 is not None and (w3.dtype != torch.int8 or scales3 is None)):
             raise _abi.ColdCompressError("gemv_fused_multi: int8 weights need their per-row scales (and w3 int8 with scales3)")
@@ -371,6 +371,58 @@ def gemv_fused_multi(weight, x, w3=None, delta=None, norm_weight=None, eps=1e-5,
     y = torch.empty((T, N), dtype=weight.dtype, device=weight.device)
     _abi.call("cc_gemv_fused_multi", _p(weight), _p(w3), _p(xc), _p(dc), _p(norm_weight), float(eps), _p(h_out), _p(bias), _p(fc),
               int(rope_rows), int(head_dim), _p(y), N, K, T, _DT[weight.dtype], _stream())
+    return y
+
+
+def gemv_fused_w4_multi(weight, x, scales, groupsize, w3=None, scales3=None, delta=None, norm_weight=None, eps=1e-5, h_out=None,
+                        bias=None, freqs=None, rope_rows=0, head_dim=0):
+    """gemv_fused's int4 form for T input vectors from ONE pass over the weights (cc_gemv_fused_w4_multi), 1 <= T <= 4: uint8
+    `weight` (and `w3`) [N, K / 2] packed codes, `scales` (`scales3`) the contiguous bf16 (scale, zero) pairs [N, K / groupsize, 2],
+    bf16 x [T, K] (delta, h_out likewise), freqs [T, head_dim / 2, 2] -> bf16 [T, N].  Row t is bit-identical to gemv_fused on row t.
+    A function of its own: gemv_fused_multi keeps its signature and its refusal of int4 weights.  Every refusal precedes the
+    library call."""
+    what = "gemv_fused_w4_multi"
+    if not torch.is_tensor(weight) or weight.dtype != torch.uint8 or weight.dim() != 2:
+        raise _abi.ColdCompressError(f"{what}: int4 weights are uint8 [N, K / 2] packed codes, got "
+                                     f"{getattr(weight, 'dtype', type(weight))} {tuple(getattr(weight, 'shape', ()))}")
+    if scales is None or groupsize is None or (w3 is not None and (w3.dtype != torch.uint8 or scales3 is None)) or \
+            (w3 is None and scales3 is not None):
+        raise _abi.ColdCompressError(f"{what}: int4 weights need their (scale, zero) pairs and groupsize (and w3 uint8 with scales3)")
+    if int(groupsize) not in (32, 64, 128, 256):
+        raise _abi.ColdCompressError(f"{what}: groupsize must be 32, 64, 128 or 256, got {groupsize}")
+    groupsize = int(groupsize)
+    N, K = weight.shape[0], 2 * weight.shape[1]
+    if K % groupsize:
+        raise _abi.ColdCompressError(f"{what}: K = {K} is not a multiple of the groupsize {groupsize}")
+    if w3 is not None and tuple(w3.shape) != tuple(weight.shape):
+        raise _abi.ColdCompressError(f"{what}: w3 must have the shape of weight {tuple(weight.shape)}, got {tuple(w3.shape)}")
+    for t in (scales, scales3):
+        if t is not None and (t.dtype != torch.bfloat16 or not t.is_contiguous() or tuple(t.shape) != (N, K // groupsize, 2)):
+            raise _abi.ColdCompressError(f"{what}: int4 (scale, zero) pairs must be contiguous bf16 [{N}, K / {groupsize}, 2] "
+                                         f"(K = {K}), got {t.dtype} {tuple(t.shape)}")
+    if x.dtype != torch.bfloat16:
+        raise _abi.ColdCompressError(f"{what}: int4 weights need bf16 activations, got {x.dtype}")
+    if x.dim() != 2 or x.shape[1] != K:
+        raise _abi.ColdCompressError(f"{what}: x must be [T, {K}], got {tuple(x.shape)}")
+    T = x.shape[0]
+    if not 1 <= T <= GEMV_MULTI_MAX_T:
+        raise _abi.ColdCompressError(f"{what}: 1 <= T <= {GEMV_MULTI_MAX_T}, got T = {T}")
+    for name, t, shape in (("delta", delta, (T, K)), ("h_out", h_out, (T, K)), ("freqs", freqs, (T, head_dim // 2, 2))):
+        if t is not None and tuple(t.shape) != shape:
+            raise _abi.ColdCompressError(f"{what}: {name} must be {list(shape)}, got {tuple(t.shape)}")
+    for name, t in (("delta", delta), ("h_out", h_out), ("norm_weight", norm_weight), ("bias", bias), ("freqs", freqs)):
+        if t is not None and t.dtype != torch.bfloat16:
+            raise _abi.ColdCompressError(f"{what}: {name} must be bf16, got {t.dtype}")
+    if h_out is not None and not h_out.is_contiguous():
+        raise _abi.ColdCompressError(f"{what}: h_out must be contiguous")
+    if not x.is_cuda:
+        _host(x, f"{what} input")
+    xc = x.contiguous()
+    dc = delta.contiguous() if delta is not None else None
+    fc = freqs.contiguous() if freqs is not None else None
+    y = torch.empty((T, N), dtype=torch.bfloat16, device=weight.device)
+    _abi.call("cc_gemv_fused_w4_multi", _p(weight), _p(scales), _p(w3), _p(scales3), _p(xc), _p(dc), _p(norm_weight), float(eps),
+              _p(h_out), _p(bias), _p(fc), int(rope_rows), int(head_dim), _p(y), N, K, groupsize, T, _DT[torch.bfloat16], _stream())
     return y
 
 

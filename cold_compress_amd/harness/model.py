@@ -102,7 +102,8 @@ def _quant(linear, suffix=""):
     """glue.gemv_fused's quantisation arguments for a weight-only linear (harness/quantize.py), none for a dense one: int8 its
     per-row scales, int4 its per-row (scale, zero) pairs and groupsize, MXFP4 its e8m0 block-scale bytes (uint8 codes like int4's:
     told apart by the module's buffer, before the int4 branch).  suffix "3": the w3 of a SwiGLU pair.  glue.gemv_fused_multi takes
-    the same arguments except int4's `groupsize` (it has no int4 form): Transformer.block_eligible keeps int4 linears away from it."""
+    the same arguments except int4's `groupsize` (it refuses int4 weights); glue.gemv_fused_w4_multi takes int4's: _gemv_multi picks
+    between the two, and Transformer.block_eligible admits int4 linears only under `block_int4`."""
     if linear.weight.dtype == torch.uint8 and hasattr(linear, "block_scales"):
         return {"scales" + suffix: linear.block_scales}
     if linear.weight.dtype == torch.int8:
@@ -110,6 +111,17 @@ def _quant(linear, suffix=""):
     if linear.weight.dtype == torch.uint8:
         return {"scales" + suffix: linear.scales_and_zeros, "groupsize": linear.groupsize}
     return {}
+
+
+def _gemv_multi(linear, x, w3=None, **kw):
+    """One multi-vector product of forward_block / forward_streams: int4 linears through glue.gemv_fused_w4_multi (a function of
+    its own: gemv_fused_multi refuses int4 and takes no groupsize), every other kind through glue.gemv_fused_multi."""
+    q = _quant(linear)
+    if w3 is not None:
+        q.update(_quant(w3, "3"))
+        kw["w3"] = w3.weight
+    fn = glue.gemv_fused_w4_multi if "groupsize" in q else glue.gemv_fused_multi
+    return fn(linear.weight, x, **kw, **q)
 
 
 class RMSNorm(nn.Module):
@@ -290,20 +302,19 @@ class TransformerBlock(nn.Module):
         HQ, H, D = att.n_head, att.n_local_heads, att.head_dim
         x2 = x.view(T, -1)
         h1 = torch.empty_like(x2)
-        qkv = glue.gemv_fused_multi(att.wqkv.weight, x2, delta=None if delta is None else delta.view(T, -1),
-                                    norm_weight=self.attention_norm.weight, eps=self.attention_norm.eps, h_out=h1, bias=att.wqkv.bias,
-                                    freqs=freqs_cis, rope_rows=(HQ + H) * D, head_dim=D, **_quant(att.wqkv))
+        qkv = _gemv_multi(att.wqkv, x2, delta=None if delta is None else delta.view(T, -1),
+                          norm_weight=self.attention_norm.weight, eps=self.attention_norm.eps, h_out=h1, bias=att.wqkv.bias,
+                          freqs=freqs_cis, rope_rows=(HQ + H) * D, head_dim=D)
         ys = []
         for t in range(T):
             row = qkv[t]
             ys.append(att.decode_attend(row[: HQ * D].view(1, HQ, 1, D), row[HQ * D: (HQ + H) * D].view(1, H, 1, D),
                                         row[(HQ + H) * D:].view(1, H, 1, D), input_ids[:, t:t + 1], input_pos[t:t + 1], attn_top_k,
                                         cache=None if caches is None else caches[t]).view(1, -1))
-        a = glue.gemv_fused_multi(att.wo.weight, torch.cat(ys), **_quant(att.wo))
+        a = _gemv_multi(att.wo, torch.cat(ys))
         h2 = torch.empty_like(x2)
-        g = glue.gemv_fused_multi(ffn.w1.weight, h1, w3=ffn.w3.weight, delta=a, norm_weight=self.ffn_norm.weight, eps=self.ffn_norm.eps,
-                                  h_out=h2, **{**_quant(ffn.w1), **_quant(ffn.w3, "3")})
-        return h2.view(1, T, -1), glue.gemv_fused_multi(ffn.w2.weight, g, **_quant(ffn.w2)).view(1, T, -1)
+        g = _gemv_multi(ffn.w1, h1, w3=ffn.w3, delta=a, norm_weight=self.ffn_norm.weight, eps=self.ffn_norm.eps, h_out=h2)
+        return h2.view(1, T, -1), _gemv_multi(ffn.w2, g).view(1, T, -1)
 
 
 class Transformer(nn.Module):
@@ -320,6 +331,9 @@ class Transformer(nn.Module):
         # True: block_eligible also accepts weight-only int8 and MXFP4 linears (cc_gemv_fused_w8_multi / cc_gemv_fused_mx4_multi: the
         # same bits as the token-by-token route).  OPT-IN: DESIGN.md §2.12 has what blocks are worth for quantised weights
         self.block_weight_only = False
+        # True: block_eligible also accepts int4 group-wise linears at bf16 activations (cc_gemv_fused_w4_multi: the same bits as the
+        # token-by-token route).  OPT-IN and independent of block_weight_only: DESIGN.md §2.27
+        self.block_int4 = False
 
     @classmethod
     def from_name(cls, name: str):
@@ -397,10 +411,12 @@ class Transformer(nn.Module):
         run after later tokens have read the layer's cache; the fused quantised modes are fine), one rank.
         With `block_weight_only` set, each of the five linears of a layer and the LM head may also be a WeightOnlyInt8Linear (bf16 or
         f16 activations) or a WeightOnlyMxfp4Linear (bf16 activations) — recognised as the module with its scale buffer, not by the
-        weight's dtype — with w1 and w3 of the same kind.  Int4 linears have no multi GEMV: not eligible either way."""
+        weight's dtype — with w1 and w3 of the same kind.  With `block_int4` set (independent of `block_weight_only`; either or both),
+        each may also be a WeightOnlyInt4Linear carrying its (scale, zero) pairs and groupsize, at bf16 activations, with w1 and w3 of
+        the same groupsize (cc_gemv_fused_w4_multi).  Without it an int4 linear is not eligible, whatever `block_weight_only` says."""
         from ..cache import KVCacheAnalysis
         from .generation import _tp_world
-        from .quantize import is_int8_linear, is_mxfp4_linear
+        from .quantize import is_int4_linear, is_int8_linear, is_mxfp4_linear
 
         if attn_top_k != 1.0 or _tp_world() > 1 or self.freqs_cis is None:
             return False
@@ -409,11 +425,13 @@ class Transformer(nn.Module):
         on_device = probe.is_cuda  # (CPU tensors exist under tests/cpu_twin.py only: forward_block's row-by-row twin serves them)
 
         def kind(linear):
-            """'dense', 'int8' or 'mxfp4' for a linear the multi GEMVs serve at this model's activation dtype, else None."""
+            """'dense', 'int8', 'mxfp4' or 'int4' for a linear the multi GEMVs serve at this model's activation dtype, else None."""
             if self.block_weight_only and is_int8_linear(linear):
                 return "int8" if probe.dtype in (torch.bfloat16, torch.float16) else None
             if self.block_weight_only and is_mxfp4_linear(linear):
                 return "mxfp4" if probe.dtype == torch.bfloat16 else None
+            if self.block_int4 and is_int4_linear(linear):
+                return "int4" if probe.dtype == torch.bfloat16 else None
             return "dense" if linear.weight.dtype in dense else None
 
         if kind(self.output) is None or (on_device and not (self.output.bias is None and glue.gemv_supported(self.output.weight))):
@@ -421,6 +439,8 @@ class Transformer(nn.Module):
         for layer in self.layers:
             att, ffn, cache = layer.attention, layer.feed_forward, layer.attention.kv_cache
             if any(kind(m) is None for m in (att.wqkv, att.wo, ffn.w1, ffn.w3, ffn.w2)) or kind(ffn.w1) != kind(ffn.w3):
+                return False
+            if kind(ffn.w1) == "int4" and ffn.w1.groupsize != ffn.w3.groupsize:
                 return False
             if (on_device and not layer.device_fused(probe)) or att.fuse_qkv_step or cache is None or isinstance(cache, KVCacheAnalysis):
                 return False
@@ -444,8 +464,8 @@ class Transformer(nn.Module):
             if self.batch_quant_flush:
                 flush_quantized([layer.attention.kv_cache for layer in self.layers])
             return torch.cat([self.output(self.norm(x[:, t:t + 1], delta[:, t:t + 1])[1]) for t in range(T)], 1)
-        return glue.gemv_fused_multi(self.output.weight, x.view(T, -1), delta=delta.view(T, -1), norm_weight=self.norm.weight,
-                                     eps=self.norm.eps, **_quant(self.output)).view(1, T, -1)
+        return _gemv_multi(self.output, x.view(T, -1), delta=delta.view(T, -1), norm_weight=self.norm.weight,
+                           eps=self.norm.eps).view(1, T, -1)
 
     def streams_eligible(self, streams, attn_top_k=1.0):
         """block_eligible evaluated over every stream's caches (harness/streams.py, DecodeStreams): True when forward_streams
@@ -484,5 +504,5 @@ class Transformer(nn.Module):
                 for caches in streams.sets:
                     flush_quantized(list(caches))
             return torch.cat([self.output(self.norm(x[:, t:t + 1], delta[:, t:t + 1])[1]) for t in range(T)], 1)
-        return glue.gemv_fused_multi(self.output.weight, x.view(T, -1), delta=delta.view(T, -1), norm_weight=self.norm.weight,
-                                     eps=self.norm.eps, **_quant(self.output)).view(1, T, -1)
+        return _gemv_multi(self.output, x.view(T, -1), delta=delta.view(T, -1), norm_weight=self.norm.weight,
+                           eps=self.norm.eps).view(1, T, -1)

@@ -234,7 +234,8 @@ class WeightOnlyInt4QuantHandler:
 
 
 def is_int4_linear(m) -> bool:
-    return isinstance(m, WeightOnlyInt4Linear)
+    """The module with its (scale, zero) pairs and groupsize, not a bare uint8 weight."""
+    return isinstance(m, WeightOnlyInt4Linear) and getattr(m, "scales_and_zeros", None) is not None and hasattr(m, "groupsize")
 
 
 def check_int4_state_dict(model: nn.Module, sd) -> None:

@@ -284,7 +284,7 @@ def generate_streams(model, prompts, prefill, max_new_tokens, n_streams=None, se
     streams are finished or after `max_new_tokens`.  `graph` (device tensors): one joint step is captured (GraphedStreamsDecoder); a
     refused capture falls back to eager joint steps with a line through `log`.  The single-launch status word is read once behind
     every joint step and a set word raises, with the step's positions: a joint step cannot be rewound token-wise.
-    A model that is not `streams_eligible` (int4 weights, a cache quantising in reference mode, attn_top_k < 1, more than one rank)
+    A model that is not `streams_eligible` (int4 weights without `model.block_int4`, a cache quantising in reference mode, attn_top_k < 1, more than one rank)
     runs its streams one at a time per step through activate(s) + decode_one_token: the same results, no speed-up.
     Not served (ValueError before any launch): penalties, constraints, top_logprobs, next_tokens, feed_long_prompts,
     decode_first_token — their state is per sequence — and a prompt exactly as long as the smallest cache, which generate() splits

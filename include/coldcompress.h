@@ -783,7 +783,7 @@ int cc_gemv_fused(const void* W, const void* W3, const void* x, const void* delt
  * Row t of y and of h_out is BIT-IDENTICAL to cc_gemv_fused called with row t of x, delta and freqs, for every dtype, form and
  * shape cc_gemv_fused serves (a row's arithmetic there depends neither on the rows and column steps in flight nor on the grid, and
  * is kept per token here).  Same argument checks and CC_ERR_UNSUPPORTED cases; T outside 1 .. CC_GEMV_MULTI_MAX_T:
- * CC_ERR_BAD_ARG.  Dense weights only (int8 / MXFP4: cc_gemv_fused_w8_multi / cc_gemv_fused_mx4_multi).  A plain grid: no workgroup waits for another.  Arguments are validated before any launch:
+ * CC_ERR_BAD_ARG.  Dense weights only (int8 / MXFP4 / int4: cc_gemv_fused_w8_multi / cc_gemv_fused_mx4_multi / cc_gemv_fused_w4_multi).  A plain grid: no workgroup waits for another.  Arguments are validated before any launch:
  * an error writes nothing. */
 #define CC_GEMV_MULTI_MAX_T 4
 int cc_gemv_fused_multi(const void* W, const void* W3, const void* x, const void* delta, const void* norm_w, float eps,
@@ -920,7 +920,8 @@ int cc_gemv_fused_mx4(const uint8_t* W, const uint8_t* scales, const uint8_t* W3
  * The norm prologue passes the T tokens one after the other through ONE staging buffer: the dynamic LDS of a workgroup is the
  * single-vector kernel's.  Same argument checks and CC_ERR_UNSUPPORTED cases as the single-vector entry point; T outside
  * 1 .. CC_GEMV_MULTI_MAX_T: CC_ERR_BAD_ARG.  T = 1 launches the single-vector kernel itself.  A plain grid: no workgroup waits for
- * another.  Arguments are validated before any launch: an error writes nothing.  (Int4 group-wise weights have no multi form.)
+ * another.  Arguments are validated before any launch: an error writes nothing.  (Int4 group-wise weights: cc_gemv_fused_w4_multi,
+ * below.)
  * Under the tuning hooks (CC_GEMV_W8_CFG / CC_GEMV_MX4_CFG) the refusals are the single-vector entry point's too; the MXFP4 form
  * builds the default geometries only and runs the shape's default one where the hook names another that cc_gemv_fused_mx4 serves
  * (results do not depend on the geometry). */
@@ -932,6 +933,28 @@ int cc_gemv_fused_mx4_multi(const uint8_t* W, const uint8_t* scales, const uint8
                             const void* delta, const void* norm_w, float eps, void* h_out, const void* bias, const void* freqs,
                             int32_t rope_rows, int32_t head_dim, void* y, int32_t N, int32_t K, int32_t T, int32_t dtype,
                             cc_stream_t stream);
+
+/* cc_gemv_fused_w4 for T input vectors from ONE pass over the weights, 1 <= T <= CC_GEMV_MULTI_MAX_T: what cc_gemv_fused_mx4_multi is
+ * to cc_gemv_fused_mx4, for int4 group-wise weight-only models.
+ *   x, delta (or NULL), h_out (or NULL): [T, K];  freqs (or NULL): [T, head_dim / 2, 2], row t the (cos, sin) of token t's position;
+ *   y: [T, N];  W, W3, qparams, qparams3, norm_w, bias: as cc_gemv_fused_w4, shared by the T rows.
+ * Row t of y and of h_out is BIT-IDENTICAL to cc_gemv_fused_w4 called with row t of x, delta and freqs, for every form, groupsize and
+ * shape it serves, K * 2 = 64 KiB with the norm prologue included: the lane that owns a 16-byte code chunk, the order of its dot
+ * chain from -136 Sx, the two fused multiply-adds per chunk (scale, then zero times Sx), the wave and workgroup reductions (the waves
+ * per row are a function of K) and every rounding point are kept per token; a code register and its (scale, zero) word are loaded and
+ * decoded once and feed T accumulator chains.  The norm prologue passes the T tokens one after the other through ONE staging buffer:
+ * the dynamic LDS of a workgroup is the single-vector kernel's.  cc_gemv_fused_w4's argument checks and return codes, through the
+ * same function (qparams present and paired with W3, groupsize, the shared conditions, bf16 only, K % groupsize == 0); T outside
+ * 1 .. CC_GEMV_MULTI_MAX_T: CC_ERR_BAD_ARG; and, here only, W / W3 / x / delta / norm_w / h_out not 16-byte aligned or qparams /
+ * qparams3 not 4-byte aligned: CC_ERR_BAD_ARG.  T = 1 launches the single-vector kernel itself.  A plain grid: no workgroup waits
+ * for another, no atomics.  Arguments are validated before any launch: an error writes nothing.  Under the tuning hook
+ * (CC_GEMV_W4_CFG) the refusals are cc_gemv_fused_w4's too; only the default geometries are built for T > 1, and the shape's default
+ * one runs where the hook names another that cc_gemv_fused_w4 serves, under the hook's grid cap (results do not depend on the
+ * geometry). */
+int cc_gemv_fused_w4_multi(const uint8_t* W, const void* qparams, const uint8_t* W3, const void* qparams3, const void* x,
+                           const void* delta, const void* norm_w, float eps, void* h_out, const void* bias, const void* freqs,
+                           int32_t rope_rows, int32_t head_dim, void* y, int32_t N, int32_t K, int32_t groupsize, int32_t T,
+                           int32_t dtype, cc_stream_t stream);
 
 /* Greedy sampling tail, ref: generation_utils.py:136-142: probs[V] = dtype(softmax_fp32(logits[V])),
  * *idx_out = first index of the largest rounded probability (torch.argmax semantics).  Two small launches; `workspace`

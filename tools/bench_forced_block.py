@@ -13,9 +13,11 @@ Prints one JSON object; profiles/forced_block.md is written from it.
 
 --weights int8 / mxfp4 quantises the random model with the weight-only handler (harness/quantize.py, as tools/run_configs.py
 --weights does) and sets Transformer.block_weight_only: the blocks and the per-matrix table then run cc_gemv_fused_w8_multi /
-cc_gemv_fused_mx4_multi against cc_gemv_fused_w8 / cc_gemv_fused_mx4 (profiles/forced_block_weight_only.md).  Default bf16: as it was.
+cc_gemv_fused_mx4_multi against cc_gemv_fused_w8 / cc_gemv_fused_mx4 (profiles/forced_block_weight_only.md).  --weights int4
+--groupsize G does the same with the int4 handler and Transformer.block_int4: cc_gemv_fused_w4_multi against cc_gemv_fused_w4
+(profiles/w4_multi.md).  Default bf16: as it was.
 
-    python tools/bench_forced_block.py [--n_layer 32] [--tokens 256] [--rounds 5] [--weights bf16|int8|mxfp4] [--out FILE]"""
+    python tools/bench_forced_block.py [--n_layer 32] [--tokens 256] [--rounds 5] [--weights bf16|int8|mxfp4|int4] [--groupsize G] [--out FILE]"""
 import argparse
 import json
 import os
@@ -28,7 +30,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def build(n_layer, dev, weights="bf16"):
+def build(n_layer, dev, weights="bf16", groupsize=128):
     from cold_compress_amd.harness import CONFIGS, ModelArgs, Transformer
 
     cfg = dict(CONFIGS["Meta-Llama-3-8B-Instruct"], n_layer=n_layer, block_size=16384)
@@ -42,9 +44,10 @@ def build(n_layer, dev, weights="bf16"):
             p.fill_(1.0) if "norm" in name else p.normal_(0.0, 0.02, generator=g)
     model.eval()
     if weights != "bf16":
-        from cold_compress_amd.harness.quantize import WeightOnlyInt8QuantHandler, WeightOnlyMxfp4QuantHandler
+        from cold_compress_amd.harness.quantize import WeightOnlyInt4QuantHandler, WeightOnlyInt8QuantHandler, WeightOnlyMxfp4QuantHandler
 
-        handler = {"int8": WeightOnlyInt8QuantHandler, "mxfp4": WeightOnlyMxfp4QuantHandler}[weights]
+        handler = {"int8": WeightOnlyInt8QuantHandler, "mxfp4": WeightOnlyMxfp4QuantHandler,
+                   "int4": lambda m: WeightOnlyInt4QuantHandler(m, groupsize)}[weights]
         sd = handler(model).create_quantized_state_dict()
         del model
         with torch.device("meta"):
@@ -53,7 +56,10 @@ def build(n_layer, dev, weights="bf16"):
         model = model.to(device=dev, dtype=torch.bfloat16).eval()
         del sd
         torch.cuda.empty_cache()
-        model.block_weight_only = True
+        if weights == "int4":
+            model.block_int4 = True  # (callers that want the per-token route clear it)
+        else:
+            model.block_weight_only = True
     return model
 
 
@@ -65,14 +71,15 @@ def main():
     ap.add_argument("--tokens", type=int, default=256)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--settle", type=int, default=160)
-    ap.add_argument("--weights", default="bf16", choices=["bf16", "int8", "mxfp4"])
+    ap.add_argument("--weights", default="bf16", choices=["bf16", "int8", "mxfp4", "int4"])
+    ap.add_argument("--groupsize", type=int, default=128, choices=[32, 64, 128, 256], help="--weights int4: columns per group")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     from cold_compress_amd.harness import GraphedDecoder, decode_n_tokens, decode_one_token, glue, prefill, setup_caches
-    from cold_compress_amd.harness.model import _quant
+    from cold_compress_amd.harness.model import _gemv_multi, _quant
 
     dev = torch.device("cuda", 0)
-    model = build(args.n_layer, dev, args.weights)
+    model = build(args.n_layer, dev, args.weights, args.groupsize)
     ck = dict(max_cache_length=[float(args.cache_len)], cache_bits=None, cache_length_pattern="tile", cache_strategy=["heavy_hitter"],
               cache_strategy_pattern="tile", feed_long_prompts=False, prompt_compression_strategy=["heavy_hitter"], global_tokens=4,
               recent_window=10, history_window_size=1, attn_thresholding=False, min_recovery_frac=0.9)
@@ -127,21 +134,20 @@ def main():
         h4 = torch.empty_like(x4)
         rope = dict(rope_rows=(HQ + H) * D, head_dim=D)
         mats = {
-            "wqkv": (len(L), lambda i, T: glue.gemv_fused_multi(L[i].attention.wqkv.weight, x4[:T], delta=d4[:T], norm_weight=L[i].attention_norm.weight,
-                                                                 h_out=h4[:T], freqs=fr4[:T], **rope, **_quant(L[i].attention.wqkv)),
+            "wqkv": (len(L), lambda i, T: _gemv_multi(L[i].attention.wqkv, x4[:T], delta=d4[:T], norm_weight=L[i].attention_norm.weight,
+                                                      h_out=h4[:T], freqs=fr4[:T], **rope),
                      lambda i: glue.gemv_fused(L[i].attention.wqkv.weight, x4[0], delta=d4[0], norm_weight=L[i].attention_norm.weight, h_out=h4[0],
                                                freqs=fr4[0], **rope, **_quant(L[i].attention.wqkv))),
-            "wo": (len(L), lambda i, T: glue.gemv_fused_multi(L[i].attention.wo.weight, x4[:T], **_quant(L[i].attention.wo)),
+            "wo": (len(L), lambda i, T: _gemv_multi(L[i].attention.wo, x4[:T]),
                    lambda i: glue.gemv_fused(L[i].attention.wo.weight, x4[0], **_quant(L[i].attention.wo))),
-            "w1/w3": (len(L), lambda i, T: glue.gemv_fused_multi(L[i].feed_forward.w1.weight, x4[:T], w3=L[i].feed_forward.w3.weight, delta=d4[:T],
-                                                                  norm_weight=L[i].ffn_norm.weight, h_out=h4[:T],
-                                                                  **{**_quant(L[i].feed_forward.w1), **_quant(L[i].feed_forward.w3, "3")}),
+            "w1/w3": (len(L), lambda i, T: _gemv_multi(L[i].feed_forward.w1, x4[:T], w3=L[i].feed_forward.w3, delta=d4[:T],
+                                                       norm_weight=L[i].ffn_norm.weight, h_out=h4[:T]),
                       lambda i: glue.gemv_fused(L[i].feed_forward.w1.weight, x4[0], w3=L[i].feed_forward.w3.weight, delta=d4[0],
                                                 norm_weight=L[i].ffn_norm.weight, h_out=h4[0],
                                                 **{**_quant(L[i].feed_forward.w1), **_quant(L[i].feed_forward.w3, "3")})),
-            "w2": (len(L), lambda i, T: glue.gemv_fused_multi(L[i].feed_forward.w2.weight, g4[:T], **_quant(L[i].feed_forward.w2)),
+            "w2": (len(L), lambda i, T: _gemv_multi(L[i].feed_forward.w2, g4[:T]),
                    lambda i: glue.gemv_fused(L[i].feed_forward.w2.weight, g4[0], **_quant(L[i].feed_forward.w2))),
-            "lm_head": (1, lambda i, T: glue.gemv_fused_multi(model.output.weight, x4[:T], delta=d4[:T], norm_weight=model.norm.weight, **_quant(model.output)),
+            "lm_head": (1, lambda i, T: _gemv_multi(model.output, x4[:T], delta=d4[:T], norm_weight=model.norm.weight),
                         lambda i: glue.gemv_fused(model.output.weight, x4[0], delta=d4[0], norm_weight=model.norm.weight, **_quant(model.output))),
         }
         gemv = {}
@@ -158,7 +164,7 @@ def main():
                 for k in order[r % len(order):] + order[:r % len(order)]:
                     us[k].append(ev_us(runs[k], reps * n))
             gemv[name] = {k: round(statistics.median(v), 2) for k, v in us.items()}
-    out = {"shape": "Meta-Llama-3-8B-Instruct", "weights": args.weights, "n_layer": args.n_layer, "cache_len": args.cache_len, "tokens": args.tokens, "rounds": args.rounds,
+    out = {"shape": "Meta-Llama-3-8B-Instruct", "weights": args.weights, **({"groupsize": args.groupsize} if args.weights == "int4" else {}), "n_layer": args.n_layer, "cache_len": args.cache_len, "tokens": args.tokens, "rounds": args.rounds,
            "device": torch.cuda.get_device_name(0),
            "tokens_per_s": {m: {"median": round(statistics.median(v), 1), "min": round(min(v), 1), "max": round(max(v), 1)} for m, v in tps.items()},
            "ms_per_token": {m: round(1e3 / statistics.median(v), 3) for m, v in tps.items()}, "gemv_us": gemv}

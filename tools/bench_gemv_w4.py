@@ -3,7 +3,10 @@
 Llama-3-8B decode shapes and the LM head, in the fused forms the decode loop launches (wqkv: norm + RoPE; w1/w3: norm + SwiGLU
 pair; LM head: final norm).  Each format rotates over enough distinct weight copies to exceed the 256 MB Infinity Cache; hipGraph
 replays, HIP events, median of 10.  One JSON line per shape; TB/s counts the bytes each format streams (int4: codes + pairs).
-    python tools/bench_gemv_w4.py [shape ...] [--int4-only]   (CC_GEMV_W4_CFG="RB,CU[,workgroups]" overrides the int4 geometry)"""
+    python tools/bench_gemv_w4.py [shape ...] [--int4-only]   (CC_GEMV_W4_CFG="RB,CU[,workgroups]" overrides the int4 geometry)
+    python tools/bench_gemv_w4.py [shape ...] --tokens T      cc_gemv_fused_w4_multi at 1 .. T input rows (T <= 4) against as many
+        single-vector launches, G = 32 and 128, the same rotation and timing; five passes in alternating order, the median of the
+        passes' medians.  us per launch; "x_singles" is t(T) / (T * t(single)): below 1 the one pass over the weights wins."""
 import json
 import os
 import sys
@@ -25,9 +28,76 @@ def _int4(N, K, G):
     return pack_int4(q).contiguous(), torch.stack([s, z], -1).contiguous()
 
 
+SHAPES = {"wqkv": (6144, 4096), "wo": (4096, 4096), "w1w3": (14336, 4096), "w2": (4096, 14336), "lm_head": (128256, 4096)}
+
+
+def main_tokens(tmax, only, passes=5):
+    torch.manual_seed(0)
+    bf = torch.bfloat16
+    for name, (N, K) in SHAPES.items():
+        if only and name not in only:
+            continue
+        pair = name == "w1w3"
+        nmat = 2 if pair else 1
+        x = torch.randn(tmax, K, device=dev).to(bf)
+        delta = torch.randn(tmax, K, device=dev).to(bf)
+        nw = torch.ones(K, device=dev, dtype=bf)
+        h = torch.empty(tmax, K, device=dev, dtype=bf)
+        fr = torch.rand(tmax, 64, 2, device=dev).to(bf)
+        for G in (32, 128):
+            b4 = nmat * N * (K // 2 + 4 * (K // G))
+            Q4 = [[_int4(N, K, G) for _ in range(nmat)] for _ in range(max(2, SET // b4 + 1))]
+            n = len(Q4)
+
+            def kw(T, one):
+                r = slice(0, 1) if one else slice(0, T)
+                if name == "wqkv":
+                    k = dict(delta=delta[r], norm_weight=nw, h_out=h[r], freqs=fr[r], rope_rows=5120, head_dim=128)
+                elif pair or name == "lm_head":
+                    k = dict(delta=delta[r], norm_weight=nw, h_out=h[r])
+                else:
+                    k = {}
+                return {a: (b[0] if one and torch.is_tensor(b) and a != "norm_weight" else b) for a, b in k.items()}
+
+            def single(i):
+                m = Q4[i % n]
+                return glue.gemv_fused(m[0][0], x[0], w3=m[1][0] if pair else None, scales=m[0][1], scales3=m[1][1] if pair else None,
+                                       groupsize=G, **kw(1, True))
+
+            def multi(T):
+                def run(i):
+                    m = Q4[i % n]
+                    return glue.gemv_fused_w4_multi(m[0][0], x[:T], m[0][1], G, w3=m[1][0] if pair else None,
+                                                    scales3=m[1][1] if pair else None, **kw(T, False))
+                return run
+
+            runs = [("single", single)] + [(f"T{T}", multi(T)) for T in range(1, tmax + 1)]
+            ts = {k: [] for k, _ in runs}
+            for ps in range(passes):  # alternating order
+                for k, fn in (runs if ps % 2 == 0 else runs[::-1]):
+                    ts[k].append(timed(fn, max(n, 8)))
+            med = {k: sorted(v)[len(v) // 2] for k, v in ts.items()}
+            res = {"shape": name, "N": N, "K": K, "matrices": nmat, "G": G, "MB_int4": round(b4 / 1e6, 1), "single_us": round(med["single"], 2)}
+            for T in range(1, tmax + 1):
+                t = med[f"T{T}"]
+                res.update({f"T{T}_us": round(t, 2), f"T{T}_x_singles": round(t / (T * med["single"]), 3), f"T{T}_TBps": round(b4 / t / 1e6, 2)})
+            cfg = os.environ.get("CC_GEMV_W4_CFG")
+            if cfg:
+                res["w4_cfg"] = cfg
+            print(json.dumps(res), flush=True)
+            del Q4
+            torch.cuda.empty_cache()
+
+
 def main():
     torch.manual_seed(0)
-    shapes = {"wqkv": (6144, 4096), "wo": (4096, 4096), "w1w3": (14336, 4096), "w2": (4096, 14336), "lm_head": (128256, 4096)}
+    shapes = SHAPES
+    if "--tokens" in sys.argv[1:]:
+        i = sys.argv.index("--tokens")
+        tmax = int(sys.argv[i + 1])
+        if not 1 <= tmax <= glue.GEMV_MULTI_MAX_T:
+            sys.exit(f"--tokens: 1 .. {glue.GEMV_MULTI_MAX_T}")
+        return main_tokens(tmax, [a for a in sys.argv[1:i] + sys.argv[i + 2:] if not a.startswith("--")])
     int4_only = "--int4-only" in sys.argv[1:]
     only = [a for a in sys.argv[1:] if a != "--int4-only"]
     bf = torch.bfloat16

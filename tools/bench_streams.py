@@ -12,7 +12,16 @@ in alternating order, `--rounds` times each, on one device in one process; token
 one-token loop runs on stream 0, which the streams modes step too: every mode continues each sequence where the last run left it.
 Prints one JSON object; profiles/streams.md is written from it.
 
-    python tools/bench_streams.py [--n_layer 32] [--tokens 128] [--rounds 5] [--temperature T --top_k K --top_p P] [--out FILE]"""
+--weights int8 / mxfp4 / int4 (--groupsize G) quantises the random model with the weight-only handler and sets the matching opt-in
+attribute (Transformer.block_weight_only / block_int4).  Such runs add
+
+    serial_N           N = 2, 3, 4 streams, one stream at a time per step (decode_one_token on each stream's caches): the route these
+                       models take with the attribute off
+
+Default bf16: as it was.
+
+    python tools/bench_streams.py [--n_layer 32] [--tokens 128] [--rounds 5] [--temperature T --top_k K --top_p P]
+                                  [--weights bf16|int8|mxfp4|int4] [--groupsize G] [--out FILE]"""
 import argparse
 import json
 import os
@@ -39,19 +48,21 @@ def main():
     ap.add_argument("--temperature", type=float, default=None, help="default: greedy, as bench.py decodes")
     ap.add_argument("--top_k", type=int, default=None)
     ap.add_argument("--top_p", type=float, default=None)
+    ap.add_argument("--weights", default="bf16", choices=["bf16", "int8", "mxfp4", "int4"])
+    ap.add_argument("--groupsize", type=int, default=128, choices=[32, 64, 128, 256], help="--weights int4: columns per group")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     from cold_compress_amd.harness import DecodeStreams, GraphedDecoder, GraphedStreamsDecoder, decode_n_tokens, glue, prefill, setup_caches
     from cold_compress_amd.harness.streams import decode_streams
 
     dev = torch.device("cuda", 0)
-    model = build(args.n_layer, dev)
+    model = build(args.n_layer, dev, args.weights, args.groupsize)  # (sets the opt-in attribute of a weight-only model)
     ck = dict(max_cache_length=[float(args.cache_len)], cache_bits=None, cache_length_pattern="tile", cache_strategy=["heavy_hitter"],
               cache_strategy_pattern="tile", feed_long_prompts=False, prompt_compression_strategy=["heavy_hitter"], global_tokens=4,
               recent_window=10, history_window_size=1, attn_thresholding=False, min_recovery_frac=0.9)
     setup_caches(model, None, dev, 16384, ck)
     streams4 = DecodeStreams(model, 4)
-    assert model.streams_eligible(streams4) and glue.w12_enabled()
+    assert model.streams_eligible(streams4) and (args.weights != "bf16" or glue.w12_enabled())
     gen = torch.Generator().manual_seed(7)
     V = model.config.vocab_size
     prompt = torch.randint(0, V, (args.prompt_len,), generator=gen, dtype=torch.int32).to(dev)
@@ -75,12 +86,13 @@ def main():
             pos[:1] = p
             return steps / dt
 
-        def joint(n, graph_it, steps):
+        def joint(n, graph_it, steps, serial=False):
             dec = decs[n] if graph_it else None
             settings = (tuple(range(n)), args.temperature, args.top_k, args.top_p, None, False)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            toks, _, _, dec2 = decode_streams(model, streams4.first(n), tok[:, :n].contiguous(), pos[:n].clone(), steps, settings, dec=dec)
+            toks, _, _, dec2 = decode_streams(model, streams4.first(n), tok[:, :n].contiguous(), pos[:n].clone(), steps, settings, dec=dec,
+                                                  joint=not serial)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             assert dec2 is dec, "the capture of the joint step was refused"
@@ -93,6 +105,9 @@ def main():
         for n in (2, 3, 4):
             modes[f"eager_{n}"] = (lambda n: lambda steps: joint(n, False, steps))(n)
             modes[f"graphed_{n}"] = (lambda n: lambda steps: joint(n, True, steps))(n)
+        if args.weights != "bf16":
+            for n in (2, 3, 4):
+                modes[f"serial_{n}"] = (lambda n: lambda steps: joint(n, False, steps, serial=True))(n)
         names = list(modes)
         for m in names:  # one untimed pass of every mode (captures included)
             modes[m](16)
@@ -101,7 +116,8 @@ def main():
             for m in names[r % len(names):] + names[:r % len(names)]:  # alternating order
                 tps[m].append(modes[m](args.tokens))
     width = {m: 1 if m == "graphed_1" else int(m.split("_")[1]) for m in names}
-    out = {"shape": "Meta-Llama-3-8B-Instruct", "n_layer": args.n_layer, "cache_len": args.cache_len, "steps_per_run": args.tokens,
+    out = {"shape": "Meta-Llama-3-8B-Instruct", "weights": args.weights, **({"groupsize": args.groupsize} if args.weights == "int4" else {}),
+           "n_layer": args.n_layer, "cache_len": args.cache_len, "steps_per_run": args.tokens,
            "rounds": args.rounds, "sampling": skw, "device": torch.cuda.get_device_name(0),
            "cache_set_gb": round(sum(b.numel() * b.element_size() for c in streams4.sets[1] for b in c._buffers.values() if b is not None) / 1e9, 3),
            "aggregate_tokens_per_s": {m: {"median": round(statistics.median(v), 1), "min": round(min(v), 1), "max": round(max(v), 1)}
