@@ -41,13 +41,21 @@ __global__ __launch_bounds__(kGvThreads) void gemv_kernel(GemvArgs a) {
   gemv_body<T, SWIGLU, RB, CU, XS>(a, issue, get, get3);
 }
 
-static GvCfg pick_cfg(const GemvArgs& a, int vec) {
+// tuning hook: CC_GEMV_CFG="RB,CU[,max workgroups]" (read once per process) -> true and the geometry it names
+static bool env_cfg(GvCfg* c) {
   static int env_rb = -1, env_cu = -1, env_cap = 2048;
-  if (env_rb < 0) {  // tuning hook: CC_GEMV_CFG="RB,CU[,max workgroups]"
+  if (env_rb < 0) {
     env_rb = env_cu = 0;
     if (const char* e = getenv("CC_GEMV_CFG")) sscanf(e, "%d,%d,%d", &env_rb, &env_cu, &env_cap);
   }
-  if (env_rb > 0 && env_cu > 0) return {env_rb, env_cu, env_cap};
+  if (env_rb <= 0 || env_cu <= 0) return false;
+  *c = {env_rb, env_cu, env_cap};
+  return true;
+}
+
+static GvCfg pick_cfg(const GemvArgs& a, int vec) {
+  GvCfg env;
+  if (env_cfg(&env)) return env;
   const int nseg = (a.K / vec + 63) / 64, nstep = (nseg + kGvWaves - 1) / kGvWaves;
   // measured on MI355X (tools/bench_gemv.py): 2 rows x 2 segments per wave for the SwiGLU pair at K = 4096 (w1 + w3 39.5 us =
   // 5.95 TB/s), 4 x 4 for K = 14336 (w2 20.9 us)
@@ -272,8 +280,26 @@ __global__ __launch_bounds__(kGvThreads) void gemv_multi_kernel(GemvArgs a) {
 // The geometry of a multi launch: pick_cfg's choice for the shape, with fewer rows / column steps in flight where NT * XS input
 // chunks per lane leave no room for it (results do not depend on either number).  Only fp32 needs it (DESIGN.md §2.10 has the
 // register figures of every instantiation): 16 chunks x 3 tokens fit at 2 x 2, and 4 x 8 at 8 chunks x 4 tokens becomes 4 x 4.
+//
+// 16-bit rows at 3 and 4 tokens (profiles/gemv_multi_geometry.md: a same-session sweep of every geometry the table builds without
+// scratch over the 8B model's four decode shapes, bf16; each choice below beat pick_cfg's by more than the spread of pick_cfg's own
+// five runs; nothing qualified at T = 2, and the wo shape keeps pick_cfg's choice at every T).  A 256-thread workgroup is one wave
+// per SIMD, and the registers of an instantiation set how many workgroups a CU holds (§2.11's table):
+//   - long rows (w2, XS = 8) at T = 4: 4 x 4 takes 260 registers — one wave per SIMD — and 2 x 4 takes 228, two: 31.0 -> 23.3 us;
+//   - the SwiGLU pair at K <= 4096 and T >= 3: 2 x 2 takes 90 / 104 registers, 5 / 4 workgroups per CU, so 2048 workgroups are
+//     a second, partial round of residency; 1024 are all resident and loop: 44.7 -> 42.5 us (T = 3), 50.9 -> 46.1 (T = 4);
+//   - short plain rows whose row groups are no whole number of rounds of the 1024 (wqkv: 1536 groups of 4 rows) at T >= 3: 512
+//     workgroups run three whole rounds: 16.7 -> 15.9 us (T = 3), 18.9 -> 17.3 (T = 4).
+// CC_GEMV_CFG names the geometry itself: none of these applies under it.
 static GvCfg pick_multi_cfg(const GemvArgs& a, int vec, int xs, int nt) {
   GvCfg c = pick_cfg(a, vec);
+  GvCfg env;
+  if (vec == 8 && nt >= 3 && !env_cfg(&env)) {
+    const int groups = (a.N + c.rb - 1) / c.rb;
+    if (xs == 8 && a.W3 == nullptr && nt == 4 && c.rb == 4 && c.cu == 4) c.rb = 2;
+    else if (xs == 2 && a.W3 != nullptr && c.cap > 1024) c.cap = 1024;
+    else if (xs == 2 && a.W3 == nullptr && a.N < 32768 && groups > c.cap && groups % c.cap != 0) c.cap = 512;
+  }
   if (vec == 4 && xs == 16 && nt >= 3) c.rb = c.cu = 2;
   if (vec == 4 && xs == 8 && nt == 4 && c.rb == 4 && c.cu == 8) c.cu = 4;
   return c;

@@ -509,7 +509,6 @@ extern "C" int cc_gemv_fused_w12(const void* codes, const void* records, int32_t
   if ((W3 != nullptr) != (codes3 != nullptr) || (W3 != nullptr) != (records3 != nullptr)) return CC_ERR_BAD_ARG;
   if (base < 0 || base > 240 || (W3 && (base3 < 0 || base3 > 240))) return CC_ERR_BAD_ARG;
   if (layout != 0 && ((base & 1) || (W3 && (base3 & 1)))) return CC_ERR_BAD_ARG;
-  if (!w12_layout_ok(codes, layout) || (codes3 && !w12_layout_ok(codes3, layout))) return CC_ERR_BAD_ARG;  // packed in the other layout
   if ((delta || h_out) && !norm_w) return CC_ERR_BAD_ARG;
   if (freqs && (W3 || rope_rows < 0 || rope_rows > N || head_dim <= 0 || (head_dim & 1) || (rope_rows % head_dim))) return CC_ERR_BAD_ARG;
   if (W3 && bias) return CC_ERR_BAD_ARG;
@@ -517,6 +516,9 @@ extern "C" int cc_gemv_fused_w12(const void* codes, const void* records, int32_t
   int32_t geo[5];
   const int rc = cc_w12_geometry(N, K, (W3 != nullptr ? 1 : 0) | (layout << 8), geo);
   if (rc != CC_OK) return rc;
+  // (behind the shape's verdict: the registry is keyed by address and never forgets, so a fresh buffer at the address of a freed copy
+  //  of another layout would otherwise turn the CC_ERR_UNSUPPORTED of a shape this id does not serve into CC_ERR_BAD_ARG)
+  if (!w12_layout_ok(codes, layout) || (codes3 && !w12_layout_ok(codes3, layout))) return CC_ERR_BAD_ARG;  // packed in the other layout
   if (geo[0] != rb || geo[1] != cu) return CC_ERR_BAD_ARG;  // the records were laid out for another launch geometry
   GemvW12Args a;
   a.g = GemvArgs{W, W3, x, delta, norm_w, bias, freqs, h_out, y, eps, N, K, freqs ? rope_rows : 0, freqs ? head_dim : 2};

@@ -6,6 +6,7 @@ Budget helpers are exact-integer restatements checked against tests/golden/f8_bu
 """
 import math
 import time
+from types import SimpleNamespace
 from typing import NamedTuple
 
 import torch
@@ -633,6 +634,194 @@ def _recover_token(model, cur_token, input_pos, decode_fn, nt, npb, forced, attn
 
 _MAX_BLOCK = 4  # glue.GEMV_MULTI_MAX_T: the most input vectors cc_gemv_fused_multi takes
 
+_FORCED = object()  # greedy()'s `next_token` for a forced row of a block: anything but None takes its torch.softmax branch
+
+
+def _block_tail(logits, idx, pos, targets, last_free, kw):
+    """Everything of a block of T decode steps behind Transformer.forward_block — the ONE place it lives: decode_n_tokens' eager
+    block and GraphedBlockDecoder's captured block both call it, so the two cannot drift.  logits [1, T, V]: forward_block's rows;
+    idx [1, T] / pos [T]: the steps' input tokens and positions; targets [T] int32: the forced token of each row, -1 for a free last
+    row (read with `logprobs` only: may be None without); last_free: the last row's token is drawn from its own row at its own
+    position, every other row is forced; kw: the sampling settings (GraphedDecoder._SETTINGS).
+    In order: `penalties.apply` over the T rows, `constraints.apply` (in place on the penalties' output), then per row the
+    probability row — greedy / sample, a forced greedy row being torch.softmax — or with `logprobs` one cc_logprob_rows /
+    cc_logprob_topn call over the model's own T rows, the free row's token drawn first and scored through `fallback`.
+    -> (the free last row's token or None, the T probability rows as a list or the TokenScores / TokenTopScores of T rows)."""
+    T = logits.shape[1]
+    pen, con = _active_penalties(kw.get("penalties")), _active_constraints(kw.get("constraints"))
+    temperature = kw.get("temperature")
+
+    def choose(row, p, forced):
+        if temperature is None:
+            return greedy(row, _FORCED if forced else None)
+        return sample(row, None, temperature, kw.get("top_k"), kw.get("seed", 0), p, top_p=kw.get("top_p"), min_p=kw.get("min_p"))
+
+    own = logits  # (the model's own rows: what logprobs scores)
+    if pen is not None:
+        logits = pen.apply(logits, idx, pos)
+    if con is not None:  # (in place on the penalties' output; the model's own rows stay as they are)
+        logits = con.apply(logits, idx, pos, out=logits if pen is not None else None)
+    if kw.get("logprobs", False):
+        fallback = last = None
+        if last_free:
+            last, _ = choose(logits[:, T - 1:T], pos[T - 1:T], False)
+            fallback = torch.zeros((T,), dtype=torch.int32, device=logits.device)
+            fallback[T - 1:] = last.view(1)
+        return last, _score_rows(own, targets, fallback, _check_top_logprobs(kw))
+    last, rows = None, []
+    for t in range(T):
+        free = last_free and t == T - 1
+        nt, npb = choose(logits[:, t:t + 1], pos[t:t + 1], not free)
+        rows.append(npb)
+        if free:
+            last = nt
+    return last, rows
+
+
+class GraphedBlockDecoder:
+    """A forced block — Transformer.forward_block over T = 2..4 known input tokens and the whole per-block tail (_block_tail) —
+    captured in a hipGraph, on GraphedDecoder's and GraphedStreamsDecoder's pattern.  One graph per (T, last_free)
+    under one set of settings (GraphedDecoder._SETTINGS, carried BY VALUE; `penalties` and `constraints` compare by identity behind
+    `active`), captured lazily — at most six — into one shared memory pool.  Each graph reads three static tensors of its own that the
+    host fills before a replay: `tok` [1, T], `pos` [T] and `targets` [T] (the forced token of each row; -1 for a free last row);
+    nothing else that moves between blocks is carried by value.  The captured work is one linear stream of launches.
+    Capture follows GraphedDecoder.capture: unseeded fused pipelines are seeded at pos[0:1], every cache buffer, `_next_valid`,
+    `_quant_pending` and the penalties' counts are snapshotted, `warmup` whole blocks run on a side stream with positions advancing by
+    T, and whatever happens the state handed in is put back.  All graphs are dropped and captured again when the settings differ,
+    when a cache's `_graph_epoch` moved (KVCacheRandom's per-generation seed) or when the model's caches were rebuilt
+    (setup_caches).  glue.w12_epoch is not watched: a block launches no packed-copy GEMV (the multi GEMVs stream the dense weights).
+    Before every replay a cache whose `_next_valid` is False is seeded again, so one decoder serves consecutive generations.  A capture that raises is logged in one line (`log`, default print) and that block and
+    every later one until `begin()` — decode_n_tokens calls it once per call — run as eager blocks.  CPU tensors
+    (tests/cpu_twin.py) pass through to the eager block.  `captures`, `replays` and `keys()` tell the routes apart."""
+
+    def __init__(self, model, warmup=1, log=None):
+        self.model, self.warmup, self.log = model, int(warmup), log
+        self.captures = self.replays = 0
+        self.refused = False
+        self.reset()
+
+    def reset(self):
+        """Drop every captured graph (and the pool they share)."""
+        self._graphs, self._pool, self.settings = {}, None, None
+        self._epoch = self._cache_set = None
+
+    def begin(self):
+        """A new decode_n_tokens call: a capture refused in an earlier call is tried again."""
+        self.refused = False
+
+    def keys(self):
+        """The captured (T, last_free) pairs."""
+        return set(self._graphs)
+
+    def _caches(self):
+        return [l.attention.kv_cache for l in self.model.layers]
+
+    _cache_epoch = GraphedDecoder._cache_epoch
+
+    @staticmethod
+    def _seed_pipelines(caches, pos):
+        """prepare_decode sits OUTSIDE the captured block: every cache whose fused pipeline is not seeded (a prefill, a reset, a
+        three-call step) is seeded at the block's first position."""
+        for c in caches:
+            if hasattr(c, "prepare_decode") and c.supports_fused_step() and not c._next_valid:
+                c.prepare_decode(pos[0:1])
+
+    @staticmethod
+    def _settings_of(kw):
+        s = dict(zip(GraphedDecoder._SETTINGS, (None, None, 0, None, None, False, None, None, None)))
+        s.update({k: kw[k] for k in s if k in kw})
+        s["logprobs"] = bool(s["logprobs"])
+        s["penalties"], s["constraints"] = _active_penalties(s["penalties"]), _active_constraints(s["constraints"])
+        s["top_logprobs"] = _check_top_logprobs(s)
+        return tuple(s[k] for k in GraphedDecoder._SETTINGS)
+
+    def capture(self, g, T, last_free, kw, attn_top_k=1.0):
+        """Capture the block of `g`'s static tensors.  Starts from a state where extra (discarded) blocks are harmless: they run on
+        a snapshot."""
+        caches = self._caches()
+        self._seed_pipelines(caches, g.pos)  # BEFORE the snapshot, so that the restored state is runnable
+        snap = [{k: v.clone() for k, v in c._buffers.items() if v is not None} for c in caches]
+        flags = [(getattr(c, "_next_valid", None), getattr(c, "_quant_pending", False)) for c in caches]
+        pos0 = g.pos.clone()
+        pen = _active_penalties(kw.get("penalties"))
+        pen_snap = pen.snapshot() if pen is not None else None  # (the warm-up blocks would be counted)
+
+        def block():
+            return _block_tail(self.model.forward_block(g.tok, g.pos, attn_top_k=attn_top_k), g.tok, g.pos, g.targets, last_free, kw)
+
+        try:
+            s = torch.cuda.Stream()
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s):
+                for _ in range(self.warmup):  # positions advance like a real decode (the pipelines assume +1 steps)
+                    block()
+                    g.pos += T
+            torch.cuda.current_stream().wait_stream(s)
+            if self._pool is None:
+                self._pool = torch.cuda.graph_pool_handle()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, pool=self._pool):
+                g.last, g.outs = block()
+            g.graph = graph
+        finally:  # also when the capture is refused: the caller falls back to eager blocks and must find the state it handed in
+            g.pos.copy_(pos0)
+            if pen is not None:
+                pen.restore(pen_snap)
+            for c, sn, fl in zip(caches, snap, flags):
+                for k, v in sn.items():
+                    c._buffers[k].copy_(v)
+                if fl[0] is not None:
+                    c._next_valid = fl[0]
+                c._quant_pending = fl[1]
+                if hasattr(c, "_ring_version"):  # ring and tracked window sums were restored together: still in step
+                    c._ring_version = c._ring_tag()
+
+    def _eager(self, idx, pos, targets, last_free, kw, attn_top_k):
+        return _block_tail(self.model.forward_block(idx, pos, attn_top_k=attn_top_k), idx, pos, targets, last_free, kw)
+
+    def __call__(self, idx, pos, targets, last_free, kw, attn_top_k=1.0):
+        """One block: idx [1, T], pos [T], targets [T] int32 (-1: the free last row) -> (tokens, rows or scores): T one-element
+        token tensors — the forced ones views of the static `targets`, a free last one the graph's own output — and what _block_tail
+        returns beside them.  Static tensors all: the caller clones what it keeps before the next call."""
+        T, last_free = int(idx.shape[1]), bool(last_free)
+        if not idx.is_cuda or self.refused or not 2 <= T <= _MAX_BLOCK:
+            last, outs = self._eager(idx, pos, targets, last_free, kw, attn_top_k)
+            return [targets[t:t + 1] for t in range(T - 1)] + [last if last_free else targets[T - 1:]], outs
+        caches = self._caches()
+        settings = self._settings_of(kw)
+        if self._graphs:
+            self._seed_pipelines(caches, pos)  # (KVCacheRandom's first seeding of a generation moves the epoch)
+            same = self._cache_set is not None and len(caches) == len(self._cache_set) and all(a is b for a, b in zip(caches, self._cache_set))
+            if settings != self.settings or not same or self._cache_epoch() != self._epoch:
+                self.reset()
+        g = self._graphs.get((T, last_free))
+        if g is None:
+            dev = idx.device
+            g = SimpleNamespace(tok=torch.zeros((1, T), dtype=torch.int32, device=dev), pos=torch.zeros((T,), dtype=torch.int32, device=dev),
+                                targets=torch.full((T,), -1, dtype=torch.int32, device=dev), graph=None, last=None, outs=None)
+            g.tok.copy_(idx)
+            g.pos.copy_(pos)
+            g.targets.copy_(targets)
+            try:
+                self.capture(g, T, last_free, kw, attn_top_k)
+            except Exception as e:  # capture refused: the state is as it was handed in (capture's finally)
+                (print if self.log is None else self.log)(f"hipGraph capture of a forced block of {T} failed ({type(e).__name__}: {e}); "
+                                                          "falling back to eager blocks")
+                self.refused = True
+                return self(idx, pos, targets, last_free, kw, attn_top_k)
+            if not self._graphs:
+                self.settings, self._cache_set = settings, caches
+            self._epoch = self._cache_epoch()
+            self._graphs[(T, last_free)] = g
+            self.captures += 1
+        g.tok.copy_(idx)
+        g.pos.copy_(pos)
+        g.targets.copy_(targets)
+        self._seed_pipelines(caches, g.pos)
+        g.graph.replay()
+        self.replays += 1
+        return [g.targets[t:t + 1] for t in range(T - 1)] + [g.last if last_free else g.targets[T - 1:]], g.outs
+
 _L2_HANDOFF_DEMOTED = set()  # device indices on which the recovery path demoted the L2-resident hand-off: generate() restores them
 
 
@@ -747,8 +936,9 @@ def decode_n_tokens(model, cur_token, input_pos, decode_one_token, num_new_token
     are forced (their outputs, the inputs of i+1 .. i+T-1, are then known) — every dense product of a layer is one pass over its
     weights for the T tokens, the layer's T cache steps run in order, and the T results are committed in order exactly as the single
     steps commit them (the last step of a block may be a free one: its token is drawn from its own row at its own position).
-    Blocks are eager launches; everything else — free steps, fewer than two known inputs, an ineligible model — runs through
-    `decode_one_token` as before.  A single-launch step that fails INSIDE a block cannot be rewound token-wise (earlier layers have
+    Blocks are eager launches, or with `block_decoder` (ours; default None: this loop as it was; a GraphedBlockDecoder built for this
+    model, else ValueError) replays of a captured hipGraph per (T, last step free); everything else — free steps, fewer than two
+    known inputs, an ineligible model — runs through `decode_one_token` as before, and the decoder captures nothing.  A single-launch step that fails INSIDE a block cannot be rewound token-wise (earlier layers have
     committed all T tokens): with `recover` the status word is read once behind each block, and a set word raises.
     `logprobs` (ours; default False: this loop as it was): the second result is not the list of V-sized probability rows but
     TokenScores(logprob, rank), one element per committed token in commit order (trimmed with the tokens when the loop rewinds).  A
@@ -772,8 +962,13 @@ def decode_n_tokens(model, cur_token, input_pos, decode_one_token, num_new_token
     top_n = _check_top_logprobs(kw)
     recover = kw.pop("recover", None)
     block = kw.pop("forced_block", 1)
+    block_decoder = kw.pop("block_decoder", None)
+    if block_decoder is not None and block_decoder.model is not model:
+        raise ValueError("decode_n_tokens: block_decoder was built for another model")
     block = 1 if block is None else max(1, min(int(block), _MAX_BLOCK))
     use_blocks = block > 1 and prefix is not None and len(prefix) > 0 and bool(getattr(model, "block_eligible", lambda *_: False)(attn_top_k))
+    if block_decoder is not None:
+        block_decoder.begin()
     tp = _tp_world() > 1
     recover = (cur_token.is_cuda and not tp) if recover is None else bool(recover)
     watch = _StatusWatch(cur_token.device) if recover and not tp else None
@@ -810,11 +1005,7 @@ def decode_n_tokens(model, cur_token, input_pos, decode_one_token, num_new_token
         T = min(block, num_new_tokens - k, len(prefix) - k + 1)
         return T if T >= 2 else 0
 
-    def run_block(k, T):
-        """steps k .. k+T-1 through model.forward_block; commits T results in order."""
-        idx = torch.cat([cur.view(1, 1), prefix[k:k + T - 1].view(1, -1).to(cur.dtype)], 1)
-        pos = input_pos + torch.arange(T, device=input_pos.device, dtype=input_pos.dtype)
-        logits = model.forward_block(idx, pos, attn_top_k=attn_top_k)
+    def check_block_status(T, pos):
         if recover and cur_token.is_cuda and _collective_status(cur_token.device):
             from ..attention_utils import raise_single_launch_failure
 
@@ -822,37 +1013,27 @@ def decode_n_tokens(model, cur_token, input_pos, decode_one_token, num_new_token
                 raise_single_launch_failure(cur_token.device)  # (clears the word)
             except Exception as e:
                 raise type(e)(f"in the block of {T} forced decode steps starting at position {int(pos[0])}: {e}") from None
-        own = logits  # (the model's own rows: what logprobs scores)
-        if pen is not None:
-            logits = pen.apply(logits, idx, pos)
-        if con is not None:  # (in place on the penalties' output; the model's own rows stay as they are)
-            logits = con.apply(logits, idx, pos, out=logits if pen is not None else None)
-        if logprobs:
-            n_forced = min(T, len(prefix) - k)  # T or T - 1: only the last step of a block may be a free one
-            targets = torch.full((T,), -1, dtype=torch.int32, device=logits.device)
+
+    def run_block(k, T):
+        """steps k .. k+T-1 through model.forward_block (eager launches, or `block_decoder`'s captured block); commits T results
+        in order."""
+        idx = torch.cat([cur.view(1, 1), prefix[k:k + T - 1].view(1, -1).to(cur.dtype)], 1)
+        pos = input_pos + torch.arange(T, device=input_pos.device, dtype=input_pos.dtype)
+        n_forced = min(T, len(prefix) - k)  # T or T - 1: only the last step of a block may be a free one
+        targets = None
+        if logprobs or block_decoder is not None:
+            targets = torch.full((T,), -1, dtype=torch.int32, device=idx.device)
             targets[:n_forced] = prefix[k:k + n_forced]
-            fallback = last = None
-            if n_forced < T:
-                row = logits[:, T - 1:T]
-                if kw.get("temperature") is None:
-                    last, _ = greedy(row, None)
-                else:
-                    last, _ = sample(row, None, kw["temperature"], kw.get("top_k"), kw.get("seed", 0), pos[T - 1:T], top_p=kw.get("top_p"),
-                                     min_p=kw.get("min_p"))
-                fallback = torch.zeros((T,), dtype=torch.int32, device=logits.device)
-                fallback[T - 1:] = last.view(1)
-            scores = _score_rows(own, targets, fallback, top_n)
-            for t in range(T):
-                commit(k + t, forced_at(k + t) if t < n_forced else last, type(scores)(*(s[t:t + 1] for s in scores)))
-            return
+        if block_decoder is not None:
+            toks, outs = block_decoder(idx, pos, targets, n_forced < T, kw, attn_top_k=attn_top_k)
+            last = toks[T - 1]
+            check_block_status(T, pos)
+        else:
+            logits = model.forward_block(idx, pos, attn_top_k=attn_top_k)
+            check_block_status(T, pos)
+            last, outs = _block_tail(logits, idx, pos, targets, n_forced < T, kw)
         for t in range(T):
-            row = logits[:, t:t + 1]
-            if kw.get("temperature") is None:
-                nt, npb = greedy(row, forced_at(k + t))
-            else:
-                nt, npb = sample(row, forced_at(k + t), kw["temperature"], kw.get("top_k"), kw.get("seed", 0), pos[t:t + 1],
-                                 top_p=kw.get("top_p"), min_p=kw.get("min_p"))
-            commit(k + t, nt, npb)
+            commit(k + t, forced_at(k + t) if t < n_forced else last, type(outs)(*(s[t:t + 1] for s in outs)) if logprobs else outs[t])
 
     while True:
         running = i < num_new_tokens and not stopped
@@ -916,8 +1097,12 @@ def generate(model, prompt, prefill, decode_one_token, max_new_tokens, next_toke
     `constraints=LogitConstraints(...)` (ours): n-gram blocking, banned sequences and a minimum number of new tokens on every row a
     token is chosen from, behind the penalties, with the token history on the device by position; the object is reset with the tokens
     that are prefilled and the same `gen_start` as the penalties.  A ValueError before the prefill when the prompt and the new tokens
-    do not fit its `max_positions`."""
+    do not fit its `max_positions`.
+    `block_decoder=GraphedBlockDecoder(model)` (ours, with `forced_block` > 1): the blocks are replayed from captured hipGraphs; a
+    decoder built for another model is a ValueError before anything runs."""
     _check_top_logprobs(kw)
+    if kw.get("block_decoder") is not None and kw["block_decoder"].model is not model:
+        raise ValueError("generate: block_decoder was built for another model")
     prompt_length = prompt.size(0)
     device, dtype = prompt.device, prompt.dtype
     gen_start = prompt_length  # (penalties: a prompt tail that is fed through decode steps below still counts as prompt)

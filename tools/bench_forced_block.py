@@ -6,10 +6,12 @@ Llama-3-8B (bf16, random weights), heavy_hitter, cache 4096.  Behind a prefill a
     forced_block = 1, hipGraph decoder    (what generate() callers run today)
     forced_block = 4                      (blocks are eager launches; status word read behind each block)
     forced_block = 4, recover=False       (no status read: the host runs ahead of the device)
+    forced_block = 4, captured blocks     (block_decoder=GraphedBlockDecoder: each block one hipGraph replay)
 
 in alternating order, `--rounds` times each; tokens/s is the median.  Then the HIP-event time of cc_gemv_fused_multi (T = 4) against
 cc_gemv_fused per matrix (wqkv, wo, w1/w3, w2 over the 32 layers' own weights, so every launch streams cold weights; the LM head).
-Prints one JSON object; profiles/forced_block.md is written from it.
+Prints one JSON object; profiles/forced_block.md and profiles/forced_block_graph.md are written from it.  --no_gemv leaves the
+per-matrix part out.
 
 --weights int8 / mxfp4 quantises the random model with the weight-only handler (harness/quantize.py, as tools/run_configs.py
 --weights does) and sets Transformer.block_weight_only: the blocks and the per-matrix table then run cc_gemv_fused_w8_multi /
@@ -17,7 +19,7 @@ cc_gemv_fused_mx4_multi against cc_gemv_fused_w8 / cc_gemv_fused_mx4 (profiles/f
 --groupsize G does the same with the int4 handler and Transformer.block_int4: cc_gemv_fused_w4_multi against cc_gemv_fused_w4
 (profiles/w4_multi.md).  Default bf16: as it was.
 
-    python tools/bench_forced_block.py [--n_layer 32] [--tokens 256] [--rounds 5] [--weights bf16|int8|mxfp4|int4] [--groupsize G] [--out FILE]"""
+    python tools/bench_forced_block.py [--n_layer 32] [--tokens 256] [--rounds 5] [--weights bf16|int8|mxfp4|int4] [--groupsize G] [--no_gemv] [--out FILE]"""
 import argparse
 import json
 import os
@@ -73,9 +75,10 @@ def main():
     ap.add_argument("--settle", type=int, default=160)
     ap.add_argument("--weights", default="bf16", choices=["bf16", "int8", "mxfp4", "int4"])
     ap.add_argument("--groupsize", type=int, default=128, choices=[32, 64, 128, 256], help="--weights int4: columns per group")
+    ap.add_argument("--no_gemv", action="store_true", help="the loop modes only: no per-matrix GEMV table")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    from cold_compress_amd.harness import GraphedDecoder, decode_n_tokens, decode_one_token, glue, prefill, setup_caches
+    from cold_compress_amd.harness import GraphedBlockDecoder, GraphedDecoder, decode_n_tokens, decode_one_token, glue, prefill, setup_caches
     from cold_compress_amd.harness.model import _gemv_multi, _quant
 
     dev = torch.device("cuda", 0)
@@ -93,6 +96,7 @@ def main():
         pos = torch.tensor([args.prompt_len], dtype=torch.int32, device=dev)
         cur = tok.view(1, 1).to(torch.int32)
         graphed = GraphedDecoder(model)
+        blocks = GraphedBlockDecoder(model)
 
         def feed(n, dec, **kw):
             nonlocal cur
@@ -107,7 +111,8 @@ def main():
 
         feed(args.settle, graphed)  # clocks settle, the graph is captured (bench.py does the same ahead of its timed region)
         modes = {"eager_1": (decode_one_token, {}), "graphed_1": (graphed, {}), "block_4": (decode_one_token, {"forced_block": 4}),
-                 "block_4_norecover": (decode_one_token, {"forced_block": 4, "recover": False})}
+                 "block_4_norecover": (decode_one_token, {"forced_block": 4, "recover": False}),
+                 "block_4_graph": (decode_one_token, {"forced_block": 4, "block_decoder": blocks})}
         names = list(modes)
         for m in names:  # one untimed pass of every mode
             feed(16, modes[m][0], **modes[m][1])
@@ -151,7 +156,7 @@ def main():
                         lambda i: glue.gemv_fused(model.output.weight, x4[0], delta=d4[0], norm_weight=model.norm.weight, **_quant(model.output))),
         }
         gemv = {}
-        for name, (n, multi, single) in mats.items():
+        for name, (n, multi, single) in ({} if args.no_gemv else mats).items():
             reps = 4 if n > 1 else 8
             runs = {"single": lambda: [single(i) for _ in range(reps) for i in range(n)]}
             for T in (2, 3, 4):
@@ -167,7 +172,8 @@ def main():
     out = {"shape": "Meta-Llama-3-8B-Instruct", "weights": args.weights, **({"groupsize": args.groupsize} if args.weights == "int4" else {}), "n_layer": args.n_layer, "cache_len": args.cache_len, "tokens": args.tokens, "rounds": args.rounds,
            "device": torch.cuda.get_device_name(0),
            "tokens_per_s": {m: {"median": round(statistics.median(v), 1), "min": round(min(v), 1), "max": round(max(v), 1)} for m, v in tps.items()},
-           "ms_per_token": {m: round(1e3 / statistics.median(v), 3) for m, v in tps.items()}, "gemv_us": gemv}
+           "ms_per_token": {m: round(1e3 / statistics.median(v), 3) for m, v in tps.items()},
+           "captured_blocks": {"captures": blocks.captures, "replays": blocks.replays, "keys": sorted(blocks.keys())}, "gemv_us": gemv}
     text = json.dumps(out, indent=1)
     print(text)
     if args.out:
