@@ -43,6 +43,38 @@ class KVView(C.Structure):
     ]
 
 
+class PenaltyRow(C.Structure):
+    """struct cc_penalty_row_t (include/coldcompress.h): one row's state and settings for cc_logits_penalize_streams."""
+
+    _fields_ = [
+        ("prompt_count", C.c_void_p),
+        ("gen_count", C.c_void_p),
+        ("gen_start", C.c_void_p),
+        ("bias", C.c_void_p),
+        ("r", C.c_float),
+        ("f", C.c_float),
+        ("p", C.c_float),
+    ]
+
+
+class ConstraintRow(C.Structure):
+    """struct cc_constraint_row_t (include/coldcompress.h): one row's state and settings for cc_logits_constrain_streams."""
+
+    _fields_ = [
+        ("hist", C.c_void_p),
+        ("cap", C.c_int32),
+        ("gen_start", C.c_void_p),
+        ("ngram", C.c_int32),
+        ("ngram_from_gen", C.c_int32),
+        ("min_new_tokens", C.c_int32),
+        ("term_ids", C.c_void_p),
+        ("n_term", C.c_int32),
+        ("bw_tokens", C.c_void_p),
+        ("bw_offsets", C.c_void_p),
+        ("n_bw", C.c_int32),
+    ]
+
+
 _vp, _i32, _f32, _sz = C.c_void_p, C.c_int32, C.c_float, C.c_size_t
 _view = C.POINTER(KVView)
 
@@ -81,7 +113,9 @@ SIGNATURES = {
     "cc_token_history_write": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp]),
     "cc_logits_constrain": (C.c_int, [_vp, _vp, _i32, _i32, C.c_int64, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp,
                                       _i32, _vp]),
-    "cc_gemv_fused": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
+    "cc_logits_penalize_streams": (C.c_int, [_vp, _vp, _i32, _i32, C.c_int64, _i32, C.POINTER(PenaltyRow), _vp, _vp, _vp]),
+    "cc_logits_constrain_streams": (C.c_int, [_vp, _vp, _i32, _i32, C.c_int64, _i32, C.POINTER(ConstraintRow), _vp, _vp, _vp]),
+    "cc_gemv_fused":(C.c_int, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
     "cc_gemv_fused_multi": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     "cc_w12_geometry": (C.c_int, [_i32, _i32, _i32, _vp]),
     "cc_w12_meta_words": (_sz, []),
@@ -217,6 +251,8 @@ DEVICE_ONLY = {"cc_error_string", "cc_device_info", "cc_decode_step_single_launc
                "cc_logprob_topn_workspace_bytes", "cc_logprob_topn",  # the N best alternatives of a row: the float64 order and values (tests/logprob_topn_twin.py)
                "cc_token_counts_add", "cc_logits_penalize",  # token-history penalties: the fp32 torch twin of the contract (tests/penalty_twin.py)
                "cc_token_history_write", "cc_logits_constrain",  # n-gram blocking, banned sequences, minimum length: the plain-Python twin (tests/constraint_twin.py)
+               # the two for rows of different sequences: their checkers are cc_logits_penalize / cc_logits_constrain themselves at T = 1, bit for bit
+               "cc_logits_penalize_streams", "cc_logits_constrain_streams",
                # the fused quantised cache's ring and hybrid steps: their checker is the same policy's 16-bit step on the dequantised values
                "cc_decode_step_heavy_hitter_ring_quant", "cc_decode_step_hybrid_quant_rc", "cc_decode_step_hybrid_quant_single_launch",
                # inter-GPU transport: no CPU twin (the oracle of the all-reduce is torch.distributed's)

@@ -11,6 +11,9 @@
 //                  with.  The last workgroup of a row does the terminators and the banned sequences, and that of row 0 stores the T
 //                  history words.  Several threads may store -inf to one element: the same value, so no atomics; no workgroup waits
 //                  for another.
+//   ban_streams    the ban pass for T rows of DIFFERENT sequences (cc_logits_constrain_streams): grid (largest slice count of the rows
+//                  + 1, T), blockIdx.y selects the row's record (its own history, cap, gen_start and rules, carried in the kernel
+//                  arguments by value) and the row sits at its own pos[t]; both passes end in con_row, the bans of one row.
 // A token read from hist or tokens is compared as an integer and becomes an address only behind the [0, V) check.
 #include "cc_common.h"
 
@@ -79,18 +82,12 @@ __device__ __forceinline__ int con_elem(const ConArgs& a, int pos0, long long j)
   return (a.tokens && j >= (long long)pos0) ? a.tokens[j - pos0] : a.hist[j];
 }
 
+// The bans of ONE row at position p of the sequence `a` describes (a.tokens: the inputs from position pos0 on), by the workgroup x of
+// a.slices + 1 that work on the row: both entry points' kernels end here, so a row's bits are the same from either.
 template <typename U>
-__global__ __launch_bounds__(kConThreads) void logits_constrain_kernel(U* out, ConArgs a) {
-  __shared__ int tail[CC_CONSTRAIN_MAX_NGRAM];
-  const int t = blockIdx.y, pos0 = a.pos[0];
-  const long long p = (long long)pos0 + t;  // the row's position: its history is s[0 .. p]
-  const bool misc = (int)blockIdx.x == a.slices;
-  if (misc && t == 0 && a.tokens && (int)threadIdx.x < a.T) {  // hist[pos0 + k] = tokens[k]: positions no row of this launch reads from hist
-    const long long q = (long long)pos0 + threadIdx.x;
-    if (q >= 0 && q < (long long)a.cap) a.hist[q] = a.tokens[threadIdx.x];
-  }
+__device__ __forceinline__ void con_row(U* row, const ConArgs& a, int pos0, long long p, int x, int* tail) {
+  const bool misc = x == a.slices;
   if (p < 0 || p >= (long long)a.cap) return;  // (block-uniform) a position outside the history: the row stays as it is
-  U* row = out + (size_t)t * (size_t)a.row_stride;
   const U ninf = con_neg_inf<U>();
   if (misc) {
     const long long gs = a.gen_start[0];
@@ -123,7 +120,7 @@ __global__ __launch_bounds__(kConThreads) void logits_constrain_kernel(U* out, C
   if (last < i0) return;  // (block-uniform: in front of the barrier)
   if ((int)threadIdx.x < n - 1) tail[threadIdx.x] = con_elem(a, pos0, p - n + 2 + threadIdx.x);
   __syncthreads();
-  for (long long s0 = i0 + (long long)blockIdx.x * CC_CONSTRAIN_SLICE; s0 <= last; s0 += (long long)a.slices * CC_CONSTRAIN_SLICE) {
+  for (long long s0 = i0 + (long long)x * CC_CONSTRAIN_SLICE; s0 <= last; s0 += (long long)a.slices * CC_CONSTRAIN_SLICE) {
 #pragma unroll
     for (int c = 0; c < CC_CONSTRAIN_SLICE / kConThreads; c++) {
       const long long i = s0 + c * kConThreads + threadIdx.x;
@@ -138,8 +135,57 @@ __global__ __launch_bounds__(kConThreads) void logits_constrain_kernel(U* out, C
 }
 
 template <typename U>
+__global__ __launch_bounds__(kConThreads) void logits_constrain_kernel(U* out, ConArgs a) {
+  __shared__ int tail[CC_CONSTRAIN_MAX_NGRAM];
+  const int t = blockIdx.y, pos0 = a.pos[0];
+  const long long p = (long long)pos0 + t;  // the row's position: its history is s[0 .. p]
+  if ((int)blockIdx.x == a.slices && t == 0 && a.tokens && (int)threadIdx.x < a.T) {  // hist[pos0 + k] = tokens[k]: positions no row of
+    const long long q = (long long)pos0 + threadIdx.x;                                // this launch reads from hist
+    if (q >= 0 && q < (long long)a.cap) a.hist[q] = a.tokens[threadIdx.x];
+  }
+  con_row<U>(out + (size_t)t * (size_t)a.row_stride, a, pos0, p, (int)blockIdx.x, tail);
+}
+
+template <typename U>
 void con_launch(void* out, const ConArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(logits_constrain_kernel<U>, dim3((unsigned int)a.slices + 1u, (unsigned int)a.T), dim3(kConThreads), 0, st, (U*)out, a);
+}
+
+// ---- rows of DIFFERENT sequences (cc_logits_constrain_streams): blockIdx.y is the row and selects its record; the row sits at its own
+//      position pos[t] over its own history, whose last element is tokens[t].  The grid's x extent is the largest slice count of the
+//      rows + 1; a row with fewer slices lets the workgroups it has no use for return, and its last workgroup in use does the rest.
+struct ConRows {
+  cc_constraint_row_t row[CC_GEMV_MULTI_MAX_T];
+};
+
+__host__ __device__ __forceinline__ int con_slices(int cap, int ngram) {  // (from cap, not *pos: a captured launch keeps its grid as the
+  const long long slices = ((long long)cap + CC_CONSTRAIN_SLICE - 1) / CC_CONSTRAIN_SLICE;  //  history grows)
+  return ngram > 0 ? (int)(slices < kConMaxSlices ? slices : kConMaxSlices) : 0;
+}
+
+template <typename U>
+__global__ __launch_bounds__(kConThreads) void logits_constrain_streams_kernel(U* out, int V, long long row_stride, ConRows rows,
+                                                                               const int32_t* tokens, const int32_t* pos) {
+  __shared__ int tail[CC_CONSTRAIN_MAX_NGRAM];
+  const int t = blockIdx.y;
+  const cc_constraint_row_t s = rows.row[t];
+  if (!s.hist) return;  // no rules for this stream: the row as it is
+  ConArgs a;
+  a.T = 1, a.V = V, a.cap = s.cap, a.ngram = s.ngram, a.ngram_from_gen = s.ngram_from_gen, a.min_new_tokens = s.min_new_tokens;
+  a.n_term = s.min_new_tokens > 0 ? s.n_term : 0, a.n_bw = s.n_bw, a.slices = con_slices(s.cap, s.ngram);
+  a.row_stride = row_stride, a.hist = s.hist, a.tokens = tokens ? tokens + t : nullptr, a.pos = pos + t, a.gen_start = s.gen_start;
+  a.term_ids = s.term_ids, a.bw_tokens = s.bw_tokens, a.bw_offsets = s.bw_offsets;
+  if ((int)blockIdx.x > a.slices) return;  // (block-uniform) more workgroups than this row's history has slices
+  const int pos0 = pos[t];
+  if ((int)blockIdx.x == a.slices && tokens && threadIdx.x == 0 && pos0 >= 0 && pos0 < s.cap) s.hist[pos0] = tokens[t];
+  con_row<U>(out + (size_t)t * (size_t)row_stride, a, pos0, (long long)pos0, (int)blockIdx.x, tail);
+}
+
+template <typename U>
+void con_streams_launch(void* out, int T, int V, long long row_stride, const ConRows& rows, int slices, const int32_t* tokens,
+                        const int32_t* pos, hipStream_t st) {
+  hipLaunchKernelGGL(logits_constrain_streams_kernel<U>, dim3((unsigned int)slices + 1u, (unsigned int)T), dim3(kConThreads), 0, st,
+                     (U*)out, V, row_stride, rows, tokens, pos);
 }
 
 template <typename U>
@@ -192,8 +238,7 @@ extern "C" int cc_logits_constrain(const void* logits, void* out, int32_t T, int
   ConArgs a;
   a.T = T, a.V = V, a.cap = cap, a.ngram = ngram, a.ngram_from_gen = ngram_from_gen != 0, a.min_new_tokens = min_new_tokens;
   a.n_term = min_new_tokens > 0 ? n_term : 0, a.n_bw = n_bw;
-  const long long slices = ((long long)cap + CC_CONSTRAIN_SLICE - 1) / CC_CONSTRAIN_SLICE;  // (from cap, not *pos: a captured launch
-  a.slices = ngram > 0 ? (int)(slices < kConMaxSlices ? slices : kConMaxSlices) : 0;         //  keeps its grid as the history grows)
+  a.slices = con_slices(cap, ngram);
   a.row_stride = row_stride, a.hist = hist, a.tokens = tokens, a.pos = pos, a.gen_start = gen_start, a.term_ids = term_ids;
   a.bw_tokens = bw_tokens, a.bw_offsets = bw_offsets;
   switch (dtype) {
@@ -205,6 +250,58 @@ extern "C" int cc_logits_constrain(const void* logits, void* out, int32_t T, int
       break;
     default:
       con_launch<con_f16>(out, a, st);
+      break;
+  }
+  CC_LAUNCH_CHECK();
+  return CC_OK;
+}
+
+extern "C" int cc_logits_constrain_streams(const void* logits, void* out, int32_t T, int32_t V, int64_t row_stride, int32_t dtype,
+                                           const cc_constraint_row_t* rows, const int32_t* tokens, const int32_t* pos, cc_stream_t stream) {
+  CC_ENTRY();
+  if (!logits || !out || !rows || !pos || T < 1 || T > CC_GEMV_MULTI_MAX_T || V <= 0 || row_stride < (int64_t)V) return CC_ERR_BAD_ARG;
+  ConRows cr{};
+  int slices = 0;
+  for (int t = 0; t < T; t++) {  // cc_logits_constrain's refusals, per record; hist NULL: no rules for that row
+    const cc_constraint_row_t& s = rows[t];
+    if (!s.hist) continue;
+    if (!s.gen_start || s.cap <= 0) return CC_ERR_BAD_ARG;
+    if (s.ngram < 0 || s.ngram > CC_CONSTRAIN_MAX_NGRAM || s.min_new_tokens < 0 || s.n_term < 0 || s.n_term > CC_CONSTRAIN_MAX_TERMINATORS ||
+        (s.n_term > 0 && !s.term_ids) || s.n_bw < 0 || s.n_bw > CC_CONSTRAIN_MAX_BW || (s.n_bw > 0 && (!s.bw_tokens || !s.bw_offsets)))
+      return CC_ERR_BAD_ARG;
+    if ((((uintptr_t)s.hist | (uintptr_t)s.gen_start | (uintptr_t)s.term_ids | (uintptr_t)s.bw_tokens | (uintptr_t)s.bw_offsets) & 3u) != 0)
+      return CC_ERR_BAD_ARG;
+    for (int u = 0; u < t; u++)  // two rows on one history would race
+      if (rows[u].hist == s.hist) return CC_ERR_BAD_ARG;
+    cr.row[t] = s;
+    cr.row[t].ngram_from_gen = s.ngram_from_gen != 0;
+    const int sl = con_slices(s.cap, s.ngram);
+    slices = sl > slices ? sl : slices;
+  }
+  if ((((uintptr_t)tokens | (uintptr_t)pos) & 3u) != 0) return CC_ERR_BAD_ARG;
+  const size_t esz = cc_dt_ok(dtype) ? cc_dt_size(dtype) : 2;  // (an unknown dtype: the smallest element, so that every bad argument
+  if ((((uintptr_t)logits | (uintptr_t)out) & (esz - 1)) != 0) return CC_ERR_BAD_ARG;  //  is named before the dtype)
+  if (out != logits) {  // the same rows in place, or rows that share nothing
+    const uintptr_t a = (uintptr_t)logits, b = (uintptr_t)out;
+    const uintptr_t span = (uintptr_t)(((size_t)(T - 1) * (size_t)row_stride + (size_t)V) * esz);
+    if (a < b + span && b < a + span) return CC_ERR_BAD_ARG;
+  }
+  if (!cc_dt_ok(dtype)) return CC_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  if (out != logits) {
+    if (dtype == CC_DT_F32) con_copy_launch<uint32_t>(logits, out, T, V, row_stride, st);
+    else con_copy_launch<uint16_t>(logits, out, T, V, row_stride, st);
+    CC_LAUNCH_CHECK();
+  }
+  switch (dtype) {
+    case CC_DT_F32:
+      con_streams_launch<uint32_t>(out, T, V, row_stride, cr, slices, tokens, pos, st);
+      break;
+    case CC_DT_BF16:
+      con_streams_launch<con_bf16>(out, T, V, row_stride, cr, slices, tokens, pos, st);
+      break;
+    default:
+      con_streams_launch<con_f16>(out, T, V, row_stride, cr, slices, tokens, pos, st);
       break;
   }
   CC_LAUNCH_CHECK();

@@ -149,6 +149,11 @@ class LogitConstraints:
         else:
             self.hist[:tokens.numel()] = tokens
 
+    def record(self):
+        """This sequence's row of glue.logits_constrain_streams: the state's tensors and the settings as the kernel receives them."""
+        return (self.hist, self.gen_start, self.no_repeat_ngram_size, self.ngram_scope == "generated", self.min_new_tokens, self._terms,
+                self._bw_tokens, self._bw_offsets)
+
     def apply(self, logits, tokens=None, pos=None, out=None):
         """logits [1, T, V], T <= 4: the rows of T steps at the consecutive positions pos[0] .. pos[0] + T - 1 (`pos`: at least one
         element, on the logits' device); tokens: those steps' input tokens (T elements), or None for the prefill's row, whose history

@@ -4,7 +4,8 @@ These are NOT part of the cache/attention hot path — they are the
 (ref: model.py:317-327, 375-387, 442-443, 452-457, 507-519), which the reference leaves to ~45 eager elementwise
 launches per layer or to torch.compile.  On device tensors they call the C ABI (`cc_add_rmsnorm`, `cc_qkv_rope`,
 `cc_silu_mul`, `cc_gemv_fused`, `cc_gemv_fused_multi` and its int8 / MXFP4 / int4 forms, `cc_softmax_argmax`, `cc_sample_topk`, `cc_sample_nucleus`, `cc_sample_rows`, `cc_logprob_rows`, `cc_logprob_topn`,
-`cc_token_counts_add`, `cc_logits_penalize`, `cc_token_history_write`, `cc_logits_constrain`); CPU tensors raise — there is no host path in the package (the
+`cc_token_counts_add`, `cc_logits_penalize`, `cc_token_history_write`, `cc_logits_constrain`, `cc_logits_penalize_streams`,
+`cc_logits_constrain_streams`); CPU tensors raise — there is no host path in the package (the
 CPU model-wiring test brings its own eager twins: tests/host_glue.py).
 """
 import ctypes as C
@@ -742,4 +743,103 @@ def logits_constrain(logits_2d, hist, gen_start, tokens, pos, ngram=0, ngram_fro
     _abi.call("cc_logits_constrain", _p(x), _p(y), T, V, int(stride), _DT[x.dtype], _p(hist), hist.numel(), _p(tokens), _p(pos),
               _p(gen_start), int(ngram), int(bool(ngram_from_gen)), int(min_new_tokens), _p(term_ids),
               0 if term_ids is None else term_ids.numel(), _p(bw_tokens), _p(bw_offsets), n_bw, _stream())
+    return logits_2d if inplace else y
+
+
+def _streams_rows(what, logits_2d, states, tokens, pos, out):
+    """The checks the two streams entry points share -> (x, y, T, V, stride, inplace)."""
+    if not logits_2d.is_cuda:
+        _host(logits_2d, f"{what} logits")
+    x = logits_2d
+    if x.dim() != 2 or x.dtype not in _DT:
+        raise _abi.ColdCompressError(f"{what}: logits must be [T, V] in float32 / bfloat16 / float16, got {x.dtype} {tuple(x.shape)}")
+    T, V = x.shape
+    if not 1 <= T <= GEMV_MULTI_MAX_T:
+        raise _abi.ColdCompressError(f"{what}: 1..{GEMV_MULTI_MAX_T} rows per call, got {T}")
+    if len(states) != T:
+        raise _abi.ColdCompressError(f"{what}: {T} rows need {T} records, got {len(states)}")
+    inplace = out is not None
+    if inplace and out is not logits_2d:
+        raise _abi.ColdCompressError(f"{what}: out must be None or the logits tensor itself")
+    if V > 1 and x.stride(1) != 1 or (T > 1 and x.stride(0) < V):
+        if inplace:
+            raise _abi.ColdCompressError(f"{what}: in place needs rows of unit element stride that do not overlap")
+        x = x.contiguous()
+    stride = x.stride(0) if T > 1 else V
+    for name, t in (("tokens", tokens), ("pos", pos)):
+        if t is not None:
+            _i32_ok(what, name, t, T)
+    y = x if inplace else torch.empty((T, stride), dtype=x.dtype, device=x.device)[:, :V]  # (one row stride serves both sides)
+    return x, y, T, V, int(stride), inplace
+
+
+def logits_penalize_streams(logits_2d, states, tokens=None, pos=None, out=None):
+    """logits_penalize for T <= 4 rows that belong to DIFFERENT sequences, in one launch (cc_logits_penalize_streams;
+    include/coldcompress.h has the contract): row t is penalised against states[t] alone and carries the bits logits_penalize gives for
+    that row at T = 1 on that state.  states: T records, each None (no penalties for the row: its bits as they are) or
+    (prompt_count, gen_count, gen_start, repetition_penalty, frequency_penalty, presence_penalty, bias) as logits_penalize takes them;
+    no two records may name one count table.  tokens / pos: int32 DEVICE tensors of T elements — row t's input token and its own
+    position — or both None: count nothing.  out: None (a new contiguous tensor) or `logits_2d` itself (in place).  -> out."""
+    what = "logits_penalize_streams"
+    if (tokens is None) != (pos is None):
+        raise _abi.ColdCompressError(f"{what}: tokens and pos come together")
+    x, y, T, V, stride, inplace = _streams_rows(what, logits_2d, states, tokens, pos, out)
+    recs = (_abi.PenaltyRow * T)()
+    tables = set()
+    for t, s in enumerate(states):
+        if s is None:
+            continue
+        prompt_count, gen_count, gen_start, r, f, p, bias = s
+        _counts_ok(what, V, prompt_count, gen_count, gen_start)
+        if bias is not None and not (bias.is_cuda and bias.dtype == torch.float32 and bias.numel() == V and bias.is_contiguous()):
+            raise _abi.ColdCompressError(f"{what}: bias must be a contiguous float32 device tensor of {V} elements, got {bias.dtype} "
+                                         f"{tuple(bias.shape)} on {bias.device}")
+        for c in (prompt_count, gen_count):
+            if c.data_ptr() in tables:
+                raise _abi.ColdCompressError(f"{what}: record {t} names a count table that another record names: one object is one sequence's state")
+        tables.update((prompt_count.data_ptr(), gen_count.data_ptr()))
+        recs[t] = _abi.PenaltyRow(prompt_count.data_ptr(), gen_count.data_ptr(), gen_start.data_ptr(), None if bias is None else bias.data_ptr(),
+                                  float(r), float(f), float(p))
+    _abi.call("cc_logits_penalize_streams", _p(x), _p(y), T, V, stride, _DT[x.dtype], recs, _p(tokens), _p(pos), _stream())
+    return logits_2d if inplace else y
+
+
+def logits_constrain_streams(logits_2d, states, tokens, pos, out=None):
+    """logits_constrain for T <= 4 rows that belong to DIFFERENT sequences (cc_logits_constrain_streams; include/coldcompress.h has the
+    contract): row t sits at its own position pos[t] over states[t]'s history and carries the bits logits_constrain gives for that row
+    at T = 1 on that state; hist[pos[t]] = tokens[t] is stored.  states: T records, each None (no rules for the row) or
+    (hist, gen_start, ngram, ngram_from_gen, min_new_tokens, term_ids, bw_tokens, bw_offsets) as logits_constrain takes them; no two
+    records may share one hist.  pos: int32 DEVICE tensor of T elements; tokens: likewise, or None (the prefill's row).  out: None (a new
+    contiguous tensor) or `logits_2d` itself (in place).  -> out."""
+    what = "logits_constrain_streams"
+    if pos is None:
+        raise _abi.ColdCompressError(f"{what}: pos must hold every row's position")
+    x, y, T, V, stride, inplace = _streams_rows(what, logits_2d, states, tokens, pos, out)
+    recs = (_abi.ConstraintRow * T)()
+    hists = set()
+    for t, s in enumerate(states):
+        if s is None:
+            continue
+        hist, gen_start, ngram, ngram_from_gen, min_new_tokens, term_ids, bw_tokens, bw_offsets = s
+        _i32_ok(what, "hist", hist)
+        _i32_ok(what, "gen_start", gen_start, 1)
+        if hist.data_ptr() in hists:
+            raise _abi.ColdCompressError(f"{what}: record {t} shares its hist with another record: one object is one sequence's state")
+        hists.add(hist.data_ptr())
+        if term_ids is not None:
+            _i32_ok(what, "term_ids", term_ids)
+        if (bw_tokens is None) != (bw_offsets is None):
+            raise _abi.ColdCompressError(f"{what}: bw_tokens and bw_offsets come together")
+        n_bw = 0
+        if bw_tokens is not None:
+            _i32_ok(what, "bw_tokens", bw_tokens)
+            _i32_ok(what, "bw_offsets", bw_offsets)
+            n_bw = bw_offsets.numel() - 1
+            if n_bw < 0 or bw_tokens.numel() > CONSTRAIN_MAX_BW_TOKENS:
+                raise _abi.ColdCompressError(f"{what}: bw_offsets needs n + 1 elements and bw_tokens at most {CONSTRAIN_MAX_BW_TOKENS}")
+        ptr = lambda t_: None if t_ is None else t_.data_ptr()  # noqa: E731
+        recs[t] = _abi.ConstraintRow(hist.data_ptr(), hist.numel(), gen_start.data_ptr(), int(ngram), int(bool(ngram_from_gen)),
+                                     int(min_new_tokens), ptr(term_ids), 0 if term_ids is None else term_ids.numel(), ptr(bw_tokens),
+                                     ptr(bw_offsets), n_bw)
+    _abi.call("cc_logits_constrain_streams", _p(x), _p(y), T, V, stride, _DT[x.dtype], recs, _p(tokens), _p(pos), _stream())
     return logits_2d if inplace else y

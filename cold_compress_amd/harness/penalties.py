@@ -120,6 +120,11 @@ class LogitPenalties:
         self.gen_start.copy_(snap[2])
         self._prompt = snap[3]
 
+    def record(self):
+        """This sequence's row of glue.logits_penalize_streams: the state's tensors and the settings as the kernel receives them."""
+        return (self.prompt_count, self.gen_count, self.gen_start, self.repetition_penalty, self.frequency_penalty, self.presence_penalty,
+                self.bias)
+
     # ---- the step
     def apply(self, logits, tokens=None, pos=None):
         """logits [1, T, V], T <= 4: the rows of T steps; tokens / pos: those steps' input tokens and positions (T elements each, on the

@@ -6,16 +6,86 @@ or n different prompts (batch) through `Transformer.forward_streams` — every d
 rows, every stream's cache step the existing launch on that stream's own cache — and one `cc_sample_rows` call per step.  Every
 stream ends exactly where a lone `generate()` run of it ends: tokens, per-step probability rows or scores, and every cache buffer of
 every layer, bit for bit."""
+import collections
 import time
 
 import torch
 
 from .. import _abi
 from . import glue
+from .constraints import LogitConstraints, active as _active_constraints
 from .generation import (TokenScores, _clone_scores, _collective_status, _restore_l2_handoff, decode_one_token, greedy, sample,
                          token_logprobs)
+from .penalties import LogitPenalties, active as _active_penalties
 
 MAX_STREAMS = glue.GEMV_MULTI_MAX_T
+
+# The logit processors of n streams (DESIGN §2.29): per stream a LogitPenalties / LogitConstraints or None (a neutral object is None
+# here), and `key`, every object's settings as the kernels receive them — a captured step carries them by value, so two of these
+# compare equal exactly where one captured step serves both (the objects themselves compare by identity).
+Processors = collections.namedtuple("Processors", "pens cons key")
+
+
+def processors(pens, cons):
+    """-> the Processors of these per-stream objects (two sequences of n entries), or None where no stream has any."""
+    pens, cons = tuple(_active_penalties(p) for p in pens), tuple(_active_constraints(c) for c in cons)
+    if all(o is None for o in pens + cons):
+        return None
+    key = tuple(None if o is None else tuple(x.data_ptr() if torch.is_tensor(x) else x for x in o.record()) for o in pens + cons)
+    return Processors(pens, cons, key)
+
+
+def _per_stream(name, v, n, cls, vocab_size):
+    """generate_streams' `penalties` / `constraints` -> n entries (an object of `cls` or None each), or ValueError."""
+    if v is None:
+        return (None,) * n
+    if isinstance(v, cls):
+        raise ValueError(f"generate_streams: {name} takes a list of {n} entries, one {cls.__name__} (or None) per stream — one object is "
+                         f"one sequence's state; got a single {cls.__name__}")
+    if not isinstance(v, (list, tuple)) or any(o is not None and not isinstance(o, cls) for o in v):
+        raise ValueError(f"generate_streams: {name} must be a list or tuple of {cls.__name__} objects or None, one per stream")
+    if len(v) != n:
+        raise ValueError(f"generate_streams: {n} streams need {n} entries of {name}, got {len(v)}")
+    given = [o for o in v if o is not None]
+    if len({id(o) for o in given}) != len(given):
+        raise ValueError(f"generate_streams: one {cls.__name__} appears twice in {name}: one object is one sequence's state")
+    for o in given:
+        if o.vocab_size != vocab_size:
+            raise ValueError(f"generate_streams: {name} for a vocabulary of {o.vocab_size}, the model's has {vocab_size}")
+    return tuple(v)
+
+
+def _processed(logits, tok, pos, proc):
+    """The rows the tokens are chosen from behind the streams' processors: row t of logits [1, n, V] penalised against stream t's
+    counts and constrained over stream t's history, as decode_one_token does it for that stream alone (penalties first, constraints
+    in place behind them; without penalties the constraints write a new tensor).  tok: the rows' input tokens [1, n], counted and
+    stored at pos [n] — or None for the prefill's row, whose prompt the objects hold already.  -> [1, n, V], or None without `proc`.
+    Device tensors: one launch per stage whatever n is (and the copy when constraints run alone); CPU tensors: the objects' own host
+    contract, row by row."""
+    if proc is None:
+        return None
+    pens, cons = proc.pens, proc.cons
+    n = logits.shape[1]
+    tokens = None if tok is None else tok.reshape(-1).to(torch.int32).contiguous()
+    pos = pos.reshape(-1).to(torch.int32).contiguous()
+    has_pen, has_con = any(p is not None for p in pens), any(c is not None for c in cons)
+    if logits.is_cuda:
+        out = logits[0]
+        if has_pen:
+            out = glue.logits_penalize_streams(out, [None if p is None else p.record() for p in pens], tokens, None if tokens is None else pos)
+        if has_con:
+            out = glue.logits_constrain_streams(out, [None if c is None else c.record() for c in cons], tokens, pos, out=out if has_pen else None)
+        return out.unsqueeze(0)
+    rows = []
+    for t in range(n):
+        row = logits[:, t:t + 1]
+        tk, ps = None if tokens is None else tokens[t:t + 1], pos[t:t + 1]
+        chosen = pens[t].apply(row, tk, ps) if pens[t] is not None else None
+        if cons[t] is not None:
+            chosen = cons[t].apply(chosen, tk, ps, out=chosen) if chosen is not None else cons[t].apply(row, tk, ps)
+        rows.append(row if chosen is None else chosen)
+    return torch.cat(rows, dim=1)
+
 
 # host-side step state that reset() and the fused pipelines maintain beside the registered buffers
 _HOST_STATE = ("_next_valid", "_quant_pending", "_state_fused")
@@ -100,17 +170,20 @@ def _copy_cache_state(a, b):
         b._next_valid = False
 
 
-def _choose(logits, pos, seeds, temperature, top_k, top_p, min_p, logprobs):
+def _choose(logits, pos, seeds, temperature, top_k, top_p, min_p, logprobs, chosen_from=None):
     """Row t of logits [1, n, V] -> its token, drawn as the lone step draws it (greedy, or seeded at pos[t] under seeds[t]), and what
-    the lone step returns beside it.  -> (tokens [n] int32, probs [n, V]) or, with `logprobs`, (tokens, TokenScores of n)."""
+    the lone step returns beside it.  -> (tokens [n] int32, probs [n, V]) or, with `logprobs`, (tokens, TokenScores of n).
+    `chosen_from` (_processed): the rows behind the streams' logit processors — the tokens and the probability rows are theirs, the
+    scores stay the model's own rows' (generation._scored)."""
     n = logits.shape[1]
+    pick = logits if chosen_from is None else chosen_from
     if temperature is None:  # (softmax_argmax once per row: a rows form of that kernel is not part of this)
-        picks = [greedy(logits[:, t:t + 1], None) for t in range(n)]
+        picks = [greedy(pick[:, t:t + 1], None) for t in range(n)]
         tokens, probs = torch.cat([p[0].view(1) for p in picks]), torch.stack([p[1] for p in picks])
     elif logits.is_cuda:
-        probs, tokens = glue.sample_rows(logits[0], temperature, top_k, top_p, min_p, seeds, pos.to(torch.int32).contiguous())
+        probs, tokens = glue.sample_rows(pick[0], temperature, top_k, top_p, min_p, seeds, pos.to(torch.int32).contiguous())
     else:
-        picks = [sample(logits[:, t:t + 1], None, temperature, top_k, seeds[t], pos[t:t + 1], top_p=top_p, min_p=min_p) for t in range(n)]
+        picks = [sample(pick[:, t:t + 1], None, temperature, top_k, seeds[t], pos[t:t + 1], top_p=top_p, min_p=min_p) for t in range(n)]
         tokens, probs = torch.cat([p[0].view(1) for p in picks]), torch.stack([p[1] for p in picks])
     if logprobs:
         return tokens, TokenScores(*token_logprobs(logits, None, tokens))
@@ -119,24 +192,35 @@ def _choose(logits, pos, seeds, temperature, top_k, top_p, min_p, logprobs):
 
 def _joint_step(model, streams, tok, pos, settings, attn_top_k=1.0):
     logits = model.forward_streams(tok, pos, streams, attn_top_k=attn_top_k)
-    return _choose(logits, pos, *settings)
+    proc = settings[6] if len(settings) > 6 else None
+    return _choose(logits, pos, *settings[:6], chosen_from=_processed(logits, tok, pos, proc))
 
 
 class GraphedStreamsDecoder:
     """ONE joint step (Transformer.forward_streams + the sampling tail) of n streams captured in a hipGraph, on GraphedDecoder's
     pattern: the tokens `tok` [1, n] and positions `pos` [n] live in static device tensors that every kernel reads, the seeds and
     sampling settings are carried by value (other settings: capture again).  The warm-up steps run on a snapshot of all n cache sets;
-    the state handed in is restored whether or not the capture succeeds.  The captured work is one linear stream of launches."""
+    the state handed in is restored whether or not the capture succeeds.  The captured work is one linear stream of launches.
+    `penalties` / `constraints`: per stream an object or None (`processors`).  The captured tail then holds the two streams launches
+    with the addresses of the objects' buffers and their settings by value, all part of `settings`: other objects, or the same ones
+    with other settings, capture again.  The warm-up steps count their inputs into the penalties' tables, so every stream's object
+    is snapshotted beside the caches and restored with them; the constraints' histories need nothing (§2.21: the warm-up steps store
+    positions at and behind the captured one, which the replays write again before anything reads them)."""
 
-    def __init__(self, model, streams, seeds, temperature=None, top_k=None, top_p=None, min_p=None, logprobs=False, warmup=2):
+    def __init__(self, model, streams, seeds, temperature=None, top_k=None, top_p=None, min_p=None, logprobs=False, warmup=2,
+                 penalties=None, constraints=None):
         self.model, self.streams, self.warmup = model, streams, warmup
         self.settings = (tuple(int(s) for s in seeds), temperature, top_k, top_p, min_p, bool(logprobs))
+        none = (None,) * streams.n
+        proc = processors(none if penalties is None else penalties, none if constraints is None else constraints)
+        if proc is not None:  # (a seventh element only where a stream has a processor: six-element settings stay what they were)
+            self.settings += (proc,)
         dev = model.output.weight.device
         self.tok = torch.zeros((1, streams.n), dtype=torch.int32, device=dev)
         self.pos = torch.zeros((streams.n,), dtype=torch.int32, device=dev)
         self.graph = None
         self.out_tok = self.out_probs = None
-        self.replays = 0
+        self.replays = self.captures = 0
 
     def _caches(self):
         return [(t, c) for t, caches in enumerate(self.streams.sets) for c in caches]
@@ -165,6 +249,10 @@ class GraphedStreamsDecoder:
         snap = [{k: v.clone() for k, v in c._buffers.items() if v is not None} for c in caches]
         flags = [(getattr(c, "_next_valid", None), getattr(c, "_quant_pending", False)) for c in caches]
         pos0 = self.pos.clone()
+        proc = self.settings[6] if len(self.settings) > 6 else None
+        pens = [p for p in proc.pens if p is not None] if proc is not None else []
+        pen_snaps = [p.snapshot() for p in pens]  # (the warm-up steps and the captured step would be counted)
+        self.captures += 1
         try:
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
@@ -181,6 +269,8 @@ class GraphedStreamsDecoder:
             self._w12_epoch = self._weights_epoch()
         finally:  # also when the capture is refused: the caller falls back to eager joint steps and must find the state it handed in
             self.pos.copy_(pos0)
+            for p, sn in zip(pens, pen_snaps):
+                p.restore(sn)
             for c, sn, fl in zip(caches, snap, flags):
                 for k, v in sn.items():
                     c._buffers[k].copy_(v)
@@ -213,13 +303,16 @@ class GraphedStreamsDecoder:
 
 def decode_streams(model, streams, tok, pos, num_steps, settings, terminator_ids=None, dec=None, joint=True, attn_top_k=1.0, log=print):
     """Up to `num_steps` lock-step decode steps of streams.n streams from the tokens `tok` [1, n] at the positions `pos` [n]
-    (generate_streams' loop; tools/bench_streams.py times it).  settings: (seeds, temperature, top_k, top_p, min_p, logprobs).
+    (generate_streams' loop; tools/bench_streams.py times it).  settings: (seeds, temperature, top_k, top_p, min_p, logprobs) and,
+    where a stream has logit processors, `processors(...)` as a seventh element (the objects hold their sequences' state already).
     `dec`: a GraphedStreamsDecoder whose captured step is replayed (a refused capture: eager joint steps from there on, a line through
     `log`); `joint` False: one stream at a time through activate(s) + decode_one_token.
     -> (per step the tokens [n], per step the rows [n, V] or TokenScores of n, per stream the number of steps it keeps or None while
     it has not emitted a terminator, the decoder or None)."""
     n = streams.n
-    seeds, temperature, top_k, top_p, min_p, logprobs = settings
+    seeds, temperature, top_k, top_p, min_p, logprobs = settings[:6]
+    proc = settings[6] if len(settings) > 6 else None  # (a seventh element: the streams' logit processors, `processors`)
+    pens, cons = (proc.pens, proc.cons) if proc is not None else ((None,) * n, (None,) * n)
     skw = dict(temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p, logprobs=logprobs)
     device = tok.device
     on_device = device.type == "cuda"
@@ -248,7 +341,8 @@ def decode_streams(model, streams, tok, pos, num_steps, settings, terminator_ids
             try:
                 for s in range(n):
                     streams.activate(s)
-                    outs.append(decode_one_token(model, tok[:, s:s + 1], pos[s:s + 1], attn_top_k=attn_top_k, seed=seeds[s], **skw))
+                    outs.append(decode_one_token(model, tok[:, s:s + 1], pos[s:s + 1], attn_top_k=attn_top_k, seed=seeds[s],
+                                                 penalties=pens[s], constraints=cons[s], **skw))
             finally:
                 streams.activate(0)
             nt = torch.cat([o[0].view(1) for o in outs])
@@ -267,7 +361,7 @@ def decode_streams(model, streams, tok, pos, num_steps, settings, terminator_ids
     return step_toks, step_probs, kept, dec
 
 
-_NOT_SERVED = ("penalties", "constraints", "top_logprobs", "next_tokens", "feed_long_prompts", "decode_first_token")
+_NOT_SERVED = ("top_logprobs", "next_tokens", "feed_long_prompts", "decode_first_token")
 
 
 @torch.no_grad()
@@ -286,11 +380,21 @@ def generate_streams(model, prompts, prefill, max_new_tokens, n_streams=None, se
     every joint step and a set word raises, with the step's positions: a joint step cannot be rewound token-wise.
     A model that is not `streams_eligible` (int4 weights without `model.block_int4`, a cache quantising in reference mode, attn_top_k < 1, more than one rank)
     runs its streams one at a time per step through activate(s) + decode_one_token: the same results, no speed-up.
-    Not served (ValueError before any launch): penalties, constraints, top_logprobs, next_tokens, feed_long_prompts,
-    decode_first_token — their state is per sequence — and a prompt exactly as long as the smallest cache, which generate() splits
-    into a prefill and a forced step.  On return stream 0 is active: the model is as a plain generate() leaves it.
-    `streams`: a DecodeStreams to use (default: one built for this call)."""
+    `penalties` / `constraints`: a LIST or TUPLE of n entries, each a LogitPenalties / LogitConstraints or None, one
+    per stream — one object is one sequence's state, so a single object, a wrong length, one object twice, a vocabulary that is not
+    the model's or constraints whose `max_positions` is below the stream's prompt length + max_new_tokens raise ValueError before the
+    prefill.  Every object is reset with its stream's prompt (gen_start = the prompt's length), as generate() resets it; stream s then
+    equals generate(..., penalties=<its object>, constraints=<its object>).  A joint step puts its n rows through ONE
+    cc_logits_penalize_streams and ONE cc_logits_constrain_streams launch, both captured with the step; a neutral object is None.
+    A finished stream keeps stepping, so its objects' state runs on past its terminator: afterwards it is NOT the lone run's.
+    Not served (ValueError before any launch): top_logprobs, next_tokens, feed_long_prompts, decode_first_token — their state is per
+    sequence — and a prompt exactly as long as the smallest cache, which generate() splits into a prefill and a forced step.  On
+    return stream 0 is active: the model is as a plain generate() leaves it.
+    `streams`: a DecodeStreams to use (default: one built for this call).  `decoder`: a GraphedStreamsDecoder built for `streams` to
+    use instead of a new one — its captured step is replayed where the settings are the ones it was captured with, the processors'
+    among them, and captured again where they are not."""
     attn_top_k = kw.pop("attn_top_k", 1.0)
+    penalties, constraints, decoder = kw.pop("penalties", None), kw.pop("constraints", None), kw.pop("decoder", None)
     for name in _NOT_SERVED:
         v = kw.pop(name, None)
         if v is not None and v is not False:
@@ -326,9 +430,22 @@ def generate_streams(model, prompts, prefill, max_new_tokens, n_streams=None, se
             raise ValueError(f"generate_streams: a prompt of {p.numel()} tokens is as long as the smallest cache ({min_cache_length}): "
                              "generate() splits it and forces its last token through a decode step, which is not served here")
     device, dtype = plist[0].device, plist[0].dtype
+    vocab_size = model.output.weight.shape[0]
+    pens = _per_stream("penalties", penalties, n, LogitPenalties, vocab_size)
+    cons = _per_stream("constraints", constraints, n, LogitConstraints, vocab_size)
+    for s, c in enumerate(cons):
+        L = int(plist[0 if fork else s].numel())
+        if _active_constraints(c) is not None and L + int(max_new_tokens) > c.max_positions:
+            raise ValueError(f"generate_streams: stream {s}: {L} prompt tokens and {max_new_tokens} new ones do not fit the constraints' "
+                             f"max_positions = {c.max_positions}")
+    if decoder is not None and (decoder.model is not model or (streams is not None and decoder.streams is not streams)):
+        raise ValueError("generate_streams: decoder was built for another model or another DecodeStreams")
+    proc = processors(pens, cons)
     if streams is None:
-        streams = DecodeStreams(model, n)
-    settings = (tuple(seeds), temperature, top_k, top_p, min_p, bool(logprobs))
+        streams = decoder.streams if decoder is not None else DecodeStreams(model, n)
+        if streams.n != n:
+            raise ValueError(f"generate_streams: the decoder's DecodeStreams holds {streams.n} streams, the call asks for {n}")
+    settings = (tuple(seeds), temperature, top_k, top_p, min_p, bool(logprobs)) + (() if proc is None else (proc,))
     skw = dict(temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p, logprobs=bool(logprobs))
     on_device = device.type == "cuda"
     joint = bool(model.streams_eligible(streams, attn_top_k))
@@ -340,9 +457,14 @@ def generate_streams(model, prompts, prefill, max_new_tokens, n_streams=None, se
 
     try:
         # ---- prefill and the n first tokens
+        lengths = [int(p.numel()) for p in plist] * (n if fork else 1)
+        if proc is not None:  # every stream's objects hold its prompt; positions from its length on count as generated (generate())
+            for s, objs in enumerate(zip(proc.pens, proc.cons)):
+                for o in objs:
+                    if o is not None:
+                        o.reset(plist[0 if fork else s], lengths[s])
         sync()
         t0 = time.perf_counter()
-        lengths = [int(p.numel()) for p in plist] * (n if fork else 1)
         if fork:
             L = lengths[0]
             streams.activate(0)
@@ -355,14 +477,16 @@ def generate_streams(model, prompts, prefill, max_new_tokens, n_streams=None, se
             streams.fork(0)
             row = last[-1]
             pos = torch.full((n,), L - 1, dtype=torch.int32, device=device)
-            first_tok, first_probs = _choose(row.expand(1, n, row.shape[-1]).contiguous(), pos, *settings)
+            rows = row.expand(1, n, row.shape[-1]).contiguous()  # (the prompt is counted and stored already: tok None)
+            first_tok, first_probs = _choose(rows, pos, *settings[:6], chosen_from=_processed(rows, None, pos, proc))
             first_tok = first_tok.clone()
             first_probs = _clone_scores(first_probs) if logprobs else first_probs.clone()
         else:
             toks, rows = [], []
             for s, p in enumerate(plist):
                 streams.activate(s)
-                ret = prefill(model, p.view(1, -1), torch.arange(0, p.numel(), device=device), seed=seeds[s], **skw)
+                pkw = dict(penalties=proc.pens[s], constraints=proc.cons[s]) if proc is not None else {}
+                ret = prefill(model, p.view(1, -1), torch.arange(0, p.numel(), device=device), seed=seeds[s], **pkw, **skw)
                 toks.append(ret[0].clone().view(1))
                 rows.append(_clone_scores(ret[1]) if logprobs else ret[1].clone())
             streams.activate(0)
@@ -374,7 +498,10 @@ def generate_streams(model, prompts, prefill, max_new_tokens, n_streams=None, se
         # ---- joint steps
         tok = first_tok.view(1, n).to(torch.int32)
         pos = torch.tensor(lengths, dtype=torch.int32, device=device)
-        dec = GraphedStreamsDecoder(model, streams, seeds, temperature, top_k, top_p, min_p, logprobs) if (graph and on_device and joint) else None
+        dec = None
+        if graph and on_device and joint:
+            dec = decoder if decoder is not None else GraphedStreamsDecoder(model, streams, seeds, temperature, top_k, top_p, min_p, logprobs,
+                                                                            penalties=pens, constraints=cons)
         step_toks, step_probs, kept, dec = decode_streams(model, streams, tok, pos, int(max_new_tokens) - 1, settings, terminator_ids, dec,
                                                           joint, attn_top_k, log)
         sync()
@@ -402,7 +529,8 @@ def generate_streams(model, prompts, prefill, max_new_tokens, n_streams=None, se
     total, prefilled = sum(counts), sum(int(p.numel()) for p in plist)
     stats = {
         "prefill_tokens": prefilled, "decode_tokens": counts, "streams": n, "joint_steps": bool(joint),
-        "graphed": dec is not None and dec.graph is not None, "decode_tokens_total": total,
+        "graphed": dec is not None and dec.graph is not None, "captures": dec.captures if dec is not None else 0,
+        "decode_tokens_total": total,
         "prefill_toks_per_sec": prefilled / (t1 - t0), "decode_toks_per_sec": total / (t2 - t1),
         "total_toks_per_sec": total / (t2 - t0), "total_seconds": t2 - t0, "prefill_seconds": t1 - t0,
         "decode_seconds": t2 - t1, "decode_seconds_frac_of_total": (t2 - t1) / (t2 - t0),

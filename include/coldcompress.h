@@ -1199,6 +1199,59 @@ int cc_logits_constrain(const void* logits, void* out, int32_t T, int32_t V, int
                         int32_t ngram_from_gen, int32_t min_new_tokens, const int32_t* term_ids, int32_t n_term,
                         const int32_t* bw_tokens, const int32_t* bw_offsets, int32_t n_bw, cc_stream_t stream);
 
+/* The two logit processors for rows that belong to DIFFERENT sequences: the joint step of up to CC_GEMV_MULTI_MAX_T decode streams,
+ * whose row t has its own counts, its own history, its own gen_start and its own position.  cc_logits_penalize reads its T rows as T
+ * consecutive steps of ONE sequence and cc_logits_constrain takes their positions as pos[0] + t over ONE history; here the grid's
+ * second index is the row and selects the row's state, as in cc_sample_rows, and a row's arithmetic does not depend on T.
+ *
+ * `rows` is a HOST array of T records, 1 <= T <= CC_GEMV_MULTI_MAX_T, copied into the kernel arguments by value before the call
+ * returns.  The pointers INSIDE a record are device pointers, which a captured launch holds: they must live as long as the graph.
+ * The settings in a record travel by value: other settings, another capture.  logits / out / T / V / row_stride / dtype are the
+ * single-sequence entry points'; tokens[T] / pos[T] are device int32, read by the kernels (a captured call advances through them).
+ *
+ * THE CONTRACT of both: row t of a T-row call carries exactly the bits, in `out` and in the state, that the single-sequence entry
+ * point writes when it is called with T = 1 for that row (logits + t * row_stride, tokens + t, pos + t) on rows[t]'s state.
+ *
+ * cc_logits_penalize_streams: row t is penalised against rows[t] alone by the per-element formula above (same operations, same
+ * rounding points, fp32 first and then one rounding to the dtype).  tokens[t] at pos[t] is counted into rows[t]'s tables before the
+ * row is computed — generated when pos[t] >= *rows[t].gen_start — and the count is stored only where it changed.  tokens NULL: nothing
+ * is counted (the prefill's row).  A record whose prompt_count is NULL means no penalties for that row: it is copied bit for bit
+ * (out != logits) or left alone (in place), and the record's other fields are not looked at.  One launch on a (groups of 16 bytes, T)
+ * grid: an element of a row has one owner; no atomics, no workspace, plain vector stores; 16-byte loads where the base of a row, of a
+ * count table or of a bias is 16-byte aligned, element by element where it is not.  Refused before any launch: everything
+ * cc_logits_penalize refuses, per record, a NULL rows, and — CC_ERR_BAD_ARG — two records that name one table (prompt_count or
+ * gen_count, in either role): two rows would race on it.
+ *
+ * cc_logits_constrain_streams: row t sits at its OWN position p = pos[t]; its history is rows[t].hist[0 .. p-1] followed by tokens[t]
+ * (tokens NULL: hist[0 .. p]), and the bans are cc_logits_constrain's: -inf of the dtype, every other element keeps its bits, an id
+ * outside [0, V) bans nothing, a position outside [0, cap) leaves the row as it is and stores nothing.  The launch stores
+ * hist[pos[t]] = tokens[t] for each row; no workgroup reads that position back from hist: it is taken from tokens.  A record whose
+ * hist is NULL passes its row through.  A copy of the rows when out != logits, then one launch on a (max over rows of the slice
+ * count + 1, T) grid; no workgroup waits for another.  Refused before any launch: everything cc_logits_constrain refuses, per
+ * record, a NULL rows, and two records that share one hist. */
+typedef struct cc_penalty_row_t {
+  int32_t* prompt_count;    /* NULL: no penalties for this row */
+  int32_t* gen_count;
+  const int32_t* gen_start;
+  const float* bias;        /* float[V] or NULL */
+  float r, f, p;            /* repetition_penalty, frequency_penalty, presence_penalty */
+} cc_penalty_row_t;
+typedef struct cc_constraint_row_t {
+  int32_t* hist;            /* NULL: no rules for this row */
+  int32_t cap;
+  const int32_t* gen_start;
+  int32_t ngram, ngram_from_gen, min_new_tokens;
+  const int32_t* term_ids;
+  int32_t n_term;
+  const int32_t* bw_tokens;
+  const int32_t* bw_offsets;
+  int32_t n_bw;
+} cc_constraint_row_t;
+int cc_logits_penalize_streams(const void* logits, void* out, int32_t T, int32_t V, int64_t row_stride, int32_t dtype,
+                               const cc_penalty_row_t* rows, const int32_t* tokens, const int32_t* pos, cc_stream_t stream);
+int cc_logits_constrain_streams(const void* logits, void* out, int32_t T, int32_t V, int64_t row_stride, int32_t dtype,
+                                const cc_constraint_row_t* rows, const int32_t* tokens, const int32_t* pos, cc_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * One-shot sum all-reduce over the GPUs of ONE node, for the decode-size messages of tensor parallelism.
  * ref: tp.py:134-138, 156-160 (`all_reduce(sum)` of the wo and FFN outputs: 2 * dim bytes, 8-16 KiB, twice per layer).
